@@ -11,10 +11,13 @@ gallery, row-sharded over the ranks (HIP; RCCL all-gather of queries and of per-
 on-device merge) -> fused (lat, lon, sin, cos) head (HIP).  Weak scaling: B per GPU is fixed.
 Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` for the dominant
 hand-written kernel (the HBM-bound kNN score kernel, timed live with HIP events inside the timed
-region), `kernels` (one roofline row per other hand-written stage; the SALAD row is measured live
-inside the timed region too), `recall_at_1` (planted positives, through all-gather + merge when the
-gallery is sharded), `dist` (process group, ranks it really has, exchange time per step) and
+region).  A plain run does nothing else: set-up, warm-up, the timed steps, the line.
+--full adds what is measured or checked after the timed region: `kernels` (one roofline row per other
+hand-written stage; the SALAD row is measured live inside the timed region too), `stages`,
+`recall_at_1` (planted positives, through all-gather + merge when the gallery is sharded),
+`uncertified_queries`, `dist` (process group, ranks it really has, exchange time per step) and
 `cpu_baseline` (oracle/ + the same backbone on the host cores, bounded sample).
+--dump-outputs DIR writes what the last timed step returned (rank 0's StepOutput) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -40,6 +43,7 @@ D_DESC = 8448
 MFMA_BF16_PEAK_TFLOPS = 2500.0      # dense bf16, MI355X_MICROARCH.md
 MFMA_FP8_PEAK_TFLOPS = 5000.0       # dense fp8 (block-scaled f8f6f4 MFMA), same guide
 HBM_PEAK_GBPS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_BYTES = 64 << 20      # --dump-outputs writes at most this much in all
 
 
 class _StdoutToStderr:
@@ -109,6 +113,24 @@ def cpu_baseline(ext_state, arch, head_mods, images_cpu, gallery_sample_cpu, n_t
                       f"fp32 brute-force kNN on {gallery_sample_cpu.shape[0]} of {n_total} gallery rows scaled x"
                       f"{n_total / gallery_sample_cpu.shape[0]:.0f} ({t_knn:.2f}s); torch {torch.__version__} CPU, "
                       f"{threads} threads"}
+
+
+def dump_outputs(path: str, out) -> None:
+    """The StepOutput of the last timed step as <path>/<name>.npy: f32 arrays as f32, the int32 indices as f64 (exact).
+    Above DUMP_BYTES, the same fixed, seeded sample of query rows from every array, listed in sample_rows.npy."""
+    import numpy as np
+    arrays = {"descriptors": out.descriptors.float(), "topk_scores": out.topk_scores.float(),
+              "topk_indices": out.topk_indices.double(), "pose": out.pose.float()}
+    rows = out.descriptors.shape[0]
+    row_bytes = sum(t[0].numel() * t.element_size() for t in arrays.values())
+    if rows * row_bytes > DUMP_BYTES:
+        cap = (DUMP_BYTES - 4096) // (row_bytes + 8)          # 4 KB for the .npy headers, 8 B per row for sample_rows
+        keep = torch.randperm(rows, generator=torch.Generator().manual_seed(0))[:cap].sort().values
+        arrays = {n: t[keep.to(t.device)] for n, t in arrays.items()}
+        arrays["sample_rows"] = keep.double()
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def _avg_ms(fn, n=10, warm=2):
@@ -422,6 +444,11 @@ def main():
                          "merge} (BASELINE config 5: --knn-dtype fp8 --gallery 1000000 --graph-retrieval on 8 GPUs)")
     ap.add_argument("--no-kernel-rows", action="store_true", help="skip the per-kernel roofline rows measured after the timed region")
     ap.add_argument("--fp8-rows", type=int, default=1_000_000, help="gallery rows of the e4m3 kNN row (BASELINE config 5 on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure / check: Recall@1, uncertified queries, per-stage times, the "
+                         "collective probe, per-kernel roofline rows and the CPU baseline (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (rank 0) to DIR/<name>.npy, f32 / f64, at most 64 MB")
     a = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and (a.gpus > 1 or a.force_dist):
@@ -460,7 +487,7 @@ def main():
     for p in ext32.aggregator.parameters():                # SALAD weights ~ N(0, 0.02), dustbin 1
         if p.dim() > 0:
             nn.init.normal_(p, std=0.02)
-    ext_state = {k: v.clone() for k, v in ext32.state_dict().items()}
+    ext_state = {k: v.clone() for k, v in ext32.state_dict().items()} if a.full else None    # f32 weights for cpu_baseline
     ext = ext32.to(dev).to(torch.bfloat16)
     ext.backbone.residual_in_gemm = not a.no_resid_gemm
     ext.backbone.hip_split = not a.no_split
@@ -530,7 +557,11 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out)
 
+    # The score-stage and SALAD events were recorded inside the timed steps in every run, so the timed path is the same
+    # with or without --full; reading them back costs no run of its own.
     knn_ms = sorted(e0.elapsed_time(e1) for e0, e1 in pipe.knn_events)
     knn_avg_s = sum(knn_ms) / len(knn_ms) * 1e-3
     pipe.knn_events = None
@@ -572,76 +603,80 @@ def main():
                     "frac": flops / knn_avg_s / 1e12 / peak, "traffic": None,
                     "kernel_ms": knn_avg_s * 1e3, "algorithmic_flops": flops}
 
-    # Planted-positive Recall@1 THROUGH THE SHARDED PATH (outside the timed region; every rank takes part): rank r plants
-    # its B queries next to rows of ITS OWN shard, so the all-gathered batch has its positives spread over all shards;
-    # every query is searched on every shard, the per-shard top-k are all-gathered and merged, and each rank checks its own
-    # rows of the merged answer against the global index it planted.  The reported value is the mean over all ranks.
-    gp = torch.Generator(device=dev).manual_seed(7 + rank)
-    pos_idx = torch.randint(0, n_shard, (a.batch,), device=dev, generator=gp)
-    qn = torch.nn.functional.normalize(shard[pos_idx].float() + 0.1 * torch.randn(a.batch, D_DESC, device=dev, generator=gp), dim=1)
-    _, ti = gallery.search_local_queries(qn.to(torch.bfloat16), 1)
-    hits = (ti[:, 0].long() == pos_idx + lo).double().sum().reshape(1)
-    if use_dist:
-        dist.all_reduce(hits, op=dist.ReduceOp.SUM)
-    recall1 = float(hits.item()) / (a.batch * world)
-    uncertified = gallery.uncertified_queries()                 # summed over the group when the gallery is sharded (a collective)
-    dist_info = {"process_group": (a.backend if use_dist else None), "collectives_in_step": gallery.collective,
-                 "ranks_seen": world if not use_dist else None, "collective_ms_per_step": None}
-    if gallery.collective:
-        dist_info.update(collective_probe(gallery, a.batch, a.k, dev))
+    res = {
+        "metric": "images/sec end-to-end (backbone->SALAD->kNN->pose)",
+        "value": a.steps * a.batch * world / elapsed, "unit": "images/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "bf16" if a.knn_dtype == "bf16" else "bf16 (backbone, SALAD) + fp8 e4m3 kNN", "data": "synthetic",
+        "config": {"workload": f"DINOv2 {a.arch}/14 (random init) + SALAD + {a.knn_dtype} kNN k={a.k} over a "
+                               f"{a.gallery}-row x {D_DESC} synthetic gallery sharded {world} way(s) + fused "
+                               f"(lat,lon,sin,cos) head; 3x224x224 bf16 images",
+                   "batch_per_gpu": a.batch, "global_batch": a.batch * world, "gallery_rows": a.gallery,
+                   "k": a.k, "parallelism": f"dp{world}+gallery-shard{world}", "batches_in_flight": a.in_flight,
+                   "graph_retrieval": bool(a.graph_retrieval)},
+        "roofline": roofline,
+    }
+    if a.full:
+        # Planted-positive Recall@1 THROUGH THE SHARDED PATH (outside the timed region; every rank takes part): rank r plants
+        # its B queries next to rows of ITS OWN shard, so the all-gathered batch has its positives spread over all shards;
+        # every query is searched on every shard, the per-shard top-k are all-gathered and merged, and each rank checks its own
+        # rows of the merged answer against the global index it planted.  The reported value is the mean over all ranks.
+        gp = torch.Generator(device=dev).manual_seed(7 + rank)
+        pos_idx = torch.randint(0, n_shard, (a.batch,), device=dev, generator=gp)
+        qn = torch.nn.functional.normalize(shard[pos_idx].float() + 0.1 * torch.randn(a.batch, D_DESC, device=dev, generator=gp), dim=1)
+        _, ti = gallery.search_local_queries(qn.to(torch.bfloat16), 1)
+        hits = (ti[:, 0].long() == pos_idx + lo).double().sum().reshape(1)
+        if use_dist:
+            dist.all_reduce(hits, op=dist.ReduceOp.SUM)
+        recall1 = float(hits.item()) / (a.batch * world)
+        uncertified = gallery.uncertified_queries()                 # summed over the group when the gallery is sharded (a collective)
+        dist_info = {"process_group": (a.backend if use_dist else None), "collectives_in_step": gallery.collective,
+                     "ranks_seen": world if not use_dist else None, "collective_ms_per_step": None}
+        if gallery.collective:
+            dist_info.update(collective_probe(gallery, a.batch, a.k, dev))
 
+        if rank == 0:
+
+            # per-stage device time (one extra step each, outside the timed region)
+            def stage_ms(fn, n=3):
+                fn(); torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(n):
+                    r = fn()
+                e1.record(); torch.cuda.synchronize()
+                return e0.elapsed_time(e1) / n, r
+            stages = {}
+            stages["backbone_ms"], tokens = stage_ms(lambda: ext.backbone(images, split=True))
+            stages["salad_ms"], (desc, desc16) = stage_ms(lambda: ext.aggregator(tokens, want_bf16=True))
+            if world == 1:
+                stages["knn_ms"], _ = stage_ms(lambda: gallery.search(desc16, a.k))
+            stages["head_ms"], _ = stage_ms(lambda: head(desc))
+
+            res.update({
+                "recall_at_1": recall1,
+                "recall_path": "search_local_queries: query all-gather -> shard search on every rank -> top-k all-gather -> merge; "
+                               "positives planted in every shard" if gallery.collective else "local search (one shard, no collectives)",
+                "uncertified_queries": uncertified,    # kNN answers the device could not certify exact, all shards (0 expected)
+                "stages": stages,
+                "dist": dist_info,
+            })
+            if world == 1 and not a.no_kernel_rows:
+                try:                                                # auxiliary rows never cost the run its headline line
+                    res["kernels"] = kernel_rows(dev, ext, head, images, shard if a.knn_dtype == "bf16" else None, a, salad_step_ms)
+                except Exception as e:                              # noqa: BLE001
+                    res["kernels"] = {"error": f"{type(e).__name__}: {e}"}
+            if world == 1 and not a.no_cpu_baseline:
+                sample = shard.cpu()                                # whole gallery: the sample is one full step
+                res["cpu_baseline"] = cpu_baseline(ext_state, a.arch, head_cpu, images.cpu(), sample, a.gallery, a.k)
+                try:
+                    res["cpu_baseline"]["config1_swin_tiny"] = config1_swin_tiny(dev)
+                except Exception as e:                              # noqa: BLE001  (e.g. transformers missing on the box)
+                    res["cpu_baseline"]["config1_swin_tiny"] = {"error": f"{type(e).__name__}: {e}"}
+            else:
+                res["cpu_baseline"] = None
     if rank == 0:
-
-        # per-stage device time (one extra step each, outside the timed region)
-        def stage_ms(fn, n=3):
-            fn(); torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(n):
-                r = fn()
-            e1.record(); torch.cuda.synchronize()
-            return e0.elapsed_time(e1) / n, r
-        stages = {}
-        stages["backbone_ms"], tokens = stage_ms(lambda: ext.backbone(images, split=True))
-        stages["salad_ms"], (desc, desc16) = stage_ms(lambda: ext.aggregator(tokens, want_bf16=True))
-        if world == 1:
-            stages["knn_ms"], _ = stage_ms(lambda: gallery.search(desc16, a.k))
-        stages["head_ms"], _ = stage_ms(lambda: head(desc))
-
-        res = {
-            "metric": "images/sec end-to-end (backbone->SALAD->kNN->pose)",
-            "value": a.steps * a.batch * world / elapsed, "unit": "images/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "bf16" if a.knn_dtype == "bf16" else "bf16 (backbone, SALAD) + fp8 e4m3 kNN", "data": "synthetic",
-            "config": {"workload": f"DINOv2 {a.arch}/14 (random init) + SALAD + {a.knn_dtype} kNN k={a.k} over a "
-                                   f"{a.gallery}-row x {D_DESC} synthetic gallery sharded {world} way(s) + fused "
-                                   f"(lat,lon,sin,cos) head; 3x224x224 bf16 images",
-                       "batch_per_gpu": a.batch, "global_batch": a.batch * world, "gallery_rows": a.gallery,
-                       "k": a.k, "parallelism": f"dp{world}+gallery-shard{world}", "batches_in_flight": a.in_flight,
-                       "graph_retrieval": bool(a.graph_retrieval)},
-            "roofline": roofline,
-            "recall_at_1": recall1,
-            "recall_path": "search_local_queries: query all-gather -> shard search on every rank -> top-k all-gather -> merge; "
-                           "positives planted in every shard" if gallery.collective else "local search (one shard, no collectives)",
-            "uncertified_queries": uncertified,    # kNN answers the device could not certify exact, all shards (0 expected)
-            "stages": stages,
-            "dist": dist_info,
-        }
-        if world == 1 and not a.no_kernel_rows:
-            try:                                                # auxiliary rows never cost the run its headline line
-                res["kernels"] = kernel_rows(dev, ext, head, images, shard if a.knn_dtype == "bf16" else None, a, salad_step_ms)
-            except Exception as e:                              # noqa: BLE001
-                res["kernels"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not a.no_cpu_baseline:
-            sample = shard.cpu()                                # whole gallery: the sample is one full step
-            res["cpu_baseline"] = cpu_baseline(ext_state, a.arch, head_cpu, images.cpu(), sample, a.gallery, a.k)
-            try:
-                res["cpu_baseline"]["config1_swin_tiny"] = config1_swin_tiny(dev)
-            except Exception as e:                              # noqa: BLE001  (e.g. transformers missing on the box)
-                res["cpu_baseline"]["config1_swin_tiny"] = {"error": f"{type(e).__name__}: {e}"}
-        else:
-            res["cpu_baseline"] = None
         print(json.dumps(res), flush=True)
     if use_dist:
         dist.barrier()

@@ -25,7 +25,7 @@ python3 $R/scripts/pmc_summary.py --fetch $O/${TAG}_pmc8_fetch --write $O/${TAG}
   --command "rocprofv3 --pmc FETCH_SIZE|WRITE_SIZE --kernel-trace --output-format csv -- python3 scripts/kernel_bench.py --only knn8 --N8 1000000 --iters 3"
 cp $O/${TAG}_knn8_pmc.json $R/profiles/${POUT}_knn8_pmc.json
 echo "pmc fp8 1M done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof_bench -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/${TAG}_prof_bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof_bench -- python3 $R/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > $O/${TAG}_prof_bench.log 2>&1
 echo "bench trace done"
 # matrix-pipe utilisation of the MFMA kernels (SALAD GEMMs, Sinkhorn aggregation, kNN score kernel)
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_BF16 --kernel-trace --output-format csv -d $O/${TAG}_pmc_mfma -- python3 $R/scripts/kernel_bench.py --only knn,salad --iters 5 > $O/${TAG}_pmc_mfma.log 2>&1

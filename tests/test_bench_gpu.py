@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +25,7 @@ def _json_line(out: str) -> dict:
 
 
 def test_bench_single_rank_contract(dev):
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + SMALL,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full"] + SMALL,
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     d = _json_line(p.stdout)
@@ -51,6 +52,32 @@ def test_bench_single_rank_contract(dev):
     assert rows["salad_aggregate"]["bound"] == "mfma" and rows["knn_topk_fp8"]["uncertified_queries"] == 0
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_what_they_computed(dev, tmp_path):
+    """Without --full the line holds the headline and the roofline read from the timed steps' events, nothing measured
+    after them; --dump-outputs writes the last timed step's StepOutput.  The same arguments with --full (whose extra
+    work all comes after the timed region) dump the same arrays: same seeded inputs, same timed path."""
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-kernel-rows"])):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs", str(tmp_path / mode)]
+                           + extra + SMALL, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-3000:]
+        if mode == "plain":
+            d = _json_line(p.stdout)
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"} <= set(d)
+    assert not {"recall_at_1", "uncertified_queries", "stages", "dist", "kernels", "cpu_baseline"} & set(d)
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["roofline"]["kernel_ms"] > 0
+    assert abs(d["value"] - 8 * 2 / (d["ms_per_step"] * 2e-3)) < 1e-6 * d["value"]
+    load = lambda mode, name: np.load(tmp_path / mode / f"{name}.npy")
+    assert sorted(os.listdir(tmp_path / "plain")) == ["descriptors.npy", "pose.npy", "topk_indices.npy", "topk_scores.npy"]
+    desc, scores, idx, pose = (load("plain", n) for n in ("descriptors", "topk_scores", "topk_indices", "pose"))
+    assert desc.shape == (8, 8448) and desc.dtype == np.float32 and np.isfinite(desc).all()
+    assert scores.shape == idx.shape == (8, 10) and idx.dtype == np.float64 and (np.diff(scores, axis=1) <= 0).all()
+    assert ((idx >= 0) & (idx < 3000) & (idx == np.round(idx))).all()
+    assert pose.shape == (8, 4) and np.allclose(pose[:, 2] ** 2 + pose[:, 3] ** 2, 1.0, atol=1e-5)   # unit (sin, cos)
+    for name in ("descriptors", "topk_scores", "pose"):
+        np.testing.assert_allclose(load("full", name), load("plain", name), rtol=1e-5, atol=1e-6, err_msg=name)
+    np.testing.assert_array_equal(load("full", "topk_indices"), idx)
+
+
 def test_bench_force_dist_runs_the_collectives_on_rccl(dev):
     """--force-dist: one rank, but a real RCCL process group and both all-gathers + the merge inside every step."""
     s = socket.socket()
@@ -58,7 +85,7 @@ def test_bench_force_dist_runs_the_collectives_on_rccl(dev):
     port = s.getsockname()[1]
     s.close()
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--no-cpu-baseline",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--force-dist", "--no-cpu-baseline",
                         "--no-kernel-rows"] + SMALL, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     d = _json_line(p.stdout)
@@ -71,7 +98,7 @@ def test_bench_force_dist_runs_the_collectives_on_rccl(dev):
     assert "merge" in d["recall_path"]
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["recall_at_1"] == 1.0 and d["uncertified_queries"] == 0
     # two batches in flight on two streams, each step with its collectives on the one process group
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--no-cpu-baseline",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--force-dist", "--no-cpu-baseline",
                         "--no-kernel-rows", "--in-flight", "2"] + SMALL + ["--steps", "6"], capture_output=True, text=True,
                        timeout=600, cwd=ROOT, env=dict(env, MASTER_PORT=str(port + 1)))
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
@@ -88,7 +115,7 @@ def test_bench_config5_flags_graph_retrieval_with_collectives(dev):
     port = s.getsockname()[1]
     s.close()
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--knn-dtype", "fp8",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--force-dist", "--knn-dtype", "fp8",
                         "--graph-retrieval", "--no-cpu-baseline", "--no-kernel-rows"] + SMALL,
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
@@ -100,7 +127,7 @@ def test_bench_config5_flags_graph_retrieval_with_collectives(dev):
 
 def test_bench_fp8_gallery(dev):
     """--knn-dtype fp8: e4m3 shard + per-row scales through the same pipeline; planted neighbours still found."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--knn-dtype", "fp8",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--knn-dtype", "fp8",
                         "--no-cpu-baseline"] + SMALL, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     d = _json_line(p.stdout)
@@ -111,7 +138,7 @@ def test_bench_fp8_gallery(dev):
 
 def test_bench_two_batches_in_flight(dev):
     """--in-flight 2: consecutive steps on two streams (per-stream workspaces, per-stream side chain)."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--in-flight", "2",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--in-flight", "2",
                         "--no-cpu-baseline"] + SMALL + ["--steps", "4"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     d = _json_line(p.stdout)
@@ -122,8 +149,8 @@ def test_bench_four_ranks_gloo_rehearsal(dev):
     """Four ranks on the one GPU (gloo), bare launch: four gallery shards (uneven: 3001 rows), 32 gathered queries per
     shard scan, Recall@1 through the 4-way merge with positives in every shard, counters summed over the group."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--backend", "gloo", "--no-cpu-baseline", "--no-kernel-rows",
-           "--steps", "2", "--warmup", "1", "--arch", "vit_small", "--gallery", "3001", "--batch", "8", "--no-tune"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--full", "--backend", "gloo", "--no-cpu-baseline",
+           "--no-kernel-rows", "--steps", "2", "--warmup", "1", "--arch", "vit_small", "--gallery", "3001", "--batch", "8", "--no-tune"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     d = _json_line(p.stdout)
@@ -142,7 +169,7 @@ def test_bench_two_ranks_gloo_rehearsal(dev, launcher):
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--no-cpu-baseline"] + SMALL
+    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--backend", "gloo", "--no-cpu-baseline"] + SMALL
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                "127.0.0.1", "--master-port", str(port)] + tail

@@ -135,3 +135,39 @@ def test_bench_spawns_its_own_ranks(monkeypatch):
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and int(cmd[cmd.index("--master-port") + 1]) > 0
     assert cmd[-4:] == ["--gpus", "8", "--steps", "5"] and cmd[-5].endswith("bench.py")
     assert "OMP_NUM_THREADS" in seen["env"]
+
+
+def test_bench_dump_outputs_writes_the_step_output_within_64_mb(tmp_path):
+    """bench.dump_outputs: the StepOutput of the last timed step as f32 / f64 .npy files.  A batch too large for 64 MB in all
+    is cut to the same seeded query rows in every file (sample_rows.npy), the same rows from run to run."""
+    import os
+    import numpy as np
+    import bench
+    from vpr_amd.pipeline import StepOutput
+
+    def step_output(B, k=10):
+        g = torch.Generator().manual_seed(B)
+        return StepOutput(torch.randn(B, 8448, generator=g), torch.randn(B, k, generator=g),
+                          torch.randint(0, 100_000, (B, k), dtype=torch.int32, generator=g), torch.randn(B, 4, generator=g))
+
+    small = step_output(8)
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    assert sorted(os.listdir(tmp_path / "small")) == ["descriptors.npy", "pose.npy", "topk_indices.npy", "topk_scores.npy"]
+    for name, dtype in (("descriptors", np.float32), ("topk_scores", np.float32), ("topk_indices", np.float64), ("pose", np.float32)):
+        arr = np.load(tmp_path / "small" / f"{name}.npy")
+        assert arr.dtype == dtype
+        np.testing.assert_array_equal(arr, getattr(small, name).numpy().astype(dtype))
+
+    big = step_output(2048)                                             # 69 MB of descriptors alone
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["descriptors.npy", "pose.npy", "sample_rows.npy", "topk_indices.npy", "topk_scores.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    rows = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert rows.dtype == np.float64 and 1500 < len(rows) < 2048 and (np.diff(rows) > 0).all()
+    for f in files:
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    rows = rows.astype(np.int64)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "descriptors.npy"), big.descriptors.numpy()[rows])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "topk_indices.npy"), big.topk_indices.numpy()[rows].astype(np.float64))
