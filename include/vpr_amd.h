@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define VPR_AMD_ABI_VERSION 3
+#define VPR_AMD_ABI_VERSION 4
 
 typedef enum vpr_status {
   VPR_OK = 0,
@@ -375,6 +375,37 @@ int vpr_head_train_epoch(const float* X, long long x_stride, const int* order, i
                          float* W1, float* b1, float* W2, float* b2, float* m, float* v, int first_step,
                          double lr, double beta1, double beta2, double eps, double weight_decay,
                          int loss_kind, double huber_delta, float* losses, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same step / pass with nn.Dropout(dropout_p) in training mode after the ReLU: the head
+ * Linear(D,hidden) -> ReLU -> Dropout(p) -> Linear(hidden,n_out) of dinov2salad_finetuning_2.py:113-122 and
+ * swin_transformer/swin_attempt_2.py:114-123 (model.train()).
+ *   forward  h = relu(W1 x + b1), hd = h * mask * s, preds = W2 hd + b2, s = 1 / (1 - p)
+ *   backward dW2 = dO^T hd, dz = (dO W2) * mask * s * [z > 0]; loss, AdamW and summation orders as above.
+ * Mask: a pure function of (seed, step, b, j) — not of the launch geometry, so an epoch call equals the same steps called
+ * one by one, bit for bit:
+ *   generator  Philox4x32-10 (Random123 constants: multipliers 0xD2511F53, 0xCD9E8D57; Weyl key increments 0x9E3779B9,
+ *              0xBB67AE85); key = (seed & 0xffffffff, seed >> 32); counter = (j >> 2, b, step, 0); r = output word j & 3,
+ *              with j the hidden unit, b the position in the batch (0 .. B-1) and step the 1-based step of this update
+ *              (first_step + i for batch i of an epoch call);
+ *   keep       unit (b, j) is kept iff r >= t, t = (uint32) floor(p * 2^32) formed in double;
+ *   scale      s = 1 / (1 - p) formed in double and rounded to f32 once.
+ *   Known answers of the generator: counter 0, key 0 -> 6627e8d5 e169c58d bc57ac4c 9b00dbd8; counter (243f6a88, 85a308d3,
+ *   13198a2e, 03707344), key (a4093822, 299f31d0) -> d16cfe09 94fdcceb 5001e420 24126ea1.
+ * Valid range 0 <= dropout_p < 1 (anything else, NaN included: VPR_ERR_INVALID_ARG).  dropout_p = 0 computes exactly what
+ * vpr_head_train_step / _epoch compute.  mask_out (device uint8 [B, hidden], may be NULL) receives the mask (1 = kept).
+ * Same shapes, workspace and status codes as the plain entry points. */
+int vpr_head_train_step_dropout(const float* X, long long x_stride, const int* idx, const float* Y, long long y_stride,
+                                int B, int D, int hidden, int n_out, float* W1, float* b1, float* W2, float* b2,
+                                float* m, float* v, int step, double lr, double beta1, double beta2, double eps,
+                                double weight_decay, int loss_kind, double huber_delta, float* loss_out,
+                                double dropout_p, uint64_t seed, uint8_t* mask_out, void* workspace,
+                                size_t workspace_bytes, void* stream);
+int vpr_head_train_epoch_dropout(const float* X, long long x_stride, const int* order, int n, int batch_size,
+                                 const float* Y, long long y_stride, int D, int hidden, int n_out,
+                                 float* W1, float* b1, float* W2, float* b2, float* m, float* v, int first_step,
+                                 double lr, double beta1, double beta2, double eps, double weight_decay,
+                                 int loss_kind, double huber_delta, float* losses, double dropout_p, uint64_t seed,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Swin pooler + linear head: pooled = mean_t LayerNorm(x[b,t,:]) ; out = Wh * pooled + bh

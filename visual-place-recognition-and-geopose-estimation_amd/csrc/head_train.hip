@@ -14,6 +14,11 @@
 //                                by designated workgroups
 // HBM-bound: algorithmic bytes per step = hidden*D*4 (forward read of W1) + 6*hidden*D*4 (W1, m, v read and written)
 // + 2*B*D*4 (the batch rows, forward and backward) — 121.7 MB at D = 8448, hidden = 512, B = 16.
+//
+// vpr_head_train_step_dropout / vpr_head_train_epoch_dropout: the same step with nn.Dropout(p) in training mode after the ReLU
+// (dinov2salad_finetuning_2.py:113-122, swin_attempt_2.py:114-123).  head_mid_kernel draws the keep mask where it forms h and
+// hands on hd = h * mask / (1 - p); the update kernel scales dz by 1 / (1 - p) (hd > 0 exactly where the unit is kept and
+// z > 0, and hd already feeds the gradient of W2).  The mask is a pure function of (seed, step, b, j): Philox4x32-10.
 #include <math.h>
 #include "vpr_common.h"
 #include "vpr_internal.h"
@@ -113,11 +118,36 @@ __global__ __launch_bounds__(256) void head_fwd_partial_kernel(
 // Hand-over: the partials go out as agent-scope (write-through) stores, vmcnt(0) = acknowledged, relaxed agent-scope
 // ticket, acquire fence in the last workgroup (the protocol of pose_fused_kernel).  The counter is zeroed by the forward
 // kernel of the same step (stream order) and left alone otherwise: the workspace needs no initialisation.
+// DROP: dropout after the ReLU (HeadDropout): unit (b, h) is kept iff philox word h & 3 of counter (h >> 2, b, step, 0) is
+// >= keep_t, and H / the partial outputs carry hd = h * s for a kept unit, 0 for a dropped one; mask_out (may be null) gets
+// the mask.  DROP = false is the plain step.
+struct HeadDropout { uint32_t t, k0, k1; int step; float s; uint8_t* mask_out; };
+
+// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants): ten rounds of two 32x32 -> 64 multiplies.
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
+    c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return c;
+}
+
+__device__ __forceinline__ bool dropout_keep(const HeadDropout& d, int b, int j) {
+  const uint4 r = philox4x32_10(make_uint4((uint32_t)j >> 2, (uint32_t)b, (uint32_t)d.step, 0u), d.k0, d.k1);
+  const int w = j & 3;
+  return (w == 0 ? r.x : w == 1 ? r.y : w == 2 ? r.z : r.w) >= d.t;
+}
+
+template <bool DROP>
 __global__ __launch_bounds__(256) void head_mid_kernel(
     const float* __restrict__ part, int nslice, const float* __restrict__ b1, const float* __restrict__ W2,
     const float* __restrict__ b2, const float* __restrict__ Y, long long y_stride, const int* __restrict__ idx,
     float* __restrict__ H, float* po, float* __restrict__ snap, float* __restrict__ diff, float* __restrict__ loss_out,
-    int* counter, int B, int hidden, int n_out, float huber_delta) {
+    int* counter, int B, int hidden, int n_out, float huber_delta, HeadDropout drop) {
   __shared__ float s_red[256];
   __shared__ int s_last;
   const int h0 = blockIdx.x * HT_H2, hl = threadIdx.x & 15, h = h0 + hl;
@@ -138,7 +168,12 @@ __global__ __launch_bounds__(256) void head_mid_kernel(
       for (int i = 0; i < 32; ++i)
         if (s0 + i < nslice) z += t[i];
     }
-    const float hv = valid ? fmaxf(z + bias, 0.f) : 0.f;
+    float hv = valid ? fmaxf(z + bias, 0.f) : 0.f;
+    if constexpr (DROP) {
+      const bool keep = dropout_keep(drop, b, h);
+      hv = keep ? hv * drop.s : 0.f;
+      if (valid && drop.mask_out) drop.mask_out[(long long)b * hidden + h] = keep ? 1 : 0;
+    }
     if (valid) H[(long long)b * hidden + h] = hv;
 #pragma unroll
     for (int o = 0; o < HT_MAXO; ++o)
@@ -225,7 +260,8 @@ struct HeadTrainArgs {
   const float* X; long long x_stride; const int* idx; const float* Y; long long y_stride;
   float *W1, *b1, *W2, *b2;
   float *m, *v;                         // moments, [W1 | b1 | W2 | b2]
-  const float *H, *diff, *snap;         // from head_mid_kernel: h, output - target, W2 before the update
+  const float *H, *diff, *snap;         // from head_mid_kernel: h (dropout: hd), output - target, W2 before the update
+  float drop_s;                         // dropout: 1 / (1 - p), the factor of dz (read by the DROP instantiation only)
   int B, D, hidden, n_out;
   AdamConsts c;
   int abl;                              // timing-only build (-DVPR_ABLATION): which part of the update kernel is left out
@@ -251,7 +287,7 @@ __device__ __forceinline__ void store4(float* p, const float4& v) {
   }
 }
 
-template <int IT, int BC, int RG, bool NT = false>
+template <int IT, int BC, int RG, bool NT = false, bool DROP = false>
 __global__ __launch_bounds__(256) void head_update_kernel(HeadTrainArgs a) {
   __shared__ float s_diff[HT_MAXB * HT_MAXO];
   __shared__ __attribute__((aligned(16))) float s_dz[HT_MAXB * IT];
@@ -286,7 +322,8 @@ __global__ __launch_bounds__(256) void head_update_kernel(HeadTrainArgs a) {
     const float hv = a.H[(long long)b * hidden + i0 + i];
     float g = 0.f;
     for (int o = 0; o < n_out; ++o) g += (s_diff[b * n_out + o] * gscale) * a.snap[(long long)o * hidden + i0 + i];
-    s_dz[t] = hv > 0.f ? g : 0.f;
+    if constexpr (DROP) s_dz[t] = hv > 0.f ? g * a.drop_s : 0.f;    // hd > 0 <=> kept and z > 0
+    else s_dz[t] = hv > 0.f ? g : 0.f;
     s_h[t] = hv;
   }
   __syncthreads();
@@ -379,9 +416,9 @@ __global__ __launch_bounds__(256) void head_update_kernel(HeadTrainArgs a) {
   }
 }
 
-template <int IT, int BC, int RG, bool NT = false>
+template <int IT, int BC, int RG, bool NT, bool DROP>
 static int launch_head_update(const HeadTrainArgs& a, hipStream_t stream) {
-  return launch_kernel(head_update_kernel<IT, BC, RG, NT>, dim3((a.D + HT_JT - 1) / HT_JT, a.hidden / IT), dim3(256), 0, stream, a);
+  return launch_kernel(head_update_kernel<IT, BC, RG, NT, DROP>, dim3((a.D + HT_JT - 1) / HT_JT, a.hidden / IT), dim3(256), 0, stream, a);
 }
 
 static int head_train_slices(int B, int D, int hidden) {
@@ -426,11 +463,34 @@ extern "C" long long vpr_head_train_state_floats(int D, int hidden, int n_out) {
   return (long long)hidden * D + hidden + (long long)n_out * hidden + n_out;
 }
 
+// Dropout of one call: p in [0, 1) (NaN and anything else refused); drop = false for the plain step (p = 0, no mask wanted).
+struct DropoutSpec { bool drop; uint32_t t; float s; uint64_t seed; uint8_t* mask_out; };
+static bool dropout_spec(double p, uint64_t seed, uint8_t* mask_out, DropoutSpec* d) {
+  if (!(p >= 0.0 && p < 1.0)) return false;
+  d->drop = p > 0.0 || mask_out != nullptr;
+  d->t = (uint32_t)floor(p * 4294967296.0);        // p * 2^32 < 2^32: fits
+  d->s = (float)(1.0 / (1.0 - p));
+  d->seed = seed;
+  d->mask_out = mask_out;
+  return true;
+}
+
+template <bool DROP>
+static int launch_head_update_variant(const HeadTrainArgs& a, hipStream_t stream) {
+  switch (tune_or(TUNE_HEAD_TRAIN_VARIANT, 0)) {        // A/B: rows per workgroup / batch rows per chunk / rows per load group
+    case 1:  return launch_head_update<8, 8, 8, false, DROP>(a, stream);
+    case 2:  return launch_head_update<4, 8, 4, false, DROP>(a, stream);
+    case 3:  return launch_head_update<8, 8, 4, true, DROP>(a, stream);
+    case 4:  return launch_head_update<16, 8, 4, false, DROP>(a, stream);
+    default: return launch_head_update<8, 8, 4, false, DROP>(a, stream);
+  }
+}
+
 static int head_train_step_impl(const float* X, long long x_stride, const int* idx, const float* Y, long long y_stride,
                                 int B, int D, int hidden, int n_out, float* W1, float* b1, float* W2, float* b2,
                                 float* m, float* v, int step, double lr, double beta1, double beta2, double eps,
-                                double weight_decay, int loss_kind, double huber_delta, float* loss_out, void* workspace,
-                                size_t workspace_bytes, hipStream_t stream) {
+                                double weight_decay, int loss_kind, double huber_delta, float* loss_out, const DropoutSpec& dsp,
+                                void* workspace, size_t workspace_bytes, hipStream_t stream) {
   if (!X || !Y || !W1 || !b1 || !W2 || !b2 || !m || !v || !workspace || step < 1) return VPR_ERR_INVALID_ARG;
   if (!(lr >= 0.0) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0))
     return VPR_ERR_INVALID_ARG;
@@ -459,13 +519,18 @@ static int head_train_step_impl(const float* X, long long x_stride, const int* i
   else
     VPR_TRY_LAUNCH(launch_kernel(head_fwd_partial_kernel<false>, dim3(hidden / HT_HT, p.ks, 1), dim3(256), 0, stream,
                                  X, x_stride, idx, (const float*)W1, part, B, D, hidden, sps, counter));
-  VPR_TRY_LAUNCH(launch_kernel(head_mid_kernel, dim3(p.nwg2), dim3(256), 0, stream, (const float*)part, p.ks, (const float*)b1,
-                               (const float*)W2, (const float*)b2, Y, y_stride, idx, H, po, snap, diff, loss_out, counter,
-                               B, hidden, n_out, loss_kind == VPR_LOSS_HUBER ? (float)huber_delta : 0.f));
+  HeadDropout hd;
+  hd.t = dsp.t; hd.k0 = (uint32_t)(dsp.seed & 0xffffffffu); hd.k1 = (uint32_t)(dsp.seed >> 32); hd.step = step;
+  hd.s = dsp.s; hd.mask_out = dsp.mask_out;
+  VPR_TRY_LAUNCH(launch_kernel(dsp.drop ? head_mid_kernel<true> : head_mid_kernel<false>, dim3(p.nwg2), dim3(256), 0, stream,
+                               (const float*)part, p.ks, (const float*)b1, (const float*)W2, (const float*)b2, Y, y_stride, idx, H, po,
+                               snap, diff, loss_out, counter, B, hidden, n_out,
+                               loss_kind == VPR_LOSS_HUBER ? (float)huber_delta : 0.f, hd));
   HeadTrainArgs a;
   a.X = X; a.x_stride = x_stride; a.idx = idx; a.Y = Y; a.y_stride = y_stride;
   a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.m = m; a.v = v;
   a.H = H; a.diff = diff; a.snap = snap; a.B = B; a.D = D; a.hidden = hidden; a.n_out = n_out;
+  a.drop_s = dsp.s;
   const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
   a.c.decay = (float)(1.0 - lr * weight_decay);
   a.c.one_minus_b1 = (float)(1.0 - beta1);
@@ -478,32 +543,16 @@ static int head_train_step_impl(const float* X, long long x_stride, const int* i
 #ifdef VPR_ABLATION
   if (tune_or(TUNE_HEAD_TRAIN_VARIANT, 0) >= 10) a.abl = tune_or(TUNE_HEAD_TRAIN_VARIANT, 0);
 #endif
-  switch (tune_or(TUNE_HEAD_TRAIN_VARIANT, 0)) {        // A/B: rows per workgroup / batch rows per chunk / rows per load group
-    case 1:  VPR_TRY_LAUNCH((launch_head_update<8, 8, 8>(a, stream))); break;
-    case 2:  VPR_TRY_LAUNCH((launch_head_update<4, 8, 4>(a, stream))); break;
-    case 3:  VPR_TRY_LAUNCH((launch_head_update<8, 8, 4, true>(a, stream))); break;
-    case 4:  VPR_TRY_LAUNCH((launch_head_update<16, 8, 4>(a, stream))); break;
-    default: VPR_TRY_LAUNCH((launch_head_update<8, 8, 4>(a, stream))); break;
-  }
+  VPR_TRY_LAUNCH(dsp.drop ? launch_head_update_variant<true>(a, stream) : launch_head_update_variant<false>(a, stream));
   return VPR_OK;
 }
 
-extern "C" int vpr_head_train_step(const float* X, long long x_stride, const int* idx, const float* Y, long long y_stride,
-                                   int B, int D, int hidden, int n_out, float* W1, float* b1, float* W2, float* b2,
-                                   float* m, float* v, int step, double lr, double beta1, double beta2, double eps,
-                                   double weight_decay, int loss_kind, double huber_delta, float* loss_out, void* workspace,
-                                   size_t workspace_bytes, void* stream) {
-  return head_train_step_impl(X, x_stride, idx, Y, y_stride, B, D, hidden, n_out, W1, b1, W2, b2, m, v, step, lr, beta1, beta2,
-                              eps, weight_decay, loss_kind, huber_delta, loss_out, workspace, workspace_bytes,
-                              static_cast<hipStream_t>(stream));
-}
-
-extern "C" int vpr_head_train_epoch(const float* X, long long x_stride, const int* order, int n, int batch_size,
-                                    const float* Y, long long y_stride, int D, int hidden, int n_out,
-                                    float* W1, float* b1, float* W2, float* b2, float* m, float* v, int first_step,
-                                    double lr, double beta1, double beta2, double eps, double weight_decay,
-                                    int loss_kind, double huber_delta, float* losses, void* workspace, size_t workspace_bytes,
-                                    void* stream) {
+static int head_train_epoch_impl(const float* X, long long x_stride, const int* order, int n, int batch_size,
+                                 const float* Y, long long y_stride, int D, int hidden, int n_out,
+                                 float* W1, float* b1, float* W2, float* b2, float* m, float* v, int first_step,
+                                 double lr, double beta1, double beta2, double eps, double weight_decay,
+                                 int loss_kind, double huber_delta, float* losses, const DropoutSpec& dsp, void* workspace,
+                                 size_t workspace_bytes, hipStream_t stream) {
   if (!order || n < 1 || batch_size < 1 || first_step < 1) return VPR_ERR_INVALID_ARG;
   const int nb = (n + batch_size - 1) / batch_size;
   if ((long long)first_step + nb - 1 > 2147483647LL) return VPR_ERR_INVALID_ARG;
@@ -517,8 +566,58 @@ extern "C" int vpr_head_train_epoch(const float* X, long long x_stride, const in
     const int B = n - lo < batch_size ? n - lo : batch_size;
     VPR_TRY_LAUNCH(head_train_step_impl(X, x_stride, order + lo, Y, y_stride, B, D, hidden, n_out, W1, b1, W2, b2, m, v,
                                         first_step + i, lr, beta1, beta2, eps, weight_decay, loss_kind, huber_delta,
-                                        losses ? losses + i : nullptr, workspace, workspace_bytes,
-                                        static_cast<hipStream_t>(stream)));
+                                        losses ? losses + i : nullptr, dsp, workspace, workspace_bytes, stream));
   }
   return VPR_OK;
+}
+
+extern "C" int vpr_head_train_step(const float* X, long long x_stride, const int* idx, const float* Y, long long y_stride,
+                                   int B, int D, int hidden, int n_out, float* W1, float* b1, float* W2, float* b2,
+                                   float* m, float* v, int step, double lr, double beta1, double beta2, double eps,
+                                   double weight_decay, int loss_kind, double huber_delta, float* loss_out, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  DropoutSpec none;
+  dropout_spec(0.0, 0, nullptr, &none);
+  return head_train_step_impl(X, x_stride, idx, Y, y_stride, B, D, hidden, n_out, W1, b1, W2, b2, m, v, step, lr, beta1, beta2,
+                              eps, weight_decay, loss_kind, huber_delta, loss_out, none, workspace, workspace_bytes,
+                              static_cast<hipStream_t>(stream));
+}
+
+extern "C" int vpr_head_train_epoch(const float* X, long long x_stride, const int* order, int n, int batch_size,
+                                    const float* Y, long long y_stride, int D, int hidden, int n_out,
+                                    float* W1, float* b1, float* W2, float* b2, float* m, float* v, int first_step,
+                                    double lr, double beta1, double beta2, double eps, double weight_decay,
+                                    int loss_kind, double huber_delta, float* losses, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+  DropoutSpec none;
+  dropout_spec(0.0, 0, nullptr, &none);
+  return head_train_epoch_impl(X, x_stride, order, n, batch_size, Y, y_stride, D, hidden, n_out, W1, b1, W2, b2, m, v, first_step,
+                               lr, beta1, beta2, eps, weight_decay, loss_kind, huber_delta, losses, none, workspace, workspace_bytes,
+                               static_cast<hipStream_t>(stream));
+}
+
+extern "C" int vpr_head_train_step_dropout(const float* X, long long x_stride, const int* idx, const float* Y, long long y_stride,
+                                           int B, int D, int hidden, int n_out, float* W1, float* b1, float* W2, float* b2,
+                                           float* m, float* v, int step, double lr, double beta1, double beta2, double eps,
+                                           double weight_decay, int loss_kind, double huber_delta, float* loss_out,
+                                           double dropout_p, uint64_t seed, uint8_t* mask_out, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+  DropoutSpec dsp;
+  if (!dropout_spec(dropout_p, seed, mask_out, &dsp)) return VPR_ERR_INVALID_ARG;
+  return head_train_step_impl(X, x_stride, idx, Y, y_stride, B, D, hidden, n_out, W1, b1, W2, b2, m, v, step, lr, beta1, beta2,
+                              eps, weight_decay, loss_kind, huber_delta, loss_out, dsp, workspace, workspace_bytes,
+                              static_cast<hipStream_t>(stream));
+}
+
+extern "C" int vpr_head_train_epoch_dropout(const float* X, long long x_stride, const int* order, int n, int batch_size,
+                                            const float* Y, long long y_stride, int D, int hidden, int n_out,
+                                            float* W1, float* b1, float* W2, float* b2, float* m, float* v, int first_step,
+                                            double lr, double beta1, double beta2, double eps, double weight_decay,
+                                            int loss_kind, double huber_delta, float* losses, double dropout_p, uint64_t seed,
+                                            void* workspace, size_t workspace_bytes, void* stream) {
+  DropoutSpec dsp;
+  if (!dropout_spec(dropout_p, seed, nullptr, &dsp)) return VPR_ERR_INVALID_ARG;
+  return head_train_epoch_impl(X, x_stride, order, n, batch_size, Y, y_stride, D, hidden, n_out, W1, b1, W2, b2, m, v, first_step,
+                               lr, beta1, beta2, eps, weight_decay, loss_kind, huber_delta, losses, dsp, workspace, workspace_bytes,
+                               static_cast<hipStream_t>(stream));
 }

@@ -61,7 +61,7 @@ def finetune_head(model: DINOv2RegressionModel, descriptors: torch.Tensor, label
                   epochs: int = 100, batch_size: int = 16, lr: float = 1e-5, save_dir: Optional[str] = None,
                   val: Optional[tuple] = None, seed: int = 0, log: Callable[[str], None] = print,
                   engine: str = "auto", loss: str = "mse", huber_delta: float = 1.0, weight_decay: float = 1e-2,
-                  lr_schedule: Optional[Callable[[int, list], float]] = None) -> dict:
+                  lr_schedule: Optional[Callable[[int, list], float]] = None, dropout_seed: Optional[int] = None) -> dict:
     """Trains model.regressor on cached descriptors.  labels [N,2] raw (lat, lon); they are
     standardised with a scaler fitted here (returned and, if save_dir, dumped as JSON).
     val = (val_descriptors, val_labels_raw) for the per-epoch de-normalised report.
@@ -72,7 +72,12 @@ def finetune_head(model: DINOv2RegressionModel, descriptors: torch.Tensor, label
     loss: "mse" (dinov2salad_finetuning.py:96) or "huber" with huber_delta (nn.HuberLoss(delta): dinov2salad_finetuning_2.py:154,
     swin_attempt_2.py:158); weight_decay: AdamW's (:95 default 0.01; _2.py:153 passes it explicitly).
     lr_schedule(epoch, history) -> lr for that epoch (host-side schedules such as the ReduceLROnPlateau of _2.py:155,236 are a
-    few lines of Python on the validation history; the learning rate is an argument of every training call)."""
+    few lines of Python on the validation history; the learning rate is an argument of every training call).
+    Dropout: the HIP engine also trains Linear -> ReLU -> Dropout(p) -> Linear (the _2 scripts' head, dinov2salad_finetuning_2.py
+    :113-122, swin_attempt_2.py:114-123; modules.SwinMLPRegressionModel), p read from the module at every pass.  Its masks are
+    a pure function of (dropout_seed, step, position in the batch, hidden unit) (include/vpr_amd.h); dropout_seed None = derived
+    from `seed` (default_dropout_seed), so a run is reproducible from its arguments.  The torch engine draws its masks from
+    torch's RNG: once p > 0 the two engines agree in distribution, not bit for bit."""
     if loss not in ("mse", "huber"):
         raise ValueError(f"finetune_head: loss must be 'mse' or 'huber', got {loss!r}")
     dev = descriptors.device
@@ -83,6 +88,10 @@ def finetune_head(model: DINOv2RegressionModel, descriptors: torch.Tensor, label
     if engine == "hip" and not descriptors.is_cuda:
         raise RuntimeError("finetune_head: the training step is a HIP kernel and needs the descriptors on the GPU (there is no CPU "
                            "fallback); engine='torch' runs the PyTorch-autograd loop instead, on any device")
+    if dropout_seed is None:
+        dropout_seed = default_dropout_seed(seed)
+    if not 0 <= int(dropout_seed) < 1 << 64:
+        raise ValueError(f"finetune_head: dropout_seed must be an unsigned 64-bit integer, got {dropout_seed!r}")
     scaler = LatLonScaler.fit(labels)
     y = torch.from_numpy(scaler.transform(np.asarray(labels, dtype=np.float64)).astype(np.float32)).to(dev)
     head = model.regressor.to(dev).float()
@@ -90,7 +99,8 @@ def finetune_head(model: DINOv2RegressionModel, descriptors: torch.Tensor, label
         p.requires_grad_(True)
     opt = torch.optim.AdamW(head.parameters(), lr=lr, weight_decay=weight_decay)
     loss_fn = nn.MSELoss() if loss == "mse" else nn.HuberLoss(delta=huber_delta)
-    hip = _HipHeadTrainer(head, descriptors.float().contiguous(), y, opt, loss, huber_delta) if engine == "hip" else None
+    hip = _HipHeadTrainer(head, descriptors.float().contiguous(), y, opt, loss, huber_delta, int(dropout_seed), batch_size) \
+        if engine == "hip" else None
     g = torch.Generator(device="cpu").manual_seed(seed)
     n = descriptors.shape[0]
     history = []
@@ -147,26 +157,53 @@ def finetune_head(model: DINOv2RegressionModel, descriptors: torch.Tensor, label
     return {"scaler": scaler, "history": history, "engine": engine, "optimizer": opt}
 
 
+def default_dropout_seed(seed: int) -> int:
+    """The dropout key finetune_head uses when it is given none: a fixed function of its `seed` (numpy's SeedSequence,
+    whose output is stable across numpy versions), a 64-bit value."""
+    return int(np.random.SeedSequence(int(seed) & 0xFFFFFFFFFFFFFFFF).generate_state(1, np.uint64)[0])
+
+
+def _hip_head_layout(head: nn.Module):
+    """(the two nn.Linear, the nn.Dropout or None) of a head the HIP step trains: Linear -> ReLU -> Linear
+    (dinov2salad_finetuning.py:28-32) or Linear -> ReLU -> Dropout(p) -> Linear (dinov2salad_finetuning_2.py:113-122,
+    swin_attempt_2.py:114-123).  Anything else raises and names the PyTorch engine."""
+    mods = list(head) if isinstance(head, (nn.Sequential, nn.ModuleList)) else []
+    kinds = (nn.Linear, nn.ReLU, nn.Dropout, nn.Linear)
+    if len(mods) == 3 and all(isinstance(m, k) for m, k in zip(mods, kinds[:2] + kinds[3:])):
+        return [mods[0], mods[2]], None
+    if len(mods) == 4 and all(isinstance(m, k) for m, k in zip(mods, kinds)):
+        return [mods[0], mods[3]], mods[2]
+    got = " -> ".join(type(m).__name__ for m in mods) or type(head).__name__
+    raise RuntimeError("finetune_head(engine='hip'): the HIP training step trains Linear -> ReLU -> Linear and "
+                       f"Linear -> ReLU -> Dropout(p) -> Linear heads, not {got}; "
+                       'engine="torch" trains any head with the PyTorch-autograd loop')
+
+
 class _HipHeadTrainer:
     """The HIP training step driven over an epoch: parameters are the nn.Linear tensors themselves (updated in place by the
     kernels), AdamW moments live in two flat buffers ([W1 | b1 | W2 | b2]) and are copied into a torch.optim.AdamW's state
     only when a checkpoint wants `optimizer.state_dict()` (the reference's checkpoint dict, :130-135)."""
 
     def __init__(self, head: nn.Module, X: torch.Tensor, Y: torch.Tensor, opt: torch.optim.Optimizer, loss: str = "mse",
-                 huber_delta: float = 1.0):
+                 huber_delta: float = 1.0, dropout_seed: int = 0, batch_size: int = 1):
         from . import ops, torch_ops  # noqa: F401  (torch_ops registers torch.ops.vpr.*)
-        lin = [m for m in head if isinstance(m, nn.Linear)]
-        rest = [m for m in head if not isinstance(m, (nn.Linear, nn.ReLU))]
-        if len(lin) != 2 or rest or not isinstance(head[1], nn.ReLU):
-            raise RuntimeError("finetune_head(engine='hip'): the head must be Linear -> ReLU -> Linear (dinov2salad_finetuning.py:28-32)")
+        lin, self.dropout = _hip_head_layout(head)
+        hidden, D = lin[0].weight.shape
+        n_out = lin[1].weight.shape[0]
+        if ops._lib.lib().vpr_head_train_workspace_bytes(min(batch_size, X.shape[0]), D, hidden, n_out) == 0:
+            raise RuntimeError(f"finetune_head(engine='hip'): no HIP training step for batch {batch_size}, D={D}, hidden={hidden}, "
+                               f"n_out={n_out} (needs batch <= 64, D % 16 == 0, hidden % 32 == 0, n_out <= 8); "
+                               f'engine="torch" trains it with the PyTorch-autograd loop')
         self.ops, self.opt, self.X, self.Y = ops, opt, X, Y.contiguous()
         self.params = [lin[0].weight, lin[0].bias, lin[1].weight, lin[1].bias]
         for p in self.params:
             if p.dtype != torch.float32 or not p.is_contiguous() or not p.is_cuda:
-                raise RuntimeError("finetune_head(engine='hip'): head parameters must be contiguous f32 GPU tensors")
+                raise RuntimeError("finetune_head(engine='hip'): head parameters must be contiguous f32 GPU tensors "
+                                   '(engine="torch" trains any head)')
         self.W1, self.b1, self.W2, self.b2 = (p.detach() for p in self.params)     # aliases that share the parameters' version counters
         self.m, self.v = ops.head_train_state(self.W1, self.W2)
         self.loss, self.huber_delta = loss, float(huber_delta)
+        self.dropout_seed = dropout_seed - (1 << 64) if dropout_seed >= 1 << 63 else dropout_seed   # the op's int is signed
         self.step = 0
 
     @property
@@ -179,9 +216,13 @@ class _HipHeadTrainer:
         DataLoader's default does: :89).  Returns the batch losses (device tensor; nothing here waits for the GPU)."""
         perm32 = perm.to(device=self.X.device, dtype=torch.int32).contiguous()
         h = self.hyper              # through the operator layer: the dispatcher sees the six in-place updates (version counters)
-        losses = torch.ops.vpr.head_train_epoch(self.X, self.Y, perm32, batch_size, self.W1, self.b1, self.W2, self.b2, self.m,
-                                                self.v, self.step + 1, h["lr"], h["betas"][0], h["betas"][1], h["eps"],
-                                                h["weight_decay"], self.loss, self.huber_delta)
+        args = (self.X, self.Y, perm32, batch_size, self.W1, self.b1, self.W2, self.b2, self.m, self.v, self.step + 1, h["lr"],
+                h["betas"][0], h["betas"][1], h["eps"], h["weight_decay"], self.loss, self.huber_delta)
+        p = float(self.dropout.p) if self.dropout is not None and self.dropout.training else 0.0
+        if p > 0.0:                 # masks keyed by the global step: a new mask every batch, across epochs too
+            losses = torch.ops.vpr.head_train_epoch_dropout(*args, p, self.dropout_seed)
+        else:
+            losses = torch.ops.vpr.head_train_epoch(*args)
         self.step += losses.numel()
         return losses
 

@@ -678,14 +678,28 @@ def _head_train_check(X, Y, W1, b1, W2, b2, m, v):
     return D, hidden, n_out
 
 
+def _dropout_args(dropout_p: float, dropout_seed: int):
+    """(p, seed) of the *_dropout entry points: 0 <= p < 1, seed a uint64 (include/vpr_amd.h: the mask specification)."""
+    p = float(dropout_p)
+    if not (0.0 <= p < 1.0):
+        raise RuntimeError(f"head_train: dropout_p must satisfy 0 <= p < 1 (nn.Dropout in training mode), got {dropout_p!r}")
+    seed = int(dropout_seed)
+    if not (0 <= seed < 1 << 64):
+        raise RuntimeError(f"head_train: dropout_seed must be an unsigned 64-bit integer, got {dropout_seed!r}")
+    return p, seed
+
+
 def head_train_epoch(X: torch.Tensor, Y: torch.Tensor, order: torch.Tensor, batch_size: int, W1: torch.Tensor, b1: torch.Tensor,
                      W2: torch.Tensor, b2: torch.Tensor, m: torch.Tensor, v: torch.Tensor, first_step: int, lr: float = 1e-5,
                      betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, loss: str = "mse",
-                     huber_delta: float = 1.0) -> torch.Tensor:
+                     huber_delta: float = 1.0, dropout_p: float = 0.0, dropout_seed: int = 0) -> torch.Tensor:
     """One pass over the rows listed in `order` (int32, device) in batches of `batch_size` (vpr_head_train_epoch: the whole
     launch sequence enqueued by ONE library call).  Returns the batch losses [ceil(n / batch_size)] (device tensor; nothing
-    waits for the GPU).  The caller guarantees 0 <= order < X.shape[0]: the kernels gather rows by these indices unchecked."""
+    waits for the GPU).  The caller guarantees 0 <= order < X.shape[0]: the kernels gather rows by these indices unchecked.
+    dropout_p > 0: nn.Dropout(dropout_p) in training mode after the ReLU, masks drawn from (dropout_seed, step, position in
+    the batch, hidden unit) as include/vpr_amd.h specifies (vpr_head_train_epoch_dropout)."""
     D, hidden, n_out = _head_train_check(X, Y, W1, b1, W2, b2, m, v)
+    p_drop, seed = _dropout_args(dropout_p, dropout_seed)
     _need(order, torch.int32, "order", 1)
     n = order.numel()
     if n < 1 or batch_size < 1:
@@ -697,11 +711,15 @@ def head_train_epoch(X: torch.Tensor, Y: torch.Tensor, order: torch.Tensor, batc
                            "(need 1 <= B <= 64, D % 16 == 0, hidden % 32 == 0, n_out <= 8)")
     ws = workspace("head_train", nbytes, X.device)
     losses = torch.empty((n + batch_size - 1) // batch_size, dtype=torch.float32, device=X.device)
-    st = L.vpr_head_train_epoch(_ptr(X), X.stride(0), _ptr(order), n, int(batch_size), _ptr(Y), Y.stride(0), D, hidden, n_out,
-                                _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(m), _ptr(v), int(first_step), float(lr),
-                                float(betas[0]), float(betas[1]), float(eps), float(weight_decay), _loss_kind(loss),
-                                float(huber_delta), _ptr(losses), _ptr(ws), ws.numel(), _stream())
-    _lib.check(st, "vpr_head_train_epoch")
+    args = (_ptr(X), X.stride(0), _ptr(order), n, int(batch_size), _ptr(Y), Y.stride(0), D, hidden, n_out,
+            _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(m), _ptr(v), int(first_step), float(lr),
+            float(betas[0]), float(betas[1]), float(eps), float(weight_decay), _loss_kind(loss), float(huber_delta), _ptr(losses))
+    if p_drop == 0.0:
+        st = L.vpr_head_train_epoch(*args, _ptr(ws), ws.numel(), _stream())
+        _lib.check(st, "vpr_head_train_epoch")
+    else:
+        st = L.vpr_head_train_epoch_dropout(*args, p_drop, seed, _ptr(ws), ws.numel(), _stream())
+        _lib.check(st, "vpr_head_train_epoch_dropout")
     for t in (W1, b1, W2, b2, m, v):
         torch.autograd.graph.increment_version(t)
     return losses
@@ -710,13 +728,18 @@ def head_train_epoch(X: torch.Tensor, Y: torch.Tensor, order: torch.Tensor, batc
 def head_train_step(X: torch.Tensor, Y: torch.Tensor, idx: Optional[torch.Tensor], W1: torch.Tensor, b1: torch.Tensor,
                     W2: torch.Tensor, b2: torch.Tensor, m: torch.Tensor, v: torch.Tensor, step: int, lr: float = 1e-5,
                     betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                    loss_out: Optional[torch.Tensor] = None, loss: str = "mse", huber_delta: float = 1.0) -> None:
+                    loss_out: Optional[torch.Tensor] = None, loss: str = "mse", huber_delta: float = 1.0,
+                    dropout_p: float = 0.0, dropout_seed: int = 0, mask_out: Optional[torch.Tensor] = None) -> None:
     """One batch of head-only fine-tuning on cached descriptors (vpr_head_train_step): forward, MSELoss, backward and
     AdamW update of Linear(D,hidden)-ReLU-Linear(hidden,n_out), in place on W1 / b1 / W2 / b2 / m / v.
     X [rows, D] f32, Y [rows, n_out] f32, idx [B] int32 (rows of the batch; None = all rows of X in order).  loss_out: a
     one-element f32 tensor (e.g. losses[i:i+1]) that receives the batch loss.  loss: "mse" (nn.MSELoss) or "huber"
-    (nn.HuberLoss(delta=huber_delta)).  No host synchronisation."""
+    (nn.HuberLoss(delta=huber_delta)).  No host synchronisation.
+    dropout_p > 0: Linear -> ReLU -> Dropout(dropout_p) -> Linear in training mode (vpr_head_train_step_dropout; the mask
+    of this step is drawn from (dropout_seed, step, b, j) as include/vpr_amd.h specifies); mask_out: a uint8 [B, hidden]
+    tensor that receives the mask (1 = kept)."""
     D, hidden, n_out = _head_train_check(X, Y, W1, b1, W2, b2, m, v)
+    p_drop, seed = _dropout_args(dropout_p, dropout_seed)
     if idx is not None:
         _need(idx, torch.int32, "idx", 1)
         B = idx.numel()
@@ -727,16 +750,24 @@ def head_train_step(X: torch.Tensor, Y: torch.Tensor, idx: Optional[torch.Tensor
         _need(loss_out, torch.float32, "loss_out")
         if loss_out.numel() != 1:
             raise RuntimeError("head_train_step: loss_out must have one element")
+    if mask_out is not None:
+        _need(mask_out, torch.uint8, "mask_out", 2)
+        if tuple(mask_out.shape) != (B, hidden):
+            raise RuntimeError(f"head_train_step: mask_out must be [B, hidden] = [{B}, {hidden}], got {tuple(mask_out.shape)}")
     nbytes = L.vpr_head_train_workspace_bytes(B, D, hidden, n_out)
     if nbytes == 0:
         raise RuntimeError(f"head_train_step: unsupported shape B={B} D={D} hidden={hidden} n_out={n_out} "
                            "(need 1 <= B <= 64, D % 16 == 0, hidden % 32 == 0, n_out <= 8)")
     ws = workspace("head_train", nbytes, X.device)
-    st = L.vpr_head_train_step(_ptr(X), X.stride(0), _ptr(idx), _ptr(Y), Y.stride(0), B, D, hidden, n_out,
-                               _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(m), _ptr(v), int(step), float(lr),
-                               float(betas[0]), float(betas[1]), float(eps), float(weight_decay), _loss_kind(loss),
-                               float(huber_delta), _ptr(loss_out), _ptr(ws), ws.numel(), _stream())
-    _lib.check(st, "vpr_head_train_step")
+    args = (_ptr(X), X.stride(0), _ptr(idx), _ptr(Y), Y.stride(0), B, D, hidden, n_out,
+            _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(m), _ptr(v), int(step), float(lr),
+            float(betas[0]), float(betas[1]), float(eps), float(weight_decay), _loss_kind(loss), float(huber_delta), _ptr(loss_out))
+    if p_drop == 0.0 and mask_out is None:
+        st = L.vpr_head_train_step(*args, _ptr(ws), ws.numel(), _stream())
+        _lib.check(st, "vpr_head_train_step")
+    else:
+        st = L.vpr_head_train_step_dropout(*args, p_drop, seed, _ptr(mask_out), _ptr(ws), ws.numel(), _stream())
+        _lib.check(st, "vpr_head_train_step_dropout")
     for t in (W1, b1, W2, b2, m, v):          # written behind PyTorch's back: version-keyed caches (pose-head weight planes) must see it
         torch.autograd.graph.increment_version(t)
 

@@ -8,6 +8,7 @@ that seam, so the HIP hot path is visible to PyTorch's dispatcher like any other
     torch.ops.vpr.knn_topk / knn_topk_fp8 / topk_merge
     torch.ops.vpr.pose_head / ln_meanpool_head
     torch.ops.vpr.head_train_epoch                     (head-only fine-tuning pass; mutates parameters and AdamW moments)
+    torch.ops.vpr.head_train_epoch_dropout             (the same pass with Dropout(p) after the ReLU, training mode)
 
 Each op has
   * a CUDA(HIP) implementation = the ctypes wrapper of `vpr_amd.ops` (same validation, same stream, same workspaces;
@@ -195,5 +196,23 @@ def _(X, Y, order, batch_size, W1, b1, W2, b2, m, v, first_step, lr, beta1, beta
     return X.new_empty(((order.shape[0] + batch_size - 1) // batch_size,), dtype=torch.float32)
 
 
-OPS = ("head_train_epoch", "salad_aggregate", "salad_aggregate_split", "salad_aggregate_f32", "knn_topk", "knn_topk_fp8", "quantize_fp8_rows",
+@torch.library.custom_op("vpr::head_train_epoch_dropout", mutates_args=("W1", "b1", "W2", "b2", "m", "v"))
+def head_train_epoch_dropout(X: Tensor, Y: Tensor, order: Tensor, batch_size: int, W1: Tensor, b1: Tensor, W2: Tensor, b2: Tensor,
+                             m: Tensor, v: Tensor, first_step: int, lr: float, beta1: float, beta2: float, eps: float,
+                             weight_decay: float, loss: str, huber_delta: float, dropout_p: float, dropout_seed: int) -> Tensor:
+    """head_train_epoch for Linear(D,hidden)-ReLU-Dropout(dropout_p)-Linear(hidden,n_out) in training mode
+    (dinov2salad_finetuning_2.py:113-122, swin_attempt_2.py:114-123): the masks are a pure function of (dropout_seed, step,
+    position in the batch, hidden unit) — include/vpr_amd.h.  dropout_seed is the 64 bits of the mask key (a negative value
+    stands for its two's complement: the schema's int is signed).  vpr_head_train_epoch_dropout."""
+    return ops.head_train_epoch(X, Y, order, batch_size, W1, b1, W2, b2, m, v, first_step, lr, (beta1, beta2), eps, weight_decay,
+                                loss, huber_delta, dropout_p=dropout_p, dropout_seed=dropout_seed & 0xFFFFFFFFFFFFFFFF)
+
+
+@head_train_epoch_dropout.register_fake
+def _(X, Y, order, batch_size, W1, b1, W2, b2, m, v, first_step, lr, beta1, beta2, eps, weight_decay, loss, huber_delta, dropout_p,
+      dropout_seed):
+    return X.new_empty(((order.shape[0] + batch_size - 1) // batch_size,), dtype=torch.float32)
+
+
+OPS = ("head_train_epoch", "head_train_epoch_dropout", "salad_aggregate", "salad_aggregate_split", "salad_aggregate_f32", "knn_topk", "knn_topk_fp8", "quantize_fp8_rows",
        "topk_merge", "pose_head", "ln_meanpool_head")
