@@ -15,7 +15,10 @@
  *       CU count.  A process may drive any number of GPUs, from any threads;
  *   (2) per PROCESS: the A/B tuning switches (VPR_KNN_VARIANT, ...), read from the environment
  *       ONCE when the library is loaded — a later setenv() changes nothing — and settable only
- *       through vpr_tuning_set() (benchmark scripts and tests; every value gives identical results).
+ *       through vpr_tuning_set() (benchmark scripts and tests).  Every value gives bit-identical results,
+ *       except VPR_SKINNY_NW / VPR_SKINNY_MBW: they change how K is split over waves, so results can differ in
+ *       the last bits (within f32 accumulation order).  Timing-only ablations that return wrong results
+ *       exist only in a -DVPR_ABLATION build (`make ablation`), never in the release library.
  *
  * dtype conventions: "bf16" = uint16_t holding the upper 16 bits of an IEEE fp32
  * (round-to-nearest-even); "f32" = float.
@@ -47,7 +50,7 @@ int vpr_abi_version(void);
 /* Tuning switches (process-wide A/B knobs; names = the VPR_* environment variables read at load: VPR_KNN_VARIANT,
  * VPR_KNN_GEMM_MIN_B, VPR_KNN_GEMM_KSPLIT, VPR_KNN_FP8_GEMM256, VPR_GEMM_NT_STAGES, VPR_GEMM_GROUP_VARIANT,
  * VPR_ATTN_VARIANT, VPR_LN_ROWS, VPR_POSE_KS, VPR_SKINNY_NW, VPR_SKINNY_MBW, VPR_SALAD_VARIANT, VPR_POSE_VARIANT,
- * VPR_LNHEAD_VARIANT, VPR_GEMM256_DEPTH, VPR_HEAD_TRAIN_VARIANT, VPR_GEMM256_STAGGER).  vpr_tuning_set: unset != 0 restores "not set".  vpr_tuning_get: 0 and *value, 1 if the
+ * VPR_LNHEAD_VARIANT (reserved: read by no kernel), VPR_GEMM256_DEPTH, VPR_HEAD_TRAIN_VARIANT, VPR_GEMM256_STAGGER).  vpr_tuning_set: unset != 0 restores "not set".  vpr_tuning_get: 0 and *value, 1 if the
  * switch is not set, VPR_ERR_INVALID_ARG for an unknown name.  Not for production code paths: no call may be in
  * flight on another thread while a switch changes. */
 int vpr_tuning_set(const char* name, int value, int unset);
@@ -495,7 +498,9 @@ int vpr_patchify_bf16(const uint16_t* images, int B, int Cin, int H, int W, int 
                       int lead_rows, uint16_t* out, void* stream);
 
 /* Multi-head self-attention for short ViT sequences (backbone helper): softmax(q k^T * scale) v, non-causal.
- * qkv [B, T, 3, H, 64] bf16 (the fused projection output), out [B, T, H*64] bf16.  T <= 288, head_dim == 64. */
+ * qkv [B, T, 3, H, 64] bf16 (the fused projection output), out [B, T, H*64] bf16.  T <= 288, head_dim == 64
+ * (else VPR_ERR_UNSUPPORTED), 0 < scale < inf (else VPR_ERR_INVALID_ARG).  Any shift of a query's logits by a
+ * constant leaves its output unchanged: the softmax is stabilised by the max over the T real keys only. */
 int vpr_attention_qkv_bf16(const uint16_t* qkv, uint16_t* out, int B, int T, int H, int head_dim,
                            float scale, void* stream);
 

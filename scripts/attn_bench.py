@@ -1,4 +1,9 @@
+"""Attention kernel vs SDPA at B=64, T=257, H=16, and the ablation variants 12-14 (timing only, WRONG results).
+Variants 12-14 exist only in the ablation library: `make -C visual-place-recognition-and-geopose-estimation_amd/csrc
+ablation`, then run with VPR_AMD_LIBRARY=.../libvpr_amd_ablation.so (the release library runs the default instead)."""
 import os, sys, torch, torch.nn.functional as F
+if not os.environ.get("VPR_AMD_LIBRARY", "").endswith("ablation.so"):
+    sys.exit("scripts/attn_bench.py times the ablation variants 12-14: set VPR_AMD_LIBRARY to libvpr_amd_ablation.so")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vpr_amd import _lib, ops
 dev = torch.device("cuda:0")

@@ -1,5 +1,6 @@
 """CPU: closed-form known answers that pin the SALAD and kNN oracles (SURVEY.md §8c — both are
-'parity unpinned' by the reference, so these identities are what holds them in place)."""
+'parity unpinned' by the reference, so these identities are what holds them in place), and the f64 attention
+oracle against PyTorch's own attention."""
 import math
 import os
 
@@ -7,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import attention as oattn
 from oracle import knn as oknn
 from oracle import salad as osalad
 
@@ -203,3 +205,43 @@ def test_knn_oracle_agrees_with_numpy_brute_force():
     assert np.array_equal(i.numpy(), order.astype(np.int32) + 100)
     assert np.array_equal(v.numpy(), np.take_along_axis(s, order, axis=1))
     assert i[0, :3].tolist() == [107, 140, 400]
+
+
+@pytest.mark.parametrize("B,T,H", [(2, 257, 3), (1, 1, 1), (3, 17, 2)])
+def test_attention_oracle_equals_sdpa_f64(B, T, H):
+    g = torch.Generator().manual_seed(T)
+    qkv = (torch.randn(B, T, 3 * H * 64, generator=g, dtype=torch.float64) * 1.5).to(torch.bfloat16)
+    q, k, v = qkv.double().view(B, T, 3, H, 64).permute(2, 0, 3, 1, 4)
+    sdpa = torch.nn.functional.scaled_dot_product_attention(q, k, v, scale=0.125).transpose(1, 2).reshape(B, T, H * 64)
+    assert (oattn.attention_f64(qkv, H) - sdpa).abs().max().item() < 1e-12
+    ref = torch.softmax(q @ k.transpose(-1, -2) * 0.3, dim=-1) @ v
+    assert (oattn.attention_f64(qkv, H, scale=0.3) - ref.transpose(1, 2).reshape(B, T, H * 64)).abs().max().item() < 1e-12
+
+
+def test_attention_oracle_is_invariant_to_a_per_query_logit_offset():
+    """A key dimension set to 8 in every key and to c in query i adds c to every logit of query i (scale 1/8):
+    softmax must not move — also at offsets where an unstabilised exp over- or underflows in f64."""
+    B, T, H = 2, 33, 2
+    g = torch.Generator().manual_seed(1)
+    qkv = torch.randn(B, T, 3, H, 64, generator=g, dtype=torch.float64)
+    qkv[:, :, 1, :, 63] = 8.0
+    qkv[:, :, 0, :, 63] = 0.0
+    base = oattn.attention_f64(qkv.reshape(B, T, -1), H)
+    offs = torch.tensor([-1000.0, -200.0, -40.0, 0.0, 40.0, 800.0], dtype=torch.float64)
+    qkv[:, :, 0, :, 63] = offs[torch.randint(0, len(offs), (B, T, H), generator=g)]
+    shifted = oattn.attention_f64(qkv.reshape(B, T, -1), H)
+    assert torch.isfinite(shifted).all()
+    assert (shifted - base).abs().max().item() < 1e-12
+
+
+@pytest.mark.parametrize("B,T,body", [(3, 257, 256), (2, 17, 0), (2, 17, 17), (4, 5, 1), (1, 9, 4)])
+def test_attention_split_rows_round_trip(B, T, body):
+    x = torch.arange(B * T * 2, dtype=torch.float64).reshape(B, T, 2)
+    rows = oattn.to_split_rows(x, body)
+    assert torch.equal(oattn.from_split_rows(rows, B, T, body), x)
+    idx = oattn.split_row_index(B, T, body)
+    assert sorted(idx.reshape(-1).tolist()) == list(range(B * T))            # a permutation of the rows
+    for b in range(B):
+        for t in range(T):                                                     # the layout of ops.attention_qkv_split_bf16
+            row = b * body + t if t < body else B * body + b * (T - body) + (t - body)
+            assert torch.equal(rows[row], x[b, t])

@@ -57,10 +57,31 @@ __device__ __forceinline__ void attn_qk_all(const AttnCtx& cx, const bf16x8 (&bq
     if ((kb % 3) == 2) __builtin_amdgcn_sched_barrier(0);
   }
 }
-// Row max over keys.  No masking: padded K rows are zero, so padded keys score exactly 0; they may
-// only raise the stabiliser (still an upper bound of the row), their V rows are zero, and their
-// exp2 terms are subtracted from the row sum in phase 2 (AT_KP - T of them per row).
-__device__ __forceinline__ float attn_rowmax(const f32x4 (&sc)[AT_KP / 16]) {
+// Padded keys (16kb + 4g + e >= T) score -inf: they take no part in the row max, and exp2 in phase 1 turns them
+// into p = 0 exactly, so they add nothing to the row sum or to P·V.  (The zero K rows alone score 0: with 0 as the
+// stabiliser of a row whose real logits all lie far below 0, the real p underflow next to the padded ones.)
+// Blocks before klast, the one holding key T-1, are all real; blocks after it all padding.
+__device__ __forceinline__ void attn_mask_block(f32x4& s, int kb, int klast, int lim) {
+  // (the empty asm keeps these wave-uniform branches: speculated into selects, the mask costs 4 VALU ops per block)
+  if (kb > klast) {
+    asm volatile("");
+    s = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  } else if (kb == klast) {
+    asm volatile("");
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s[e] = e < lim ? s[e] : -INFINITY;
+  }
+}
+// Masks the padded keys, then takes the row max over the real ones (key 0 is always real).
+__device__ __forceinline__ float attn_rowmax(const AttnCtx& cx, f32x4 (&sc)[AT_KP / 16]) {
+  const int klast = (cx.T - 1) >> 4;
+  const int lim = cx.T - 16 * klast - 4 * cx.g;      // in block klast, row e of this lane is a real key iff e < lim
+  if (klast < AT_KP / 16 - 2) {                       // T <= 256; at T = 257 only the last two blocks are tested
+#pragma unroll
+    for (int kb = 0; kb < AT_KP / 16 - 2; ++kb) attn_mask_block(sc[kb], kb, klast, lim);
+  }
+#pragma unroll
+  for (int kb = AT_KP / 16 - 2; kb < AT_KP / 16; ++kb) attn_mask_block(sc[kb], kb, klast, lim);
   float mx = sc[0][0];
 #pragma unroll
   for (int kb = 0; kb < AT_KP / 16; ++kb) {     // two v_max3_f32 per block
@@ -73,7 +94,7 @@ __device__ __forceinline__ float attn_rowmax(const f32x4 (&sc)[AT_KP / 16]) {
 // phase 1: p = exp2(fma(s, c, -max*c)) of the current tile -> bf16 B operands pb (k-step t packs key
 // blocks 2t (j<4) and 2t+1 (j>=4)); meanwhile the QK^T blocks 2t, 2t+1 of the next tile,
 // written IN PLACE over the score registers just consumed (one score buffer, 72 VGPRs).
-__device__ __forceinline__ float attn_phase1(const AttnCtx& cx, f32x4 (&sc)[AT_KP / 16], float mx,
+__device__ __forceinline__ void attn_phase1(const AttnCtx& cx, f32x4 (&sc)[AT_KP / 16], float mx,
                                              bf16x8 (&pb)[AT_KP / 32], bool has_next, const bf16x8 (&bq)[2]) {
   const float nm = -mx * cx.scale_log2e;
 #pragma unroll
@@ -91,15 +112,12 @@ __device__ __forceinline__ float attn_phase1(const AttnCtx& cx, f32x4 (&sc)[AT_K
 #pragma unroll
     for (int j = 0; j < 8; ++j) pb[t][j] = (__bf16)p[j];
   }
-  // what one padded key contributes to the row sum (bf16-rounded like every p): removed in phase 2
-  return (float)(__bf16)__builtin_amdgcn_exp2f(nm);
 }
 // phase 2: O^T = V^T P^T of the current tile (4 blocks of 16 dims; A = V^T by ds_read_b64_tr_b16:
 // lane 4q+p of a 16-lane group supplies the address of key row k0+q, dims 4p..4p+3 and receives
 // dim `lane&15` of those 4 keys: j=0..3 from block 2t (k0 = 32t+4g), j=4..7 from block 2t+1),
 // normalise, store; meanwhile the row max of the next tile.
-__device__ __forceinline__ float attn_phase2(const AttnCtx& cx, const bf16x8 (&pb)[AT_KP / 32], float ppad,
-                                             int qt, bool has_next, const f32x4 (&sn)[AT_KP / 16]) {
+__device__ __forceinline__ float attn_phase2(const AttnCtx& cx, const bf16x8 (&pb)[AT_KP / 32], int qt, bool has_next, f32x4 (&sn)[AT_KP / 16]) {
   // The row sum rides on the matrix pipe: a fifth "dim block" whose A operand is all ones gives
   // sum_k P^T[k][query] in every row of its accumulator — 9 MFMAs instead of 72 VALU adds and two
   // cross-lane steps, and it sums exactly the bf16 p values the numerator uses.
@@ -123,9 +141,9 @@ __device__ __forceinline__ float attn_phase2(const AttnCtx& cx, const bf16x8 (&p
       if ((t % 3) == 2) __builtin_amdgcn_sched_barrier(0);
     }
   }
-  const float inv = 1.0f / (sacc[0] - (float)(AT_KP - cx.T) * ppad);   // minus the AT_KP - T padded keys
+  const float inv = 1.0f / sacc[0];                 // >= 1: the row max's own p is bf16(exp2(~0)) = 1
   float mxn = 0.f;
-  if (has_next) mxn = attn_rowmax(sn);
+  if (has_next) mxn = attn_rowmax(cx, sn);
   // C/D: col = query (lane&15), row = dim 16db + 4g + e  -> 8-byte stores of 4 consecutive dims
   const int q = qt * 16 + cx.qcol;
   if (q < cx.T) {
@@ -216,14 +234,14 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(
   if (wave >= ntile) return;
   if constexpr (PIPE) {
     attn_qk_all(cx, qf[0], sc);
-    float mx = attn_rowmax(sc);
+    float mx = attn_rowmax(cx, sc);
 #pragma unroll
     for (int j = 0; j < AT_MAXT; ++j) {
       const int qt = wave + NW * j;
       if (qt < ntile) {   // wave-uniform
         const bool has_next = qt + NW < ntile;
-        const float ppad = attn_phase1(cx, sc, mx, pb, has_next, qf[j + 1 < AT_MAXT ? j + 1 : j]);
-        mx = attn_phase2(cx, pb, ppad, qt, has_next, sc);
+        attn_phase1(cx, sc, mx, pb, has_next, qf[j + 1 < AT_MAXT ? j + 1 : j]);
+        mx = attn_phase2(cx, pb, qt, has_next, sc);
       }
     }
   } else {   // one tile at a time: fewer live registers, more waves per SIMD
@@ -239,10 +257,10 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(
           if (qt * 16 + cx.qcol < T) cx.out[attn_row(cx, qt * 16 + cx.qcol) * cx.out_stride + 4 * cx.g] = f32_to_bf16_bits(a);
           continue;
         }
-        const float mx = attn_rowmax(sc);
-        const float ppad = attn_phase1(cx, sc, mx, pb, false, qf[j]);
+        const float mx = attn_rowmax(cx, sc);
+        attn_phase1(cx, sc, mx, pb, false, qf[j]);
         if (ABL == 2) {                  // ablation: no PV (probabilities summed into one store)
-          float a = ppad;
+          float a = 0.f;
 #pragma unroll
           for (int t = 0; t < AT_KP / 32; ++t)
 #pragma unroll
@@ -250,7 +268,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void attention_kernel(
           if (qt * 16 + cx.qcol < T) cx.out[attn_row(cx, qt * 16 + cx.qcol) * cx.out_stride + 4 * cx.g] = f32_to_bf16_bits(a);
           continue;
         }
-        attn_phase2(cx, pb, ppad, qt, false, sc);
+        attn_phase2(cx, pb, qt, false, sc);
       }
     }
   }
@@ -265,6 +283,7 @@ using namespace vpr;
 static int attention_launch(const uint16_t* qkv, uint16_t* out, int B, int T, int Tp, long long tail_row0, int H,
                             int head_dim, float scale, void* stream) {
   if (!qkv || !out || B <= 0 || T <= 0 || H <= 0 || Tp < 0 || Tp > T || tail_row0 < 0) return VPR_ERR_INVALID_ARG;
+  if (!(scale > 0.f && scale <= 3.4e38f)) return VPR_ERR_INVALID_ARG;     // the stabiliser max(s) needs scale > 0
   if (head_dim != AT_D || T > AT_KP || (long long)B * H > 0x7fffffffLL) return VPR_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(out)) & 15) return VPR_ERR_UNSUPPORTED;
   const int variant = tune_or(TUNE_ATTN_VARIANT, 0);      // A/B switch; 0 = default
@@ -278,6 +297,7 @@ static int attention_launch(const uint16_t* qkv, uint16_t* out, int B, int T, in
     VPR_TRY_LAUNCH(launch_kernel(attention_kernel<NW, PIPE>, dim3((unsigned)(B * H)), dim3(NW * 64), AT_LDS, st, \
                                  qkv, out, T, Tp, tail_row0, H, c, dephase));                                           \
   } while (0)
+#ifdef VPR_ABLATION
 #define VPR_ATTN_ABL(A)                                                                                   \
   do {                                                                                                   \
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<8, false, A>),                \
@@ -286,8 +306,9 @@ static int attention_launch(const uint16_t* qkv, uint16_t* out, int B, int T, in
     VPR_TRY_LAUNCH(launch_kernel(attention_kernel<8, false, A>, dim3((unsigned)(B * H)), dim3(512), AT_LDS, st, \
                                  qkv, out, T, Tp, tail_row0, H, c, 0));                                  \
   } while (0)
-  // Ablations (variants 12-14, timing only): K/V + Q staging alone 11.4 us (101 MB of qkv at ~9 TB/s out of the
-  // Infinity Cache), + QK^T 24.2, + softmax 32.9, full kernel 37.5 us: the phases add up, i.e. the two workgroups of a
+#endif
+  // Ablations (variants 12-14, timing only, -DVPR_ABLATION builds: `make ablation`): K/V + Q staging alone 11.4 us
+  // (101 MB of qkv at ~9 TB/s out of the Infinity Cache), + QK^T 24.2, + softmax 32.9, full kernel 37.5 us: the phases add up, i.e. the two workgroups of a
   // CU run in lockstep and staging does not overlap compute.  A persistent variant would need both K/V sets in LDS
   // (144 KB: one workgroup, two waves per SIMD).  Tried: K and V staged by LDS-DMA with the first tile's QK^T + softmax
   // running before V has landed (padded keys masked in the scores instead of zero-filled rows): correct, but 45.7 us —
@@ -299,13 +320,17 @@ static int attention_launch(const uint16_t* qkv, uint16_t* out, int B, int T, in
     case 1: VPR_ATTN_LAUNCH(4, false); break;
     case 2: VPR_ATTN_LAUNCH(4, true); break;
     case 3: VPR_ATTN_LAUNCH(6, false); break;
-    case 12: VPR_ATTN_ABL(2); break;   // ablations (timing only, wrong results): no PV
+#ifdef VPR_ABLATION     // timing-only builds (WRONG results): never in the shipped library
+    case 12: VPR_ATTN_ABL(2); break;   // no PV
     case 13: VPR_ATTN_ABL(3); break;   // staging only
     case 14: VPR_ATTN_ABL(4); break;   // staging + QK^T
+#endif
     default: VPR_ATTN_LAUNCH(8, false); break;
   }
 #undef VPR_ATTN_LAUNCH
+#ifdef VPR_ABLATION
 #undef VPR_ATTN_ABL
+#endif
   return VPR_OK;
 }
 

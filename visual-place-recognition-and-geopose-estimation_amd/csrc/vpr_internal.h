@@ -66,6 +66,7 @@ inline int launch_kernel(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t
 // ---- process-wide tuning switches (A/B experiments) --------------------------------------------------------------
 // Read from the environment ONCE, when the library is loaded (capi.hip); a later setenv() has no effect on the
 // library.  scripts/ and tests flip them through vpr_tuning_set().  TUNE_UNSET = the variable was absent.
+// TUNE_LNHEAD_VARIANT is reserved (its name stays accepted by vpr_tuning_set); no kernel reads it.
 enum TuneOpt {
   TUNE_KNN_VARIANT = 0, TUNE_KNN_GEMM_MIN_B, TUNE_KNN_GEMM_KSPLIT, TUNE_KNN_FP8_GEMM256, TUNE_GEMM_NT_STAGES,
   TUNE_GEMM_GROUP_VARIANT, TUNE_ATTN_VARIANT, TUNE_LN_ROWS, TUNE_POSE_KS, TUNE_SKINNY_NW, TUNE_SKINNY_MBW,

@@ -818,6 +818,8 @@ def layernorm_bf16(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps
     if gamma.numel() != C or beta.numel() != C:
         raise RuntimeError("layernorm_bf16: parameter size")
     y = torch.empty_like(x)
+    if x.numel() == 0:                       # no rows: nothing to launch (an empty tensor has no data pointer)
+        return y
     st = _lib.lib().vpr_layernorm_bf16(_ptr(x), _ptr(gamma), _ptr(beta), int(gamma.dtype == torch.bfloat16), float(eps),
                                        _ptr(y), x.numel() // C, C, _stream())
     _lib.check(st, "vpr_layernorm_bf16")
@@ -849,6 +851,8 @@ def bias_layernorm_bf16(x: torch.Tensor, pre_bias: torch.Tensor, gamma: torch.Te
     if gamma.numel() != C or beta.numel() != C or pre_bias.numel() != C:
         raise RuntimeError("bias_layernorm_bf16: parameter size")
     y = torch.empty_like(x)
+    if x.numel() == 0:                       # no rows: nothing to launch (an empty tensor has no data pointer)
+        return y
     st = _lib.lib().vpr_bias_layernorm_bf16(_ptr(x), _ptr(pre_bias), _ptr(gamma), _ptr(beta),
                                             int(gamma.dtype == torch.bfloat16), float(eps), _ptr(y),
                                             x.numel() // C, C, _stream())
@@ -869,6 +873,8 @@ def add_layernorm_bf16(x: torch.Tensor, res: torch.Tensor, gamma: torch.Tensor, 
     if gamma.numel() != C or beta.numel() != C:
         raise RuntimeError("add_layernorm_bf16: parameter size")
     s, y = torch.empty_like(x), torch.empty_like(x)
+    if x.numel() == 0:
+        return s, y
     st = _lib.lib().vpr_add_layernorm_bf16(_ptr(x), _ptr(res), _ptr(s), _ptr(gamma), _ptr(beta),
                                            int(gamma.dtype == torch.bfloat16), float(eps), _ptr(y),
                                            x.numel() // C, C, _stream())
@@ -908,11 +914,13 @@ def skinny_linear_bf16(inp: torch.Tensor, weight: torch.Tensor, bias: Optional[t
                        mode: int = 0, stats_bias: Optional[torch.Tensor] = None,
                        row_stats: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Linear layer on a few rows, written into `out` (a row slice of a larger buffer is fine):
-    mode 0 out = inp W^T + b; 1 gelu_tanh(inp W^T + b); 2 out += inp W^T; 3 relu; 4 erf-GELU.  With row_stats [N/16, M, 2] f32 it
-    also leaves the per-16-column (mean, M2) of bf16(out) + stats_bias there (LayerNorm statistics partials)."""
+    mode 0 out = inp W^T + b; 1 gelu_tanh(inp W^T + b); 2 out += inp W^T; 3 relu; 4 erf-GELU; 5 inp W^T + b into an
+    f32 `out`.  With row_stats [N/16, M, 2] f32 (bf16 modes) it also leaves the per-16-column (mean, M2) of
+    bf16(out) + stats_bias there (LayerNorm statistics partials)."""
     for t, name in ((inp, "inp"), (weight, "weight"), (out, "out")):
-        if not t.is_cuda or t.dtype != torch.bfloat16 or t.dim() != 2 or t.stride(1) != 1:
-            raise RuntimeError(f"skinny_linear_bf16: {name} must be a GPU bf16 matrix with unit column stride")
+        dtype = torch.float32 if t is out and mode == 5 else torch.bfloat16
+        if not t.is_cuda or t.dtype != dtype or t.dim() != 2 or t.stride(1) != 1:
+            raise RuntimeError(f"skinny_linear_bf16: {name} must be a GPU {dtype} matrix with unit column stride")
     M, K = inp.shape
     N = weight.shape[0]
     if weight.shape[1] != K or tuple(out.shape) != (M, N):
@@ -922,6 +930,8 @@ def skinny_linear_bf16(inp: torch.Tensor, weight: torch.Tensor, bias: Optional[t
                 or not bias.is_contiguous():
             raise RuntimeError("skinny_linear_bf16: bias [N] bf16/f32 required")
     if row_stats is not None:
+        if mode == 5:
+            raise RuntimeError("skinny_linear_bf16: row_stats describe a bf16 output (modes 0-4)")
         _need(row_stats, torch.float32, "row_stats", 3)
         if tuple(row_stats.shape) != (N // 16, M, 2) or N % 16:
             raise RuntimeError("skinny_linear_bf16: row_stats must be [N/16, M, 2] with N % 16 == 0")
