@@ -15,9 +15,12 @@
  *       CU count.  A process may drive any number of GPUs, from any threads;
  *   (2) per PROCESS: the A/B tuning switches (VPR_KNN_VARIANT, ...), read from the environment
  *       ONCE when the library is loaded — a later setenv() changes nothing — and settable only
- *       through vpr_tuning_set() (benchmark scripts and tests).  Every value gives bit-identical results,
- *       except VPR_SKINNY_NW / VPR_SKINNY_MBW: they change how K is split over waves, so results can differ in
- *       the last bits (within f32 accumulation order).  Timing-only ablations that return wrong results
+ *       through vpr_tuning_set() (benchmark scripts and tests).  Every value gives bit-identical results, except
+ *       VPR_SKINNY_NW / VPR_SKINNY_MBW (how K is split over waves), VPR_GEMM256_STAGGER (the order in which a
+ *       256 x 256 tile walks its K-tiles), VPR_POSE_KS (the K split of the pose head's first layer) and
+ *       VPR_POSE_VARIANT (8: eight waves split a slice's K-steps): they change the f32 accumulation order, so results
+ *       can differ in the last bits, within the f32 accumulation bound of the kernel (K u sum|products|, u = 2^-24;
+ *       results on operands whose f32 sums are exact do not change).  Timing-only ablations that return wrong results
  *       exist only in a -DVPR_ABLATION build (`make ablation`), never in the release library.
  *
  * dtype conventions: "bf16" = uint16_t holding the upper 16 bits of an IEEE fp32
@@ -33,7 +36,7 @@
 extern "C" {
 #endif
 
-#define VPR_AMD_ABI_VERSION 4
+#define VPR_AMD_ABI_VERSION 5
 
 typedef enum vpr_status {
   VPR_OK = 0,
@@ -178,10 +181,22 @@ int vpr_gemm_nt_bf16(const uint16_t* A, int lda, int a_group_rows, long long a_g
 
 /* Same operation on 256 x 256 output tiles with LDS-DMA kept in flight across barriers (the
  * large-M / large-N form: SALAD layer 1 is exactly 256 such tiles at B = 64).  Additional
- * requirements: K >= 128, ldc % 4 == 0, C 16-byte aligned. */
+ * requirements: K >= 128, ldc % 4 == 0, C and bias 16-byte aligned. */
 int vpr_gemm256_nt_bf16(const uint16_t* A, int lda, int a_group_rows, long long a_group_stride,
                         const uint16_t* W, int ldw, const float* bias, int relu,
                         void* C, int ldc, int out_is_bf16, int M, int N, int K, void* stream);
+
+/* One member of a grouped launch: the arguments of vpr_gemm_nt_bf16. */
+typedef struct vpr_gemm_problem {
+  const uint16_t* A; int lda; int a_group_rows; long long a_group_stride;
+  const uint16_t* W; int ldw; const float* bias; int relu;
+  void* C; int ldc; int out_is_bf16; int M; int N; int K;
+} vpr_gemm_problem;
+
+/* 1 <= count <= 3 independent problems (contract of vpr_gemm_nt_bf16 each) in ONE launch: the grouped kernel SALAD's
+ * second layers and f32-accurate path run on (VPR_GEMM_GROUP_VARIANT picks its tile); exposed for parity tests.
+ * Every problem is checked before anything launches; each result equals the same problem launched alone here. */
+int vpr_gemm_nt_group_bf16(const vpr_gemm_problem* probs, int count, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * kNN: cosine top-k of L2-normalised descriptors against a gallery shard.

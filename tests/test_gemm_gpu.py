@@ -2,7 +2,18 @@
 import pytest
 import torch
 
+from oracle import gemm as og
+
 pytestmark = pytest.mark.gpu
+
+
+def _assert_per_element(out, a, w, bias, relu, out_bf16):
+    """Besides the max-norm bound: every element within the f32-accumulation bound of its own dot product (plus half a
+    bf16 spacing at its own magnitude), so small-magnitude columns and ragged tiles cannot hide behind the largest value."""
+    y, s, S = og.gemm_ref(a, w, bias, relu)
+    bound = og.gemm_bound(y, s, S, a.shape[1], bias, out_bf16)
+    ratio = ((out - y).abs() / bound).max().item()
+    assert ratio <= 1.0, f"worst |err| / per-element bound = {ratio:.3f}"
 
 
 @pytest.mark.parametrize("M,N,K,relu,out_bf16", [
@@ -29,6 +40,7 @@ def test_gemm_nt(dev, M, N, K, relu, out_bf16):
                            torch.bfloat16 if out_bf16 else torch.float32).cpu().double()
     tol = 2e-2 if out_bf16 else 1e-4          # bf16 output: half an ulp of the largest values
     assert (out - ref).abs().max().item() < tol * max(1.0, ref.abs().max().item())
+    _assert_per_element(out, a, w, bias, relu, out_bf16)
 
 
 def test_gemm_identity_asymmetric(dev):
@@ -63,6 +75,7 @@ def test_gemm256(dev, M, N, K, relu, out_bf16):
                            torch.bfloat16 if out_bf16 else torch.float32, tile256=True).cpu().double()
     tol = 2e-2 if out_bf16 else 2e-4
     assert (out - ref).abs().max().item() < tol * max(1.0, ref.abs().max().item())
+    _assert_per_element(out, a, w, bias, relu, out_bf16)
 
 
 def test_gemm256_repeatable_under_load(dev):

@@ -46,6 +46,7 @@ def test_workspace_queries(lib):
 
 
 def test_invalid_arguments_are_rejected_without_a_device(lib):
+    from vpr_amd import _lib
     null = ctypes.c_void_p(0)
     buf = (ctypes.c_char * 4096)()
     p = ctypes.cast(buf, ctypes.c_void_p)
@@ -59,6 +60,13 @@ def test_invalid_arguments_are_rejected_without_a_device(lib):
     assert lib.vpr_pose_head(p, p, p, p, p, p, 1, 64, 32, 9, -1, p, 4096, null) == -2    # n_out > 8
     assert lib.vpr_ln_meanpool_head(p, 0, 1, 4, 100, p, p, 1e-5, p, null, null, 0, -1, null, null) == -2   # H unsupported
     assert lib.vpr_gemm_nt_bf16(p, 64, 0, 0, p, 64, null, 0, p, 8, 0, 8, 8, 60, null) == -2   # K % 64
+    a16 = ctypes.c_void_p((p.value + 15) // 16 * 16)
+    b4 = ctypes.c_void_p(a16.value + 4)
+    assert lib.vpr_gemm256_nt_bf16(a16, 128, 0, 0, a16, 128, b4, 0, a16, 8, 0, 8, 8, 128, null) == -2   # bias off 16 B
+    assert lib.vpr_gemm_nt_group_bf16(None, 1, None) == -1
+    bad = _lib.GemmProblemC(a16.value, 64, 0, 0, a16.value, 64, None, 0, a16.value, 8, 0, 8, 8, 60)
+    assert lib.vpr_gemm_nt_group_bf16(ctypes.byref(bad), 1, null) == -2                          # K % 64
+    assert lib.vpr_gemm_nt_group_bf16(ctypes.byref(bad), 4, null) == -1                          # more than 3 problems
     assert lib.vpr_salad_sinkhorn_aggregate(p, p, p, 1, 100, 64, 128, 256, 1.0, 3, p, null, null) == -2
     assert lib.vpr_f32_to_bf16(null, null, 4, null) == -1
     # head-only fine-tuning step: arguments are judged before anything is launched

@@ -245,3 +245,69 @@ def test_attention_split_rows_round_trip(B, T, body):
         for t in range(T):                                                     # the layout of ops.attention_qkv_split_bf16
             row = b * body + t if t < body else B * body + b * (T - body) + (t - body)
             assert torch.equal(rows[row], x[b, t])
+
+
+# ------------------------------------------------------------------------------------------------ GEMM bound (oracle/gemm.py)
+from oracle import gemm as ogemm  # noqa: E402
+
+
+@pytest.mark.parametrize("M,N,K", [(67, 130, 64), (33, 257, 1088), (16, 40, 4096)])
+@pytest.mark.parametrize("relu", [False, True])
+def test_gemm_bound_holds_for_f32_matmul(M, N, K, relu):
+    """The per-element bound covers an f32 GEMM of the same bf16 operands (torch's CPU matmul: another summation
+    order), for f32 output and after RNE to bf16."""
+    a, w, b = ogemm.random_operands(M, N, K, seed=M + N + K)
+    y, s, S = ogemm.gemm_ref(a, w, b, relu)
+    y32 = a.float() @ w.float().T + b
+    if relu:
+        y32 = y32.clamp_min(0)
+    assert ((y32.double() - y).abs() <= ogemm.gemm_bound(y, s, S, K, b)).all()
+    y16 = y32.to(torch.bfloat16).double()
+    assert ((y16 - y).abs() <= ogemm.gemm_bound(y, s, S, K, b, out_bf16=True)).all()
+
+
+def _truncate_bf16(x32):
+    return (x32.contiguous().view(torch.int32) & -65536).view(torch.float32).double()
+
+
+@pytest.mark.parametrize("M,N,K", [(64, 96, 256), (40, 130, 1088)])
+def test_gemm_bound_is_not_vacuous(M, N, K):
+    """The bound rejects a result with one 64-deep K-tile dropped, a bias shifted by one column, and bf16 conversion by
+    truncation; the exact-operand form pins the same faults bit for bit."""
+    a, w, b = ogemm.random_operands(M, N, K, seed=K)
+    y, s, S = ogemm.gemm_ref(a, w, b)
+    bound = ogemm.gemm_bound(y, s, S, K, b)
+    for j in (0, K // 64 - 1):
+        kt = slice(64 * j, 64 * j + 64)
+        dropped = y - a[:, kt].double() @ w[:, kt].double().T
+        assert ((dropped - y).abs() > bound).any(), f"K-tile {j} dropped passes"
+    shifted = s + torch.roll(b, 1).double()[None, :]
+    assert ((shifted - y).abs() > bound).any(), "bias shifted by one column passes"
+    y32 = (a.float() @ w.float().T + b)
+    trunc = _truncate_bf16(y32)
+    assert ((trunc - y).abs() > ogemm.gemm_bound(y, s, S, K, b, out_bf16=True)).any(), "truncation to bf16 passes"
+    # exact operands: f32 sums are exact in any order, the right answer is one value per element
+    a, w, b = ogemm.exact_operands(M, N, K, seed=K)
+    y, s, S = ogemm.gemm_ref(a, w, b)
+    y32 = a.float() @ w.float().T + b
+    assert torch.equal(y32.double(), y)
+    assert torch.equal(torch.flip(a, [1]).float() @ torch.flip(w, [1]).float().T + b, y32)       # order-independent
+    want16 = ogemm.exact_value(y, True)
+    assert torch.equal(y32.to(torch.bfloat16).double(), want16)
+    assert not torch.equal(_truncate_bf16(y32), want16), "truncation indistinguishable on exact operands"
+    kt = slice(0, 64)
+    assert not torch.equal(ogemm.exact_value(y - a[:, kt].double() @ w[:, kt].double().T, False), y)
+
+
+def test_gemm_ref_resolves_row_groups():
+    """rows_of / gemm_ref address row r at (r // g) * stride + (r % g) * lda, as the kernels do."""
+    M, K, lda, g, stride = 10, 64, 72, 3, 3 * 72 + 16
+    a = torch.randn(M, K).to(torch.bfloat16)
+    flat = torch.full((4 * stride + lda,), float("nan"), dtype=torch.bfloat16)
+    for r in range(M):
+        o = (r // g) * stride + (r % g) * lda
+        flat[o:o + K] = a[r]
+    assert torch.equal(ogemm.rows_of(flat, M, K, lda, g, stride), a)
+    w = torch.randn(5, K).to(torch.bfloat16)
+    y, _, _ = ogemm.gemm_ref(flat, w, None, False, g, stride, lda, M)
+    assert torch.equal(y, a.double() @ w.double().T)

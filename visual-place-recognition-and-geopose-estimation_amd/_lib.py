@@ -14,7 +14,7 @@ from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_lo
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 STATUS_OK = 0
 
@@ -29,6 +29,13 @@ class SaladWeightsF32C(Structure):
     """struct vpr_salad_weights_f32 (device pointers)."""
     _fields_ = [(n, c_void_p) for n in
                 ("w1_sc", "b1_sc", "w2_s", "b2_s", "w2_c", "b2_c", "w1_t", "b1_t", "w2_t", "b2_t")]
+
+
+class GemmProblemC(Structure):
+    """struct vpr_gemm_problem (one member of vpr_gemm_nt_group_bf16)."""
+    _fields_ = [("A", c_void_p), ("lda", c_int), ("a_group_rows", c_int), ("a_group_stride", c_longlong),
+                ("W", c_void_p), ("ldw", c_int), ("bias", c_void_p), ("relu", c_int),
+                ("C", c_void_p), ("ldc", c_int), ("out_is_bf16", c_int), ("M", c_int), ("N", c_int), ("K", c_int)]
 
 
 # name -> (restype, argtypes); kept in one table so tests can check every symbol is exported
@@ -61,6 +68,7 @@ PROTOTYPES = {
                                  c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "vpr_gemm256_nt_bf16": (c_int, [c_void_p, c_int, c_int, c_longlong, c_void_p, c_int, c_void_p, c_int,
                                     c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "vpr_gemm_nt_group_bf16": (c_int, [POINTER(GemmProblemC), c_int, c_void_p]),
     "vpr_knn_workspace_bytes": (c_size_t, [c_int] * 4),
     "vpr_knn_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                              c_void_p, c_size_t, c_void_p]),

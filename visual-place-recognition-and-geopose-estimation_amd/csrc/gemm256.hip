@@ -506,7 +506,9 @@ int launch_gemm256(const GemmProblem& in, hipStream_t stream) {
   if (!g.A || !g.W || !g.C || g.M <= 0 || g.N <= 0 || g.K <= 0) return VPR_ERR_INVALID_ARG;
   if (g.K % 64 != 0 || g.K < 128 || g.lda < g.K || g.ldw < g.K || g.ldc < g.N) return VPR_ERR_UNSUPPORTED;
   if ((g.lda % 8) || (g.ldw % 8) || (g.ldc % 4) || (g.a_group_rows > 0 && (g.a_group_stride % 8))) return VPR_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(g.A) | reinterpret_cast<uintptr_t>(g.W) | reinterpret_cast<uintptr_t>(g.C)) & 15)
+  // the epilogue reads the bias as float4 (a null bias is fine)
+  if ((reinterpret_cast<uintptr_t>(g.A) | reinterpret_cast<uintptr_t>(g.W) | reinterpret_cast<uintptr_t>(g.C) |
+       reinterpret_cast<uintptr_t>(g.bias)) & 15)
     return VPR_ERR_UNSUPPORTED;
   g.tiles_m = (g.M + G2_BM - 1) / G2_BM;
   g.tiles_n = (g.N + G2_BN - 1) / G2_BN;
@@ -615,7 +617,7 @@ extern "C" int vpr_salad_pack_w2_fragments(const uint16_t* w2, int n_out, int hi
   return launch_pack_w2_fragments(w2, n_out, hidden, out, static_cast<hipStream_t>(stream));
 }
 
-// Same contract as vpr_gemm_nt_bf16 (K >= 128, ldc % 4 == 0, C 16-byte aligned), 256 x 256 tiles.
+// Same contract as vpr_gemm_nt_bf16 (K >= 128, ldc % 4 == 0, C and bias 16-byte aligned), 256 x 256 tiles.
 extern "C" int vpr_gemm256_nt_bf16(const uint16_t* A, int lda, int a_group_rows, long long a_group_stride,
                                    const uint16_t* W, int ldw, const float* bias, int relu, void* C, int ldc,
                                    int out_is_bf16, int M, int N, int K, void* stream) {

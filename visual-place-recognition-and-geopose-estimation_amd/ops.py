@@ -329,25 +329,84 @@ def salad_sinkhorn_aggregate(scores: torch.Tensor, feats: torch.Tensor, tokfeat:
     return out, out16
 
 
-def gemm_nt_bf16(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, relu: bool = False,
-                 out_dtype: torch.dtype = torch.float32, tile256: bool = False) -> torch.Tensor:
-    """act(a @ w.T + bias): a [M,K] bf16, w [N,K] bf16 -> [M,N] f32 or bf16 (MFMA, f32 accumulate)."""
-    _need(a, torch.bfloat16, "a", 2)
-    _need(w, torch.bfloat16, "w", 2)
+def _need_rows(t: torch.Tensor, dtype: torch.dtype, name: str) -> None:
+    """A 2-D GPU matrix whose rows may be padded (stride(1) == 1, any stride(0)): the leading dimension goes to C."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name}: expected a GPU tensor (the HIP path has no CPU fallback)")
+    if t.dtype != dtype:
+        raise RuntimeError(f"{name}: expected dtype {dtype}, got {t.dtype}")
+    if t.dim() != 2 or (t.stride(1) != 1 and t.shape[1] > 1):
+        raise RuntimeError(f"{name}: expected a 2-D tensor with unit column stride")
+
+
+def _gemm_fields(a, w, bias, relu, out_dtype, out, a_group_rows, a_group_stride, m):
+    """The vpr_gemm_problem fields of one GEMM (allocating `out` if it is None).  Only what the library cannot see is
+    checked here (dtypes, shapes, that row-group addressing stays inside a's storage); strides, alignment and the
+    tile constraints are the library's to judge, and its status is passed through."""
+    _need_rows(a, torch.bfloat16, "a")
+    _need_rows(w, torch.bfloat16, "w")
     if bias is not None:
         _need(bias, torch.float32, "bias", 1)
-    M, K = a.shape
+    K = a.shape[1]
+    M = a.shape[0] if m is None else int(m)
     N = w.shape[0]
     if w.shape[1] != K or (bias is not None and bias.numel() != N):
         raise RuntimeError("gemm_nt_bf16: inconsistent shapes")
-    if out_dtype not in (torch.float32, torch.bfloat16):
-        raise RuntimeError("gemm_nt_bf16: out_dtype must be float32 or bfloat16")
-    out = torch.empty((M, N), dtype=out_dtype, device=a.device)
+    if a_group_rows > 0 and M > 0:
+        # A row r lives at a + (r // a_group_rows) * a_group_stride + (r % a_group_rows) * lda: it must stay in a's storage
+        def row(r):
+            return r // a_group_rows * a_group_stride + r % a_group_rows * a.stride(0)
+        last = max(row(r) for r in (M - 1, (M - 1) // a_group_rows * a_group_rows - 1) if r >= 0) + K
+        if a_group_stride < 0 or a.storage_offset() + last > a.untyped_storage().nbytes() // a.element_size():
+            raise RuntimeError("gemm_nt_bf16: row groups reach past the storage of a")
+    elif m is not None and m != a.shape[0]:
+        raise RuntimeError("gemm_nt_bf16: m= is for row-group addressing")
+    if out is None:
+        if out_dtype not in (torch.float32, torch.bfloat16):
+            raise RuntimeError("gemm_nt_bf16: out_dtype must be float32 or bfloat16")
+        out = torch.empty((M, N), dtype=out_dtype, device=a.device)
+    else:
+        if out.dtype not in (torch.float32, torch.bfloat16):
+            raise RuntimeError("gemm_nt_bf16: out must be float32 or bfloat16")
+        _need_rows(out, out.dtype, "out")
+        if tuple(out.shape) != (M, N):
+            raise RuntimeError(f"gemm_nt_bf16: out must be [{M}, {N}], got {tuple(out.shape)}")
+    fields = (_ptr(a), a.stride(0), int(a_group_rows), int(a_group_stride), _ptr(w), w.stride(0), _ptr(bias), int(relu),
+              _ptr(out), out.stride(0), int(out.dtype == torch.bfloat16), M, N, K)
+    return fields, out
+
+
+def gemm_nt_bf16(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, relu: bool = False,
+                 out_dtype: torch.dtype = torch.float32, tile256: bool = False, *, out: Optional[torch.Tensor] = None,
+                 a_group_rows: int = 0, a_group_stride: int = 0, m: Optional[int] = None) -> torch.Tensor:
+    """act(a @ w.T + bias): a [M,K] bf16, w [N,K] bf16 -> [M,N] f32 or bf16 (MFMA, f32 accumulate).
+
+    a / w may have padded rows (their stride(0) is passed as lda / ldw).  out: an [M,N] f32 / bf16 matrix to write into,
+    e.g. a row or column slice of a wider buffer (its stride(0) is ldc; its dtype overrides out_dtype).  With
+    a_group_rows > 0, row r of A lives at a + (r // a_group_rows) * a_group_stride + (r % a_group_rows) * a.stride(0)
+    (elements) and m gives the row count M (default a.shape[0])."""
+    fields, out = _gemm_fields(a, w, bias, relu, out_dtype, out, a_group_rows, a_group_stride, m)
     fn = _lib.lib().vpr_gemm256_nt_bf16 if tile256 else _lib.lib().vpr_gemm_nt_bf16
-    st = fn(_ptr(a), K, 0, 0, _ptr(w), K, _ptr(bias), int(relu), _ptr(out), N,
-            int(out_dtype == torch.bfloat16), M, N, K, _stream())
+    st = fn(*fields, _stream())
     _lib.check(st, "vpr_gemm256_nt_bf16" if tile256 else "vpr_gemm_nt_bf16")
     return out
+
+
+def gemm_nt_group_bf16(problems) -> list:
+    """1 to 3 GEMMs in ONE launch of the grouped kernel (vpr_gemm_nt_group_bf16).  problems: dicts with the arguments
+    of gemm_nt_bf16 (keys a, w, and optionally bias, relu, out_dtype, out, a_group_rows, a_group_stride, m).
+    Returns the outputs in order."""
+    problems = list(problems)
+    arr = (_lib.GemmProblemC * max(1, len(problems)))()
+    outs = []
+    for i, p in enumerate(problems):
+        fields, out = _gemm_fields(p["a"], p["w"], p.get("bias"), p.get("relu", False), p.get("out_dtype", torch.float32),
+                                   p.get("out"), p.get("a_group_rows", 0), p.get("a_group_stride", 0), p.get("m"))
+        arr[i] = _lib.GemmProblemC(*[f.value if isinstance(f, ctypes.c_void_p) else f for f in fields])
+        outs.append(out)
+    st = _lib.lib().vpr_gemm_nt_group_bf16(arr, len(problems), _stream())
+    _lib.check(st, "vpr_gemm_nt_group_bf16")
+    return outs
 
 
 # -------------------------------------------------------------------------------------------- kNN
