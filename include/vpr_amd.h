@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define VPR_AMD_ABI_VERSION 5
+#define VPR_AMD_ABI_VERSION 6
 
 typedef enum vpr_status {
   VPR_OK = 0,
@@ -424,6 +424,39 @@ int vpr_head_train_epoch_dropout(const float* X, long long x_stride, const int* 
                                  double lr, double beta1, double beta2, double eps, double weight_decay,
                                  int loss_kind, double huber_delta, float* losses, double dropout_p, uint64_t seed,
                                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* SALAD aggregation in training mode: the hub model's score / cluster_features MLPs are Conv -> Dropout(p) -> ReLU -> Conv,
+ * and dinov2salad/dinov2salad_finetuning.py:115 (`model.train()` every epoch) leaves those Dropouts active while the head
+ * trains (the extractor is only under torch.no_grad, :34-37).  This entry point computes that descriptor:
+ *   hidden  h = bf16( relu(x W1_sc^T + b1) * s ) for a kept unit, 0 for a dropped one — one rounding point, as in the eval
+ *           form (relu(z * s) = relu(z) * s for s > 0, so this equals Conv -> Dropout -> ReLU)
+ * The token MLP (no dropout in the hub model) and the Sinkhorn stage are those of vpr_salad_aggregate_split.
+ * Mask: a pure function of (seed, pass, image, token, unit) — not of B, of how a dataset is split into calls, or of the
+ * launch geometry.  Generator and key as for the head step above; then
+ *   counter  (u >> 2, image, token, pass); r = output word u & 3, with
+ *            u      in [0, 2*hidden): the row of w1_sc (score units first, then cluster units),
+ *            image  = image_base + b: a global image index (b = 0 .. B-1 within the call),
+ *            token  in [0, n): the patch row,
+ *            pass   a caller-chosen 32-bit pass number (finetune_head uses the epoch);
+ *   keep     unit kept iff r >= t, t = (uint32) floor(p * 2^32) formed in double;
+ *   scale    s = 1 / (1 - p) formed in double and rounded to f32 once.
+ * patch row r of image b at patch + b*patch_img_stride + r*C and cls token of image b at cls + b*cls_stride (elements;
+ * strides % 8 == 0): covers [B, n, C] + [B, C] and the hub layout [B, 1+n, C].  Same weights, workspace
+ * (vpr_salad_workspace_bytes), shapes and output contract as vpr_salad_aggregate_split.
+ * mask_out (device uint8 [B*n, 2*hidden], row b*n + token, column u, 4-byte aligned; may be NULL) receives the mask,
+ * 1 = kept — for tests.
+ * Refusals, before anything is launched (out_f32 / out_bf16 / mask_out untouched):
+ *   VPR_ERR_INVALID_ARG   dropout_p outside [0, 1) or NaN; image_base < 0 or image_base + B > 2^32; the argument checks of
+ *                         vpr_salad_aggregate_split;
+ *   VPR_ERR_UNSUPPORTED   the mask exists on the fused MLP route only (hidden = 512, the shapes of vpr_salad_aggregate):
+ *                         where the MLP stage would take the unfused route (another hidden width, or VPR_SALAD_VARIANT=1)
+ *                         the call is refused rather than masking after the rounding point (other bits).
+ * dropout_p = 0 gives exactly the bits of vpr_salad_aggregate_split on the same tokens. */
+int vpr_salad_aggregate_train(const uint16_t* patch, long long patch_img_stride, const uint16_t* cls, long long cls_stride,
+                              int B, int n, int C, const vpr_salad_weights* w, float dustbin, int m, int l, int t, int hidden,
+                              int sinkhorn_iters, double dropout_p, uint64_t seed, uint32_t pass, long long image_base,
+                              float* out_f32, uint16_t* out_bf16, uint8_t* mask_out,
+                              void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Swin pooler + linear head: pooled = mean_t LayerNorm(x[b,t,:]) ; out = Wh * pooled + bh

@@ -9,12 +9,12 @@ import torch  # noqa: F401  MUST precede loading libvpr_amd.so: the library has 
               # runtime PyTorch ships (torch/lib/libamdhip64.so), not to a second copy from /opt/rocm —
               # two runtimes in one process make every launch fail with hipErrorNoDevice.
 from ctypes import (POINTER, Structure, c_char_p, c_double, c_float, c_int, c_longlong, c_size_t,
-                    c_uint64, c_void_p)
+                    c_uint32, c_uint64, c_void_p)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 STATUS_OK = 0
 
@@ -62,6 +62,9 @@ PROTOTYPES = {
     "vpr_salad_aggregate_f32": (c_int, [c_void_p, c_longlong, c_void_p, c_longlong, c_int, c_int, c_int,
                                         POINTER(SaladWeightsF32C), c_float, c_int, c_int, c_int, c_int, c_int,
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vpr_salad_aggregate_train": (c_int, [c_void_p, c_longlong, c_void_p, c_longlong, c_int, c_int, c_int, POINTER(SaladWeightsC),
+                                          c_float, c_int, c_int, c_int, c_int, c_int, c_double, c_uint64, c_uint32, c_longlong,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vpr_salad_sinkhorn_aggregate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                              c_int, c_float, c_int, c_void_p, c_void_p, c_void_p]),
     "vpr_gemm_nt_bf16": (c_int, [c_void_p, c_int, c_int, c_longlong, c_void_p, c_int, c_void_p, c_int,

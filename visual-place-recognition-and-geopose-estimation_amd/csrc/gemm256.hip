@@ -387,9 +387,13 @@ struct Fuse2 {
 // all 256 workgroups hit at the same addresses at the same moment: 3.9 / 7.4 us (score / cluster tiles) waiting for it
 // (phase clocks, scripts/sinkhorn_phases.py).  Here the fragments are requested BEFORE the hidden tile is parked in LDS
 // (the main loop's LDS-DMA tail is older in the in-order vmcnt queue, so a counted wait still retires exactly the tail).
-template <int NOB>
-__device__ __forceinline__ void g2_fuse2_epilogue(const GemmProblem& pr, const Fuse2& f, G2Acc& acc, char* smem,
-                                                  int head, int slab, int m0, int n0, int lane, int wave) {
+// DROP: dropout on the hidden layer (Fuse2Drop; the mask contract of vpr_salad_aggregate_train in include/vpr_amd.h).  A
+// hidden value becomes relu(acc + b1) * s if its unit is kept, 0 if dropped, and only then is it rounded to bf16 — the one
+// rounding point of the plain form; relu(z * s) = relu(z) * s for s > 0, so this is Conv -> Dropout -> ReLU.  The four
+// hidden columns a lane holds in one f32x4 (4g .. 4g+3 of a 16-column block) are the four words of one Philox call.
+template <int NOB, bool DROP>
+__device__ __forceinline__ void g2_fuse2_epilogue(const GemmProblem& pr, const Fuse2& f, const Fuse2Drop& d, G2Acc& acc,
+                                                  char* smem, int head, int slab, int m0, int n0, int lane, int wave) {
   const int n_out = f.n_out[head];
   const int wr = wave >> 2, wc = wave & 3;
   const int frow = lane & 15, g = lane >> 4;
@@ -441,7 +445,21 @@ __device__ __forceinline__ void g2_fuse2_epilogue(const GemmProblem& pr, const F
         for (int cb = 0; cb < 2; ++cb) {
           const float4 b = bias4[qj][cb];
           const f32x4 a = acc[qi][qj][rb][cb];
-          const float v0 = fmaxf(a[0] + b.x, 0.f), v1 = fmaxf(a[1] + b.y, 0.f), v2 = fmaxf(a[2] + b.z, 0.f), v3 = fmaxf(a[3] + b.w, 0.f);
+          float v0 = fmaxf(a[0] + b.x, 0.f), v1 = fmaxf(a[1] + b.y, 0.f), v2 = fmaxf(a[2] + b.z, 0.f), v3 = fmaxf(a[3] + b.w, 0.f);
+          if constexpr (DROP) {
+            // unit u = col0 + 4g + e; counter (u >> 2, image, token, pass); tile row `row` is token `row` of image m0 / 256
+            const int col0 = n0 + wc * 64 + qj * 32 + cb * 16;
+            const uint4 r = philox4x32_10(make_uint4((uint32_t)(col0 >> 2) + (uint32_t)g, d.image_base + (uint32_t)(m0 / G2_BM),
+                                                     (uint32_t)row, d.pass), d.k0, d.k1);
+            const bool k0 = r.x >= d.t, k1 = r.y >= d.t, k2 = r.z >= d.t, k3 = r.w >= d.t;
+            v0 = k0 ? v0 * d.s : 0.f;
+            v1 = k1 ? v1 * d.s : 0.f;
+            v2 = k2 ? v2 * d.s : 0.f;
+            v3 = k3 ? v3 * d.s : 0.f;
+            if (d.mask_out != nullptr)
+              *reinterpret_cast<uint32_t*>(d.mask_out + (long long)(m0 + row) * (2 * f.hidden) + col0 + 4 * g) =
+                  (uint32_t)k0 | ((uint32_t)k1 << 8) | ((uint32_t)k2 << 16) | ((uint32_t)k3 << 24);
+          }
           uint2 o;
           o.x = (uint32_t)f32_to_bf16_bits(v0) | ((uint32_t)f32_to_bf16_bits(v1) << 16);
           o.y = (uint32_t)f32_to_bf16_bits(v2) | ((uint32_t)f32_to_bf16_bits(v3) << 16);
@@ -482,8 +500,16 @@ __device__ __forceinline__ void g2_fuse2_epilogue(const GemmProblem& pr, const F
   }
 }
 
-__global__ __launch_bounds__(512, 2) void gemm256_fuse2_kernel(GemmProblem pr, Fuse2 f) {
+// The plain form (DROP = false) takes no dropout argument at all: its kernel arguments — and so its code, down to the offsets
+// of the hidden arguments — are those it had before the dropout form existed.  DROP = true takes one Fuse2Drop.
+__device__ __forceinline__ Fuse2Drop fuse2_drop() { return Fuse2Drop{}; }
+__device__ __forceinline__ Fuse2Drop fuse2_drop(const Fuse2Drop& d) { return d; }
+
+template <bool DROP, typename... Drop>
+__global__ __launch_bounds__(512, 2) void gemm256_fuse2_kernel(GemmProblem pr, Fuse2 f, Drop... drop) {
+  static_assert(sizeof...(Drop) == (DROP ? 1 : 0), "the dropout form takes exactly one Fuse2Drop");
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  const Fuse2Drop d = fuse2_drop(drop...);
   G2Acc acc;
   int m0, n0, tn;
   G2_CLOCK(0);
@@ -494,8 +520,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_fuse2_kernel(GemmProblem pr, F
   const int tiles_per_head = f.hidden >> 8;
   const int head = tn >= tiles_per_head ? 1 : 0;
   const int slab = tn - head * tiles_per_head;
-  if (f.n_out[head] == 128) g2_fuse2_epilogue<2>(pr, f, acc, smem, head, slab, m0, n0, lane, wave);
-  else g2_fuse2_epilogue<1>(pr, f, acc, smem, head, slab, m0, n0, lane, wave);
+  if (f.n_out[head] == 128) g2_fuse2_epilogue<2, DROP>(pr, f, d, acc, smem, head, slab, m0, n0, lane, wave);
+  else g2_fuse2_epilogue<1, DROP>(pr, f, d, acc, smem, head, slab, m0, n0, lane, wave);
   G2_CLOCK(5);
 }
 
@@ -564,10 +590,11 @@ int launch_pack_w2_fragments(const uint16_t* w2, int n_out, int hidden, uint16_t
 // SALAD score + cluster MLPs, both layers (see gemm256_fuse2_kernel).  X rows as in GemmProblem (row-group addressing),
 // W1 [2*hidden, C] + b1, second layers W2s [m, hidden] + b2s -> S[slabs][M][m], W2c [l, hidden] + b2c -> F[slabs][M][l],
 // slabs = hidden / 256.  Returns VPR_ERR_UNSUPPORTED for shapes outside the tile geometry (the caller falls back).
+// drop (may be null): the dropout form, gemm256_fuse2_kernel<true>; needs group_rows == 256 (tile row = token of one image).
 int launch_salad_mlps_fused(const uint16_t* X, int ldx, int group_rows, long long group_stride, const uint16_t* W1, const float* b1,
                             const uint16_t* W2s, const float* b2s, const uint16_t* W2c, const float* b2c,
                             float* S, float* F, int M, int C, int hidden, int m, int l, hipStream_t stream,
-                            const uint16_t* W2s_frag, const uint16_t* W2c_frag) {
+                            const uint16_t* W2s_frag, const uint16_t* W2c_frag, const Fuse2Drop* drop) {
   if (!X || !W1 || !b1 || !W2s || !b2s || !W2c || !b2c || !S || !F || M <= 0) return VPR_ERR_INVALID_ARG;
   if ((M % G2_BM) || (hidden % 256) || hidden <= 0 || (C % 64) || C < 128) return VPR_ERR_UNSUPPORTED;
   if (!((m == 64 || m == 128) && (l == 64 || l == 128))) return VPR_ERR_UNSUPPORTED;      // 16 or 32 outputs per wave quarter
@@ -580,9 +607,17 @@ int launch_salad_mlps_fused(const uint16_t* X, int ldx, int group_rows, long lon
                 nullptr, nullptr, 1, 0, tune_or(TUNE_GEMM256_STAGGER, 0)};
   if ((reinterpret_cast<uintptr_t>(W2s_frag) | reinterpret_cast<uintptr_t>(W2c_frag)) & 15) return VPR_ERR_UNSUPPORTED;
   Fuse2 f{{W2s, W2c}, {W2s_frag, W2c_frag}, {b2s, b2c}, {S, F}, {m, l}, hidden};
+  if (drop != nullptr) {
+    if (group_rows != G2_BM || (reinterpret_cast<uintptr_t>(drop->mask_out) & 3)) return VPR_ERR_UNSUPPORTED;
+    static PerDeviceFlag attr_drop = {};
+    VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(gemm256_fuse2_kernel<true, Fuse2Drop>), G2_LDS, attr_drop));
+    VPR_TRY_LAUNCH(launch_kernel(gemm256_fuse2_kernel<true, Fuse2Drop>, dim3(g.tiles_m * g.tiles_n), dim3(512), G2_LDS, stream, g, f,
+                                 *drop));
+    return VPR_OK;
+  }
   static PerDeviceFlag attr = {};
-  VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(gemm256_fuse2_kernel), G2_LDS, attr));
-  VPR_TRY_LAUNCH(launch_kernel(gemm256_fuse2_kernel, dim3(g.tiles_m * g.tiles_n), dim3(512), G2_LDS, stream, g, f));
+  VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(gemm256_fuse2_kernel<false>), G2_LDS, attr));
+  VPR_TRY_LAUNCH(launch_kernel(gemm256_fuse2_kernel<false>, dim3(g.tiles_m * g.tiles_n), dim3(512), G2_LDS, stream, g, f));
   return VPR_OK;
 }
 

@@ -123,19 +123,6 @@ __global__ __launch_bounds__(256) void head_fwd_partial_kernel(
 // the mask.  DROP = false is the plain step.
 struct HeadDropout { uint32_t t, k0, k1; int step; float s; uint8_t* mask_out; };
 
-// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants): ten rounds of two 32x32 -> 64 multiplies.
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
-}
-
 __device__ __forceinline__ bool dropout_keep(const HeadDropout& d, int b, int j) {
   const uint4 r = philox4x32_10(make_uint4((uint32_t)j >> 2, (uint32_t)b, (uint32_t)d.step, 0u), d.k0, d.k1);
   const int w = j & 3;

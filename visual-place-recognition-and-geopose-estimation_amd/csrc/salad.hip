@@ -514,7 +514,9 @@ static int salad_stage_token(const SaladArgs& a, const uint16_t* cls, long long 
 
 // Stage M: score + cluster MLPs on the B*n patch rows -> S, F (salad_slabs() partial-sum slabs) in the workspace.
 // patch row r of image b at patch + b*patch_img_stride + r*C (addressed in place).
-static int salad_stage_mlps(const SaladArgs& a, const uint16_t* patch, long long patch_img_stride, hipStream_t stream) {
+// drop (may be null): dropout on the hidden layer — the fused route only (VPR_ERR_UNSUPPORTED on the unfused one).
+static int salad_stage_mlps(const SaladArgs& a, const uint16_t* patch, long long patch_img_stride, hipStream_t stream,
+                            const Fuse2Drop* drop = nullptr) {
   if (!patch) return VPR_ERR_INVALID_ARG;
   if (patch_img_stride % 8) return VPR_ERR_UNSUPPORTED;
   uint16_t* H = reinterpret_cast<uint16_t*>(a.ws + a.p.off_H);
@@ -524,7 +526,8 @@ static int salad_stage_mlps(const SaladArgs& a, const uint16_t* patch, long long
   const int rows = a.B * a.n, hidden = a.hidden;
   if (salad_slabs(a.n, a.C, a.m, a.l, hidden) == 2)
     return launch_salad_mlps_fused(patch, a.C, a.n, patch_img_stride, w->w1_sc, w->b1_sc, w->w2_s, w->b2_s, w->w2_c, w->b2_c,
-                                   S, F, rows, a.C, hidden, a.m, a.l, stream, w->w2_s_frag, w->w2_c_frag);
+                                   S, F, rows, a.C, hidden, a.m, a.l, stream, w->w2_s_frag, w->w2_c_frag, drop);
+  if (drop != nullptr) return VPR_ERR_UNSUPPORTED;
   // unfused: layer 1 on the 256 x 256-tile kernel (34 of SALAD's 38 GFLOP; B tiles x 4 = one full wave of workgroups at
   // B = 64), hidden activations through HBM as bf16, the two second layers as one grouped launch
   const GemmProblem l1_sc{patch, a.C, a.n, patch_img_stride, w->w1_sc, a.C, w->b1_sc, 1, H, 2 * hidden, 1, rows, 2 * hidden, a.C, 0, 0};
@@ -632,6 +635,36 @@ extern "C" int vpr_salad_aggregate_split(const uint16_t* patch_tokens, const uin
   if (patches_per_image < 1 || C <= 0) return VPR_ERR_INVALID_ARG;
   return salad_run(patch_tokens, (long long)patches_per_image * C, cls_tokens, C, B, patches_per_image, C, w, dustbin,
                    m, l, t, hidden, sinkhorn_iters, out_f32, out_bf16, workspace, workspace_bytes, stream);
+}
+
+// Train mode (include/vpr_amd.h, vpr_salad_aggregate_train): the hub model's Dropout layers of score / cluster_features
+// active.  Stage M runs first — it is the stage that may refuse (dropout exists on the fused route only), so a refused call
+// has launched nothing; stages T and A are those of the eval form.
+extern "C" int vpr_salad_aggregate_train(const uint16_t* patch, long long patch_img_stride, const uint16_t* cls,
+                                         long long cls_stride, int B, int n, int C, const vpr_salad_weights* w, float dustbin,
+                                         int m, int l, int t, int hidden, int sinkhorn_iters, double dropout_p, uint64_t seed,
+                                         uint32_t pass, long long image_base, float* out_f32, uint16_t* out_bf16,
+                                         uint8_t* mask_out, void* workspace, size_t workspace_bytes, void* stream_) {
+  if (!(dropout_p >= 0.0 && dropout_p < 1.0)) return VPR_ERR_INVALID_ARG;          // NaN fails both comparisons
+  if (image_base < 0 || B <= 0 || image_base + B > (1LL << 32)) return VPR_ERR_INVALID_ARG;
+  if (!patch || !cls || !out_f32) return VPR_ERR_INVALID_ARG;
+  SaladArgs a;
+  VPR_TRY_LAUNCH(salad_args(&a, B, n, C, m, l, t, hidden, w, workspace, workspace_bytes, true));
+  if (salad_slabs(n, C, m, l, hidden) != 2) return VPR_ERR_UNSUPPORTED;           // no mask on the unfused route
+  if ((cls_stride % 8) || cls_stride > 0x7fffffffLL) return VPR_ERR_UNSUPPORTED;  // stage T's own refusal, checked up front
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  Fuse2Drop d;
+  d.t = (uint32_t)floor(dropout_p * 4294967296.0);   // p * 2^32 < 2^32: fits
+  d.s = (float)(1.0 / (1.0 - dropout_p));
+  d.k0 = (uint32_t)(seed & 0xffffffffu);
+  d.k1 = (uint32_t)(seed >> 32);
+  d.pass = pass;
+  d.image_base = (uint32_t)image_base;
+  d.mask_out = mask_out;
+  const bool drop = dropout_p > 0.0 || mask_out != nullptr;      // p = 0 without a mask: the eval kernel (the same bits)
+  VPR_TRY_LAUNCH(salad_stage_mlps(a, patch, patch_img_stride, stream, drop ? &d : nullptr));
+  VPR_TRY_LAUNCH(salad_stage_token(a, cls, cls_stride, stream));
+  return salad_stage_aggregate(a, dustbin, sinkhorn_iters, out_f32, out_bf16, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

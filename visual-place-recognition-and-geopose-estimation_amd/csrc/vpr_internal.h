@@ -29,11 +29,16 @@ int launch_gemm_nt_fp8(const uint8_t* A, int lda, const float* a_scale, const ui
                        float* C, int ldc, int M, int N, int K, hipStream_t stream);
 int launch_gemm256(const GemmProblem& problem, hipStream_t stream);   // gemm256.hip: 256x256 tiles, K >= 128
 // gemm256.hip: SALAD score + cluster MLPs with the second layers fused into the layer-1 tile epilogue; S / F receive
-// hidden / 256 partial-sum slabs of [M][m] / [M][l] f32 (slab 0 carries the bias), to be added in slab order
+// hidden / 256 partial-sum slabs of [M][m] / [M][l] f32 (slab 0 carries the bias), to be added in slab order.
+// Fuse2Drop: dropout on the hidden layer (vpr_salad_aggregate_train): unit u of token `token` of image image_base + b is kept
+// iff Philox4x32-10 word u & 3 of counter (u >> 2, image, token, pass) under key (k0, k1) is >= t; kept values are scaled by
+// s; mask_out (may be null, 4-byte aligned) receives [M][2*hidden] uint8, 1 = kept.
+struct Fuse2Drop { uint32_t t, k0, k1, pass, image_base; float s; uint8_t* mask_out; };
 int launch_salad_mlps_fused(const uint16_t* X, int ldx, int group_rows, long long group_stride, const uint16_t* W1, const float* b1,
                             const uint16_t* W2s, const float* b2s, const uint16_t* W2c, const float* b2c,
                             float* S, float* F, int M, int C, int hidden, int m, int l, hipStream_t stream,
-                            const uint16_t* W2s_frag = nullptr, const uint16_t* W2c_frag = nullptr);
+                            const uint16_t* W2s_frag = nullptr, const uint16_t* W2c_frag = nullptr,
+                            const Fuse2Drop* drop = nullptr);
 // gemm256.hip, fp8 form: e4m3 operands with per-row scales, f32 out (kNN score tile of a >= 384-query gathered batch)
 int launch_gemm256_fp8(const uint8_t* A, int lda, const float* a_scale, const uint8_t* W, int ldw, const float* w_scale,
                        float* C, int ldc, int M, int N, int K, hipStream_t stream, int ksplit = 1, long long slab_stride = 0);

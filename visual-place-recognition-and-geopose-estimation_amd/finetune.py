@@ -13,12 +13,22 @@ the HIP entry point vpr_head_train_step — three launches per batch, no host sy
 epoch, the 17 MB gradient of W1 never written to memory — checked against oracle/finetune.py (pinned to
 torch autograd + torch.optim.AdamW).  engine="torch" keeps the PyTorch-autograd loop (CPU tensors, or an
 explicit A/B on the GPU: scripts/head_train_bench.py) and is never chosen silently.
+
+Train-mode descriptors.  The reference calls model.train() every epoch (dinov2salad_finetuning.py:115), and that call
+reaches the feature extractor, which only torch.no_grad() guards (:34-37): the hub SALAD's two Dropout(0.3) layers (in
+`score` and `cluster_features`, modules.SaladAggregator) are active while the head trains, so the head sees a freshly
+dropout-noised descriptor for every image in every epoch; validation runs in model.eval(), on clean descriptors.  The
+DINOv2 trunk has no active dropout or drop-path, so only the aggregation is stochastic: `TokenCache` keeps the backbone
+tokens (patch [N,n,C] + cls [N,C] bf16 in HBM, cache_tokens / cache_tokens_from_images) and finetune_head re-aggregates
+all N descriptors before every epoch with fresh masks (vpr_salad_aggregate_train, pass = epoch, image = row of the
+cache).  A descriptor tensor keeps the frozen-eval behaviour.
 """
 from __future__ import annotations
 
 import json
 import os
-from typing import Callable, Iterable, Optional
+from dataclasses import dataclass
+from typing import Callable, Iterable, Optional, Union
 
 import numpy as np
 import torch
@@ -57,11 +67,130 @@ def cache_descriptors_from_images(extractor: nn.Module, image_dir: str, filename
     return out
 
 
-def finetune_head(model: DINOv2RegressionModel, descriptors: torch.Tensor, labels: np.ndarray,
+@dataclass
+class TokenCache:
+    """Backbone tokens of a dataset, cached once on the GPU: patch [N, n, C] and cls [N, C], bf16 (the layout the HIP
+    backbone computes in).  At the reference's shapes (6378 images, n = 256, C = 1024) 3.4 GB of HBM.  `aggregator` (a
+    modules.SaladAggregator, optional) supplies the SALAD weights; finetune_head falls back to the model's own.
+    Row i is image i: its global image index for the dropout masks (vpr_salad_aggregate_train)."""
+    patch: torch.Tensor
+    cls: torch.Tensor
+    aggregator: Optional[nn.Module] = None
+
+    CHUNK = 64          # images per aggregation call (the kernels' batch of the pipeline)
+
+    def __post_init__(self):
+        if self.patch.dim() != 3 or self.cls.dim() != 2 or self.cls.shape != (self.patch.shape[0], self.patch.shape[2]):
+            raise ValueError(f"TokenCache: patch must be [N, n, C] and cls [N, C], got {tuple(self.patch.shape)} / "
+                             f"{tuple(self.cls.shape)}")
+        if self.patch.dtype != torch.bfloat16 or self.cls.dtype != torch.bfloat16:
+            raise ValueError("TokenCache: tokens are cached as bf16")
+
+    def __len__(self) -> int:
+        return self.patch.shape[0]
+
+    @property
+    def device(self) -> torch.device:
+        return self.patch.device
+
+    @property
+    def is_cuda(self) -> bool:
+        return self.patch.is_cuda and self.cls.is_cuda
+
+    def _agg(self, aggregator):
+        agg = aggregator if aggregator is not None else self.aggregator
+        if agg is None:
+            raise ValueError("TokenCache: no SaladAggregator to aggregate with (pass one, or build the cache with one)")
+        return agg
+
+    @torch.no_grad()
+    def descriptors(self, aggregator: Optional[nn.Module] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Eval-mode descriptors [N, 8448] f32 (no dropout), aggregated in chunks of at most CHUNK images."""
+        from . import torch_ops
+        agg = self._agg(aggregator)
+        w = agg._packed or agg.pack()
+        n = len(self)
+        for lo in range(0, n, self.CHUNK):
+            hi = min(n, lo + self.CHUNK)
+            d, _ = torch.ops.vpr.salad_aggregate_split(self.patch[lo:hi], self.cls[lo:hi], torch_ops.weight_list(w), w.dustbin, 3)
+            if out is None:
+                out = torch.empty((n, d.shape[1]), dtype=torch.float32, device=self.device)
+            out[lo:hi] = d
+        return out
+
+    @torch.no_grad()
+    def train_descriptors(self, out: torch.Tensor, seed: int, pass_index: int, aggregator: Optional[nn.Module] = None,
+                          dropout_p: Optional[float] = None) -> torch.Tensor:
+        """Training-mode descriptors of every row, written into out [N, 8448] f32 in place: Dropout(p) active in the score /
+        cluster MLPs (p = the aggregator's, or dropout_p), masks keyed by (seed, pass_index, row, token, unit)."""
+        from . import ops
+        agg = self._agg(aggregator)
+        p = agg.dropout_p() if dropout_p is None else float(dropout_p)
+        w = agg._packed or agg.pack()
+        for lo in range(0, len(self), self.CHUNK):
+            hi = min(len(self), lo + self.CHUNK)
+            ops.salad_aggregate_train((self.patch[lo:hi], self.cls[lo:hi]), w, p, seed, pass_index, image_base=lo,
+                                      want_bf16=False, out=out[lo:hi])
+        return out
+
+
+def _split_tokens(t) -> tuple:
+    from .backbone import SplitTokens
+    if not isinstance(t, SplitTokens):
+        t = SplitTokens(t[:, 1:], t[:, 0])
+    return t.patch.to(torch.bfloat16), t.cls.to(torch.bfloat16)
+
+
+@torch.no_grad()
+def cache_tokens(extractor: nn.Module, image_batches: Iterable[torch.Tensor]) -> TokenCache:
+    """The frozen backbone over all batches -> TokenCache (the counterpart of cache_descriptors for train-mode SALAD).
+    extractor: a modules.DinoV2Salad (its backbone computes the tokens, its aggregator is kept for the aggregation)."""
+    patches, clss = [], []
+    for x in image_batches:
+        p, c = _split_tokens(extractor.backbone(x, split=True))
+        patches.append(p.contiguous())
+        clss.append(c.contiguous())
+    return TokenCache(torch.cat(patches), torch.cat(clss), extractor.aggregator)
+
+
+@torch.no_grad()
+def cache_tokens_from_images(extractor: nn.Module, image_dir: str, filenames, *, batch_size: int = 64,
+                             device: str = "cuda", prep=None) -> TokenCache:
+    """cache_descriptors_from_images for tokens: same loader, same preprocessing, file-list order; stores the
+    SplitTokens of extractor.backbone(x, split=True), the backbone forward replayed from one HIP graph per batch shape."""
+    from .graphed import GraphedForward
+    from .loader import ImageBatchLoader
+    from .preprocess import HALF_MEAN, HALF_STD, ResizeNormalize
+    dev = torch.device(device)
+    extractor = extractor.to(dev).eval()
+    prep = prep or ResizeNormalize(224, "bilinear", HALF_MEAN, HALF_STD, torch.bfloat16)
+    backbone = lambda x: extractor.backbone(x, split=True)
+    fwd = GraphedForward(backbone, module=extractor) if dev.type == "cuda" else backbone
+    filenames = list(filenames)
+    patch = cls = None
+    for idxs, _, u8 in ImageBatchLoader(image_dir, filenames, batch_size, dev):
+        p, c = _split_tokens(fwd(prep(u8)))
+        if patch is None:
+            patch = torch.empty((len(filenames),) + tuple(p.shape[1:]), dtype=torch.bfloat16, device=dev)
+            cls = torch.empty((len(filenames), c.shape[1]), dtype=torch.bfloat16, device=dev)
+        rows = torch.tensor(idxs, device=dev)
+        patch[rows] = p
+        cls[rows] = c
+    return TokenCache(patch, cls, extractor.aggregator)
+
+
+def default_salad_dropout_seed(seed: int) -> int:
+    """The SALAD dropout key finetune_head uses when it is given none: a fixed function of its `seed`, distinct from the
+    head's default_dropout_seed (another SeedSequence entropy), a 64-bit value."""
+    return int(np.random.SeedSequence([int(seed) & 0xFFFFFFFFFFFFFFFF, 0x5A1AD]).generate_state(1, np.uint64)[0])
+
+
+def finetune_head(model: DINOv2RegressionModel, descriptors: Union[torch.Tensor, TokenCache], labels: np.ndarray,
                   epochs: int = 100, batch_size: int = 16, lr: float = 1e-5, save_dir: Optional[str] = None,
                   val: Optional[tuple] = None, seed: int = 0, log: Callable[[str], None] = print,
                   engine: str = "auto", loss: str = "mse", huber_delta: float = 1.0, weight_decay: float = 1e-2,
-                  lr_schedule: Optional[Callable[[int, list], float]] = None, dropout_seed: Optional[int] = None) -> dict:
+                  lr_schedule: Optional[Callable[[int, list], float]] = None, dropout_seed: Optional[int] = None,
+                  salad_dropout_seed: Optional[int] = None) -> dict:
     """Trains model.regressor on cached descriptors.  labels [N,2] raw (lat, lon); they are
     standardised with a scaler fitted here (returned and, if save_dir, dumped as JSON).
     val = (val_descriptors, val_labels_raw) for the per-epoch de-normalised report.
@@ -77,9 +206,36 @@ def finetune_head(model: DINOv2RegressionModel, descriptors: torch.Tensor, label
     :113-122, swin_attempt_2.py:114-123; modules.SwinMLPRegressionModel), p read from the module at every pass.  Its masks are
     a pure function of (dropout_seed, step, position in the batch, hidden unit) (include/vpr_amd.h); dropout_seed None = derived
     from `seed` (default_dropout_seed), so a run is reproducible from its arguments.  The torch engine draws its masks from
-    torch's RNG: once p > 0 the two engines agree in distribution, not bit for bit."""
+    torch's RNG: once p > 0 the two engines agree in distribution, not bit for bit.
+    descriptors may be a TokenCache instead (train-mode SALAD, dinov2salad_finetuning.py:34-37,115: the aggregator's
+    Dropout layers active while the head trains): before every epoch e all N training descriptors are re-aggregated in
+    place with fresh masks — vpr_salad_aggregate_train, pass = e, image = cache row, key salad_dropout_seed (None = derived
+    from `seed`: default_salad_dropout_seed, distinct from the head's) — then the epoch runs as on cached descriptors.  Both
+    engines use the HIP aggregation (the engine concerns the head step only); a TokenCache must be on the GPU.  The
+    aggregator is the cache's, or model.feature_extractor.aggregator.  val[0] may be a TokenCache too: aggregated once, in
+    eval mode (the reference validates under model.eval())."""
     if loss not in ("mse", "huber"):
         raise ValueError(f"finetune_head: loss must be 'mse' or 'huber', got {loss!r}")
+    tokens, agg = None, None
+    if isinstance(descriptors, TokenCache):
+        tokens = descriptors
+        if not tokens.is_cuda:
+            raise RuntimeError("finetune_head: a TokenCache is re-aggregated every epoch by the HIP SALAD kernels and must be on "
+                               "the GPU (there is no CPU fallback); pass cached descriptors to train on the CPU")
+        agg = tokens.aggregator if tokens.aggregator is not None else getattr(model.feature_extractor, "aggregator", None)
+        if agg is None:
+            raise ValueError("finetune_head: the TokenCache has no aggregator and model.feature_extractor has none either")
+        if salad_dropout_seed is None:
+            salad_dropout_seed = default_salad_dropout_seed(seed)
+        if not 0 <= int(salad_dropout_seed) < 1 << 64:
+            raise ValueError(f"finetune_head: salad_dropout_seed must be an unsigned 64-bit integer, got {salad_dropout_seed!r}")
+        salad_p = agg.dropout_p()
+        descriptors = tokens.descriptors(agg) if salad_p == 0.0 else \
+            torch.empty((len(tokens), agg.token_dim + agg.cluster_dim * agg.num_clusters), dtype=torch.float32,
+                        device=tokens.device)                      # p = 0: eval bits, the same every epoch: aggregated once
+    if val is not None and isinstance(val[0], TokenCache):
+        val = (val[0].descriptors(val[0].aggregator if val[0].aggregator is not None else agg or
+                                  getattr(model.feature_extractor, "aggregator", None)), val[1])
     dev = descriptors.device
     if engine not in ("auto", "hip", "torch"):
         raise ValueError(f"finetune_head: unknown engine {engine!r}")
@@ -99,6 +255,8 @@ def finetune_head(model: DINOv2RegressionModel, descriptors: torch.Tensor, label
         p.requires_grad_(True)
     opt = torch.optim.AdamW(head.parameters(), lr=lr, weight_decay=weight_decay)
     loss_fn = nn.MSELoss() if loss == "mse" else nn.HuberLoss(delta=huber_delta)
+    if tokens is not None and salad_p > 0.0:
+        tokens.train_descriptors(descriptors, int(salad_dropout_seed), 0, agg)      # epoch 0's, before the trainer reads X
     hip = _HipHeadTrainer(head, descriptors.float().contiguous(), y, opt, loss, huber_delta, int(dropout_seed), batch_size) \
         if engine == "hip" else None
     g = torch.Generator(device="cpu").manual_seed(seed)
@@ -110,6 +268,8 @@ def finetune_head(model: DINOv2RegressionModel, descriptors: torch.Tensor, label
             json.dump({"mean_": scaler.mean_.tolist(), "scale_": scaler.scale_.tolist()}, f)
     for epoch in range(epochs):
         head.train()
+        if tokens is not None and salad_p > 0.0 and epoch > 0:   # re-aggregate in place (the trainer's X is this buffer)
+            tokens.train_descriptors(descriptors, int(salad_dropout_seed), epoch, agg)
         if lr_schedule is not None:
             for grp in opt.param_groups:
                 grp["lr"] = float(lr_schedule(epoch, history))

@@ -90,7 +90,10 @@ class SaladAggregator(nn.Module):
     def forward(self, tokens, want_bf16: bool = False):
         """tokens [B, 1+n, C] (cls first) or a backbone.SplitTokens pair -> descriptor [B, 8448] f32 (and a bf16 copy).
         bf16 tokens: the bf16-operand kernels (benchmark path); f32 tokens: the f32-accurate aggregation with f32
-        weights — the reference's precision (its extractor runs in fp32)."""
+        weights — the reference's precision (its extractor runs in fp32).
+        Always eval arithmetic, whatever `.training` says: the two Dropout(0.3) layers of score / cluster_features are
+        never applied here.  The training-mode descriptor (those Dropouts active, as under the fine-tuning script's
+        model.train()) is forward_train."""
         first = tokens.patch if isinstance(tokens, SplitTokens) else tokens
         if first.dtype == torch.float32:
             w32 = self._packed_f32 or self.pack_f32()
@@ -106,6 +109,35 @@ class SaladAggregator(nn.Module):
                                                       bool(tokens.token_ready))
         else:
             desc, desc16 = _vpr.salad_aggregate(tokens, torch_ops.weight_list(w), w.dustbin, 3)
+        return (desc, desc16) if want_bf16 else desc
+
+
+    def dropout_p(self) -> float:
+        """p of the two Dropout layers (score[1], cluster_features[1]); the fused kernel draws one mask rate for both."""
+        ps, pc = float(self.score[1].p), float(self.cluster_features[1].p)
+        if ps != pc:
+            raise ValueError(f"SaladAggregator: score[1].p = {ps} and cluster_features[1].p = {pc} differ; the training-mode "
+                             "aggregation applies one dropout rate to both MLPs")
+        return ps
+
+    @torch.no_grad()
+    def forward_train(self, tokens, seed: int, pass_index: int, image_base: int = 0, want_bf16: bool = False):
+        """The descriptor in training mode: Dropout(p) of score[1] / cluster_features[1] active (the hub model while
+        dinov2salad_finetuning.py:115 has it in train(); the token MLP has no dropout).  tokens = [B, 1+n, C] bf16 (cls
+        first) or a backbone.SplitTokens pair of bf16 tensors.  The mask is a pure function of (seed, pass_index,
+        image_base + b, token, unit) — include/vpr_amd.h, vpr_salad_aggregate_train — so the same image gets the same mask
+        in any batching: pass the image's global index through image_base.  Reads p from the modules at every call (equal
+        p required: ValueError otherwise).  Independent of `.training`."""
+        p = self.dropout_p()
+        w = self._packed or self.pack()
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        seed = seed - (1 << 64) if seed >= 1 << 63 else seed          # the op's int is signed
+        if isinstance(tokens, SplitTokens):
+            desc, desc16 = _vpr.salad_aggregate_train(tokens.patch, tokens.cls, torch_ops.weight_list(w), w.dustbin, 3, p, seed,
+                                                      int(pass_index), int(image_base))
+        else:
+            desc, desc16 = _vpr.salad_aggregate_train(tokens, None, torch_ops.weight_list(w), w.dustbin, 3, p, seed,
+                                                      int(pass_index), int(image_base))
         return (desc, desc16) if want_bf16 else desc
 
 

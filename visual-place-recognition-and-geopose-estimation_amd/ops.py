@@ -259,6 +259,62 @@ def salad_aggregate_split(patch: torch.Tensor, cls: torch.Tensor, w: SaladWeight
     return out, out16
 
 
+def _bf16_tokens(tokens, what: str):
+    """[B, 1+n, C] bf16 (cls first) or a (patch [B,n,C], cls [B,C]) bf16 pair -> (patch ptr, patch image stride, cls ptr,
+    cls stride, B, n, C, device); strides in elements."""
+    if isinstance(tokens, torch.Tensor):
+        _need(tokens, torch.bfloat16, "tokens", 3)
+        B, tpi, C = tokens.shape
+        return tokens.data_ptr() + 2 * C, tpi * C, tokens.data_ptr(), tpi * C, B, tpi - 1, C, tokens.device
+    patch, cls = tokens
+    _need(patch, torch.bfloat16, "patch", 3)
+    _need(cls, torch.bfloat16, "cls", 2)
+    B, n, C = patch.shape
+    if tuple(cls.shape) != (B, C):
+        raise RuntimeError(f"{what}: cls must be [B, C] = {(B, C)}, got {tuple(cls.shape)}")
+    return patch.data_ptr(), n * C, cls.data_ptr(), C, B, n, C, patch.device
+
+
+def salad_aggregate_train(tokens, w: SaladWeights, dropout_p: float, seed: int, pass_index: int, image_base: int = 0,
+                          sinkhorn_iters: int = 3, want_bf16: bool = True, mask_out: Optional[torch.Tensor] = None,
+                          out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The aggregation in training mode: Dropout(dropout_p) active in the score / cluster MLPs, as the hub model runs while
+    dinov2salad_finetuning.py:115 has it in train() (vpr_salad_aggregate_train).  `tokens` = [B, 1+n, C] bf16 (cls first) or a
+    (patch [B,n,C], cls [B,C]) bf16 pair.  The mask is a pure function of (seed, pass_index, image_base + b, token, unit): a
+    dataset aggregated in any chunking gives the same bits.  seed: unsigned 64-bit; pass_index: unsigned 32-bit.
+    mask_out (uint8 [B*n, 2*hidden], optional) receives the mask, 1 = kept.  dropout_p = 0 gives the bits of
+    salad_aggregate_split.  out (f32 [B, t+l*m], contiguous, optional): where the descriptor goes (e.g. rows of a
+    fine-tuning buffer).  -> (descriptor f32 [B, t+l*m], bf16 copy or None)."""
+    patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, Ct, device = _bf16_tokens(tokens, "salad_aggregate_train")
+    C, hidden, m, l, t = w.validate()
+    if Ct != C:
+        raise RuntimeError(f"tokens have C={Ct}, weights expect {C}")
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"salad_aggregate_train: seed must be an unsigned 64-bit integer, got {seed!r}")
+    if not 0 <= int(pass_index) < 1 << 32:
+        raise ValueError(f"salad_aggregate_train: pass_index must be an unsigned 32-bit integer, got {pass_index!r}")
+    if mask_out is not None:
+        _need(mask_out, torch.uint8, "mask_out", 2)
+        if tuple(mask_out.shape) != (B * n, 2 * hidden):
+            raise RuntimeError(f"mask_out must be [B*n, 2*hidden] = {(B * n, 2 * hidden)}, got {tuple(mask_out.shape)}")
+    L = _lib.lib()
+    ws = workspace("salad", L.vpr_salad_workspace_bytes(B, n, C, m, l, t, hidden), device, zero=True)
+    if out is None:
+        out = torch.empty((B, t + l * m), dtype=torch.float32, device=device)
+    else:
+        _need(out, torch.float32, "out", 2)
+        if tuple(out.shape) != (B, t + l * m):
+            raise RuntimeError(f"out must be [B, t+l*m] = {(B, t + l * m)}, got {tuple(out.shape)}")
+    out16 = torch.empty((B, t + l * m), dtype=torch.bfloat16, device=device) if want_bf16 else None
+    cw = w.c_struct()
+    st = L.vpr_salad_aggregate_train(ctypes.c_void_p(patch_ptr), patch_stride, ctypes.c_void_p(cls_ptr), cls_stride, B, n, C,
+                                     ctypes.byref(cw), float(w.dustbin), m, l, t, hidden, int(sinkhorn_iters),
+                                     float(dropout_p), int(seed), int(pass_index), int(image_base), _ptr(out), _ptr(out16),
+                                     _ptr(mask_out), _ptr(ws), ws.numel(), _stream())
+    _lib.check(st, "vpr_salad_aggregate_train")
+    return out, out16
+
+
 @dataclass
 class SaladWeightsF32(SaladWeights):
     """The same ten tensors, all f32 (vpr_salad_weights_f32): operands of the f32-accurate aggregation."""

@@ -5,6 +5,7 @@ The reference's seam is `nn.Module.forward` (dinov2salad/dinov2salad_validation.
 that seam, so the HIP hot path is visible to PyTorch's dispatcher like any other operator:
 
     torch.ops.vpr.salad_aggregate / salad_aggregate_split / salad_aggregate_f32
+    torch.ops.vpr.salad_aggregate_train                (training mode: Dropout active in the score / cluster MLPs)
     torch.ops.vpr.knn_topk / knn_topk_fp8 / topk_merge
     torch.ops.vpr.pose_head / ln_meanpool_head
     torch.ops.vpr.head_train_epoch                     (head-only fine-tuning pass; mutates parameters and AdamW moments)
@@ -87,6 +88,26 @@ def salad_aggregate_f32(patch: Tensor, cls: Tensor, weights: List[Tensor], dustb
 def _(patch, cls, weights, dustbin, sinkhorn_iters):
     B, D = patch.shape[0], _desc_width(weights)
     return patch.new_empty((B, D), dtype=torch.float32), patch.new_empty((B, D), dtype=torch.bfloat16)
+
+
+@torch.library.custom_op("vpr::salad_aggregate_train", mutates_args=())
+def salad_aggregate_train(tokens: Tensor, cls: Optional[Tensor], weights: List[Tensor], dustbin: float, sinkhorn_iters: int,
+                          dropout_p: float, seed: int, pass_index: int, image_base: int) -> Tuple[Tensor, Tensor]:
+    """The aggregation in training mode (Dropout(dropout_p) active in the score / cluster MLPs: the hub model under
+    dinov2salad_finetuning.py:115's model.train()).  cls None: tokens = [B, 1+n, C] bf16, cls first; else tokens = patch
+    [B, n, C] bf16 and cls [B, C] bf16.  The mask is a pure function of (seed, pass_index, image_base + b, token, unit) —
+    include/vpr_amd.h; seed is the 64 bits of the mask key (a negative value stands for its two's complement: the schema's
+    int is signed).  vpr_salad_aggregate_train."""
+    pair = tokens if cls is None else (tokens, cls)
+    out, out16 = ops.salad_aggregate_train(pair, _weights(weights, dustbin), dropout_p, seed & 0xFFFFFFFFFFFFFFFF, pass_index,
+                                           image_base, sinkhorn_iters, True)
+    return out, out16
+
+
+@salad_aggregate_train.register_fake
+def _(tokens, cls, weights, dustbin, sinkhorn_iters, dropout_p, seed, pass_index, image_base):
+    B, D = tokens.shape[0], _desc_width(weights)
+    return tokens.new_empty((B, D), dtype=torch.float32), tokens.new_empty((B, D), dtype=torch.bfloat16)
 
 
 # -------------------------------------------------------------------------------------------------------------- kNN
@@ -214,5 +235,5 @@ def _(X, Y, order, batch_size, W1, b1, W2, b2, m, v, first_step, lr, beta1, beta
     return X.new_empty(((order.shape[0] + batch_size - 1) // batch_size,), dtype=torch.float32)
 
 
-OPS = ("head_train_epoch", "head_train_epoch_dropout", "salad_aggregate", "salad_aggregate_split", "salad_aggregate_f32", "knn_topk", "knn_topk_fp8", "quantize_fp8_rows",
+OPS = ("head_train_epoch", "head_train_epoch_dropout", "salad_aggregate", "salad_aggregate_split", "salad_aggregate_f32", "salad_aggregate_train", "knn_topk", "knn_topk_fp8", "quantize_fp8_rows",
        "topk_merge", "pose_head", "ln_meanpool_head")
