@@ -38,6 +38,18 @@ class GemmProblemC(Structure):
                 ("C", c_void_p), ("ldc", c_int), ("out_is_bf16", c_int), ("M", c_int), ("N", c_int), ("K", c_int)]
 
 
+_P = c_void_p
+_GEMM = [_P, c_int, c_int, c_longlong, _P, c_int, _P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P]    # vpr_gemm_problem fields, stream
+# kNN family: operands (bf16: q, gallery; generic / fp8: q, q_scale, gallery, gallery_scale [, is_fp8 flag]), then B N D k,
+# then index_base vals idx, then ws ws_bytes; the checked forms add norm_bound, status, uncertified; stream last
+_KNN_BF16, _KNN_FP8 = [_P, _P] + [c_int] * 4, [_P, _P, _P, _P] + [c_int] * 4
+_KNN_ANY = [_P, _P, _P, _P] + [c_int] * 5
+_KNN_OUT, _KNN_WS, _KNN_CERT = [c_int, _P, _P], [_P, c_size_t], [c_float, _P, _P]
+# head training: X ldx idx | order n batch, Y ldy, dims, six parameter / moment pointers, step, lr beta1 beta2 eps wd, loss kind, delta, loss out
+_TRAIN_TAIL = [_P] * 6 + [c_int] + [c_double] * 5 + [c_int, c_double, _P]
+_TRAIN_STEP = [_P, c_longlong, _P, _P, c_longlong] + [c_int] * 4 + _TRAIN_TAIL
+_TRAIN_EPOCH = [_P, c_longlong, _P, c_int, c_int, _P, c_longlong] + [c_int] * 3 + _TRAIN_TAIL
+
 # name -> (restype, argtypes); kept in one table so tests can check every symbol is exported
 PROTOTYPES = {
     "vpr_status_string": (c_char_p, [c_int]),
@@ -67,32 +79,21 @@ PROTOTYPES = {
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "vpr_salad_sinkhorn_aggregate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                              c_int, c_float, c_int, c_void_p, c_void_p, c_void_p]),
-    "vpr_gemm_nt_bf16": (c_int, [c_void_p, c_int, c_int, c_longlong, c_void_p, c_int, c_void_p, c_int,
-                                 c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "vpr_gemm256_nt_bf16": (c_int, [c_void_p, c_int, c_int, c_longlong, c_void_p, c_int, c_void_p, c_int,
-                                    c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "vpr_gemm_nt_bf16": (c_int, _GEMM),
+    "vpr_gemm256_nt_bf16": (c_int, _GEMM),
     "vpr_gemm_nt_group_bf16": (c_int, [POINTER(GemmProblemC), c_int, c_void_p]),
     "vpr_knn_workspace_bytes": (c_size_t, [c_int] * 4),
-    "vpr_knn_topk": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                             c_void_p, c_size_t, c_void_p]),
-    "vpr_knn_topk_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                 c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "vpr_knn_topk_checked": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                     c_void_p, c_size_t, c_float, c_void_p, c_void_p, c_void_p]),
-    "vpr_knn_select_checked": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                       c_void_p, c_size_t, c_float, c_void_p, c_void_p, c_void_p]),
-    "vpr_knn_topk_fp8_checked": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                         c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_void_p, c_void_p, c_void_p]),
-    "vpr_knn_topk_exhaustive": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "vpr_knn_topk": (c_int, _KNN_BF16 + _KNN_OUT + _KNN_WS + [_P]),
+    "vpr_knn_topk_fp8": (c_int, _KNN_FP8 + _KNN_OUT + _KNN_WS + [_P]),
+    "vpr_knn_topk_checked": (c_int, _KNN_BF16 + _KNN_OUT + _KNN_WS + _KNN_CERT + [_P]),
+    "vpr_knn_select_checked": (c_int, _KNN_BF16 + _KNN_OUT + _KNN_WS + _KNN_CERT + [_P]),
+    "vpr_knn_topk_fp8_checked": (c_int, _KNN_FP8 + _KNN_OUT + _KNN_WS + _KNN_CERT + [_P]),
+    "vpr_knn_topk_exhaustive": (c_int, _KNN_ANY + _KNN_OUT + _KNN_WS + [_P]),
     "vpr_quantize_fp8_rows": (c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p]),
-    "vpr_knn_scores": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "vpr_knn_select": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                               c_void_p, c_size_t, c_void_p]),
-    "vpr_knn_topk_scores_stage": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                          c_void_p, c_size_t, c_void_p]),
-    "vpr_knn_topk_select_stage": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
-                                          c_void_p, c_void_p, c_void_p, c_size_t, c_float, c_void_p, c_void_p, c_void_p]),
+    "vpr_knn_scores": (c_int, [_P, _P, c_int, c_int, c_int] + _KNN_WS + [_P]),
+    "vpr_knn_select": (c_int, _KNN_BF16 + _KNN_OUT + _KNN_WS + [_P]),
+    "vpr_knn_topk_scores_stage": (c_int, _KNN_ANY + _KNN_WS + [_P]),
+    "vpr_knn_topk_select_stage": (c_int, _KNN_ANY + _KNN_OUT + _KNN_WS + _KNN_CERT + [_P]),
     "vpr_knn_scores_kernel_name": (c_char_p, [c_int, c_int, c_int]),
     "vpr_knn_scores_ptr": (c_void_p, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int)]),
     "vpr_topk_merge": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
@@ -127,22 +128,10 @@ PROTOTYPES = {
                                     c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "vpr_head_train_workspace_bytes": (c_size_t, [c_int] * 4),
     "vpr_head_train_state_floats": (c_longlong, [c_int] * 3),
-    "vpr_head_train_step": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_int,
-                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                    c_double, c_double, c_double, c_double, c_double, c_int, c_double, c_void_p, c_void_p, c_size_t,
-                                    c_void_p]),
-    "vpr_head_train_epoch": (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_int, c_void_p, c_longlong, c_int, c_int, c_int,
-                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                     c_double, c_double, c_double, c_double, c_double, c_int, c_double, c_void_p, c_void_p, c_size_t,
-                                     c_void_p]),
-    "vpr_head_train_step_dropout": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_int,
-                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                            c_double, c_double, c_double, c_double, c_double, c_int, c_double, c_void_p,
-                                            c_double, c_uint64, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "vpr_head_train_epoch_dropout": (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_int, c_void_p, c_longlong, c_int, c_int,
-                                             c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                             c_double, c_double, c_double, c_double, c_double, c_int, c_double, c_void_p,
-                                             c_double, c_uint64, c_void_p, c_size_t, c_void_p]),
+    "vpr_head_train_step": (c_int, _TRAIN_STEP + [_P, c_size_t, _P]),
+    "vpr_head_train_epoch": (c_int, _TRAIN_EPOCH + [_P, c_size_t, _P]),
+    "vpr_head_train_step_dropout": (c_int, _TRAIN_STEP + [c_double, c_uint64, _P, _P, c_size_t, _P]),      # p, seed, mask out
+    "vpr_head_train_epoch_dropout": (c_int, _TRAIN_EPOCH + [c_double, c_uint64, _P, c_size_t, _P]),
     "vpr_patchify_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "vpr_add_layernorm_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p,
                                        c_longlong, c_int, c_void_p]),

@@ -16,6 +16,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ._cache import tensor_key
+
 def gemm_autotune(enable: bool = True, tuning: bool = True, max_ms_per_gemm: int = 30) -> None:
     """PyTorch TunableOp for the backbone's four hipBLASLt GEMM shapes: during the (untimed) warm-up
     steps each new shape is timed against the library's candidate kernels and the fastest is kept
@@ -318,32 +320,31 @@ class DinoV2(nn.Module):
     def _embed_consts(self, img: torch.Tensor):
         """(patch-embedding weight [C, kpad] bf16, additive token offsets [B*n + B, C] bf16 in the
         split row layout: pos[1+p] + conv bias for the patch rows, cls + pos[0] for the cls rows)."""
-        B, Cin = img.shape[0], img.shape[1]
-        P, C, n = self.patch, self.embed_dim, self.num_patches
-        K = Cin * P * P
+        B, K = img.shape[0], img.shape[1] * self.patch * self.patch
         kpad = (K + 63) // 64 * 64
-        pe = self.patch_embed
-        key = (str(img.device), B, kpad, pe.weight.data_ptr(), pe.weight._version, pe.bias._version,
-               self.pos_embed.data_ptr(), self.pos_embed._version, self.cls_token._version)
-        # one entry per batch size (an evaluation loop alternates between its full and its last, ragged batch); an entry
-        # a HIP graph was captured on is pinned: the graph addresses its tensors for as long as it is replayed
-        cache = self.__dict__.setdefault("_embed_cache", {})
-        ent = cache.get(key)
-        if ent is None:
-            for k in [k for k, e in cache.items() if not e[2]][: max(0, len(cache) - 3)]:
-                del cache[k]
-            dev = img.device
-            w = torch.zeros((C, kpad), dtype=torch.bfloat16, device=dev)
-            w[:, :K] = pe.weight.detach().reshape(C, K).to(dev, torch.bfloat16)
-            pos = self.pos_embed.detach().float().to(dev)[0]                             # [1+n, C]
-            body = (pos[1:] + pe.bias.detach().float().to(dev)).to(torch.bfloat16)       # [n, C]
-            tail = (pos[0] + self.cls_token.detach().float().to(dev).view(C)).to(torch.bfloat16)
-            off = torch.cat([body.unsqueeze(0).expand(B, -1, -1).reshape(B * n, C),
-                             tail.unsqueeze(0).expand(B, -1)], dim=0).contiguous()
-            ent = cache[key] = [w, off, False]
-        if not ent[2] and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            ent[2] = True
-        return ent[0], ent[1]
+        # one entry per batch size (an evaluation loop alternates between its full and its last, ragged batch)
+        ps = (self.patch_embed.weight, self.patch_embed.bias, self.pos_embed, self.cls_token)
+        return self._cache("_embed_cache", 3).get((img.device, B, kpad, tensor_key(*ps)), self._build_embed_consts,
+                                                  (img.device, B, K, kpad), ps)
+
+    def _build_embed_consts(self, dev: torch.device, B: int, K: int, kpad: int):
+        pe, C, n = self.patch_embed, self.embed_dim, self.num_patches
+        w = torch.zeros((C, kpad), dtype=torch.bfloat16, device=dev)
+        w[:, :K] = pe.weight.detach().reshape(C, K).to(dev, torch.bfloat16)
+        pos = self.pos_embed.detach().float().to(dev)[0]                             # [1+n, C]
+        body = (pos[1:] + pe.bias.detach().float().to(dev)).to(torch.bfloat16)       # [n, C]
+        tail = (pos[0] + self.cls_token.detach().float().to(dev).view(C)).to(torch.bfloat16)
+        off = torch.cat([body.unsqueeze(0).expand(B, -1, -1).reshape(B * n, C),
+                         tail.unsqueeze(0).expand(B, -1)], dim=0).contiguous()
+        return w, off
+
+    def _cache(self, name: str, capacity: int):
+        """This module's graph-safe cache `name` (_cache.Cache), made on first use; kept out of the module's attributes proper."""
+        c = self.__dict__.get(name)
+        if c is None:
+            from . import ops
+            c = self.__dict__[name] = ops.cache(capacity)
+        return c
 
     cls_side_chain = True
     side_sync = "events"        # fork / join of the cls side chain: "events" (torch.cuda.Event), "light" (HIP events without the system-scope
@@ -428,19 +429,6 @@ class DinoV2(nn.Module):
     # final LayerNorm of the cls rows, before that stream is joined (modules.DinoV2Salad installs SALAD's token MLP here)
     cls_tail_hook = None
 
-    def _raw_tokens(self, M: int, Mp: int, C: int, dev: torch.device) -> torch.Tensor:
-        bufs = self.__dict__.setdefault("_raw_bufs", {})     # per (device, stream, shape): two streams never share it
-        key = (str(dev), torch.cuda.current_stream(dev).cuda_stream, M, C)
-        ent = bufs.get(key)
-        if ent is None:
-            if len(bufs) > 8:
-                for k in [k for k, e in bufs.items() if not e[1]]:       # entries a HIP graph addresses stay
-                    del bufs[k]
-            ent = bufs[key] = [torch.zeros((M, C), dtype=torch.bfloat16, device=dev), False]
-        if not ent[1] and torch.cuda.is_current_stream_capturing():
-            ent[1] = True
-        return ent[0]
-
     def _forward_hip_split(self, img: torch.Tensor) -> "SplitTokens":
         """The whole backbone on the GPU in the split row layout [B*n patch rows | B cls rows]:
         every linear layer runs as one library GEMM over the B*n patch rows — at n = 256 an exact
@@ -462,7 +450,7 @@ class DinoV2(nn.Module):
         dev, bf = img.device, torch.bfloat16
         w, off = self._embed_consts(img)
         a = ops.patchify_bf16(img.contiguous(), P, w.shape[1], 0)               # [Mp, kpad]
-        raw = self._raw_tokens(M, Mp, C, dev)       # persistent: its cls rows are zero and nothing ever writes them
+        raw = ops.zero_rows_bf16(M, C, dev)         # persistent per (device, stream, shape): its cls rows are zero and nothing ever writes them
         torch.mm(a, w.t(), out=raw[:Mp])
         blocks = self.blocks
         n0 = blocks[0].norm1
@@ -585,33 +573,34 @@ class DinoV2(nn.Module):
         """ClsLinearConsts of the LayerNorm-fused cls-row linears: entry 2i = block i's (norm1, qkv) with the
         cumulative bias before it (entry 0 unused: block 0's first LayerNorm is the embedding add+LN), entry
         2i+1 = block i's (norm2, fc1).  Static, rebuilt when the parameters change identity / version."""
-        from . import ops
         ps = [p for b in self.blocks for p in (b.qkv.weight, b.qkv.bias, b.fc1.weight, b.fc1.bias, b.proj.bias, b.fc2.bias,
                                                b.norm1.weight, b.norm1.bias, b.norm2.weight, b.norm2.bias)]
-        key = (str(device),) + tuple((p.data_ptr(), p._version) for p in ps)
-        if getattr(self, "_clsf_key", None) != key:
-            cum = self._cumulative_bias(device)
-            out = []
-            for i, b in enumerate(self.blocks):
-                out.append(None if i == 0 else
-                           ops.ClsLinearConsts.build(b.qkv.weight, b.qkv.bias, b.norm1.weight, b.norm1.bias, cum[2 * i - 1]))
-                out.append(ops.ClsLinearConsts.build(b.fc1.weight, b.fc1.bias, b.norm2.weight, b.norm2.bias, cum[2 * i]))
-            self._clsf, self._clsf_key = out, key
-        return self._clsf
+        return self._cache("_clsf", 2).get((device, tensor_key(*ps)), self._build_cls_fused_consts, (device,), ps)
+
+    def _build_cls_fused_consts(self, device: torch.device) -> list:
+        from . import ops
+        cum = self._cumulative_bias(device)
+        out = []
+        for i, b in enumerate(self.blocks):
+            out.append(None if i == 0 else
+                       ops.ClsLinearConsts.build(b.qkv.weight, b.qkv.bias, b.norm1.weight, b.norm1.bias, cum[2 * i - 1]))
+            out.append(ops.ClsLinearConsts.build(b.fc1.weight, b.fc1.bias, b.norm2.weight, b.norm2.bias, cum[2 * i]))
+        return out
 
     def _cumulative_bias(self, device: torch.device):
         """cum[2i] = sum of proj/fc2 biases up to and including block i's proj; cum[2i+1] adds its fc2
-        (f32, one [2L, C] tensor; rebuilt when the biases change identity, e.g. after a state-dict load)."""
-        key = (str(device),) + tuple(b.proj.bias.data_ptr() for b in self.blocks) + tuple(b.proj.bias._version for b in self.blocks)
-        if getattr(self, "_cum_key", None) != key:
-            rows, acc = [], torch.zeros(self.embed_dim, dtype=torch.float32, device=device)
-            for blk in self.blocks:
-                acc = acc + blk.proj.bias.detach().float().to(device)
-                rows.append(acc)
-                acc = acc + blk.fc2.bias.detach().float().to(device)
-                rows.append(acc)
-            self._cum_bias, self._cum_key = torch.stack(rows).contiguous(), key
-        return self._cum_bias
+        (f32, one [2L, C] tensor; rebuilt when a bias changes identity or version, e.g. after a state-dict load)."""
+        ps = [p for b in self.blocks for p in (b.proj.bias, b.fc2.bias)]
+        return self._cache("_cum_bias", 2).get((device, tensor_key(*ps)), self._build_cumulative_bias, (device,), ps)
+
+    def _build_cumulative_bias(self, device: torch.device) -> torch.Tensor:
+        rows, acc = [], torch.zeros(self.embed_dim, dtype=torch.float32, device=device)
+        for blk in self.blocks:
+            acc = acc + blk.proj.bias.detach().float().to(device)
+            rows.append(acc)
+            acc = acc + blk.fc2.bias.detach().float().to(device)
+            rows.append(acc)
+        return torch.stack(rows).contiguous()
 
     def fold_layerscale(self) -> "DinoV2":
         for blk in self.blocks:

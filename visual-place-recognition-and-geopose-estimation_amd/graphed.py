@@ -14,9 +14,11 @@ side stream is switched off inside the captured forward: fork / join branches re
 either way (`test_cls_side_chain_is_bit_identical_to_in_stream_path`, `test_graphed_forward_equals_eager`).
 
 A captured graph addresses its operands by raw pointer, including what the package caches between calls (workspaces,
-packed weights, batch-size-keyed backbone constants).  Those caches pin every entry that is handed out while a capture
-is in progress (`ops.capturing()`): a pinned entry is never freed or replaced in place, so graphs of several input
-shapes and eager calls can be interleaved freely.
+packed weights, batch-size-keyed and weight-derived backbone constants).  All of those live in one kind of cache,
+`_cache.Cache`, which pins every entry that is handed out while a capture is in progress (`ops.capturing()`): a pinned
+entry is never evicted, and never freed when its key's value is rebuilt (a workspace that has to grow), so graphs of
+several input shapes and eager calls can be interleaved freely.  Only `ops.drop_stream_caches()` forgets pinned entries:
+those keyed by a stream that is gone, with its graphs.
 
 Weights are addressed the same way: after changing parameters (a state-dict load, `fold_layerscale()`, `pack()`), build
 a new GraphedForward.
@@ -58,10 +60,6 @@ class GraphedForward:
         self._graphs.clear()
         for s in self._streams.values():
             ops.drop_stream_caches(s.cuda_stream)
-            for b in self._backbones:
-                bufs = b.__dict__.get("_raw_bufs", {})
-                for k in [k for k in bufs if k[1] == s.cuda_stream]:
-                    del bufs[k]
         self._streams.clear()
 
     def __del__(self):

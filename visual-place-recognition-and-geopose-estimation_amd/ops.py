@@ -13,8 +13,7 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import _lib
-
-_WORKSPACES = {}
+from ._cache import Cache, tensor_key
 
 
 def _raw_stream(device_index: int = -1) -> int:
@@ -50,34 +49,61 @@ def capturing() -> bool:
     return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
 
 
-_GRAPH_PINNED: list = []       # buffers a captured graph addresses, kept alive when their cache entry is replaced
+def cache(capacity: Optional[int] = None) -> Cache:
+    """A _cache.Cache that asks this module's capturing() (looked up per call: a test can substitute it)."""
+    return Cache(_capturing, capacity)
+
+
+def _capturing() -> bool:
+    return capturing()
+
+
+def _call(name: str, *args) -> None:
+    """Call the entry point `name` of the library and raise, under that same name, on a non-zero status."""
+    st = getattr(_lib.lib(), name)(*args)
+    if st:
+        _lib.check(st, name)
+
+
+# Caches keyed (device index, raw stream handle, ...): two streams driving the library concurrently (e.g. two batches in
+# flight) never share scratch memory, and drop_stream_caches() forgets a stream that is gone.
+_WORKSPACES = cache()
+_ZERO_ROWS = cache(8)
+_STREAM_KEYED = (_WORKSPACES, _ZERO_ROWS)
+
+
+def _alloc_bytes(nbytes: int, device: torch.device, zero: bool) -> torch.Tensor:
+    return (torch.zeros if zero else torch.empty)(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+
+
+def _alloc_zero_rows(M: int, C: int, device: torch.device) -> torch.Tensor:
+    return torch.zeros((M, C), dtype=torch.bfloat16, device=device)
 
 
 def workspace(name: str, nbytes: int, device: torch.device, stream_key: Optional[int] = None, zero: bool = False) -> torch.Tensor:
-    """Cached byte buffer per (device, stream, name); grows, never shrinks.  Keyed by the current stream so that
-    two streams driving the library concurrently (e.g. two batches in flight) never share scratch memory.  A buffer
-    handed out during graph capture is never freed (a later, larger request gets a new one; the old stays pinned).
+    """Cached byte buffer per (device, stream, name); grows, never shrinks.  One entry of the package's graph-safe cache
+    (_cache.Cache): a buffer handed out during graph capture is never freed (a later, larger request gets a new one; the
+    old one stays allocated beside it) until drop_stream_caches() forgets its stream.
     stream_key: raw handle of the stream that OWNS the buffer when the caller is working for it from a helper stream.
     zero: a new buffer is zero-filled (kernels with arrival counters at the head of their workspace need zeros on first use
     and leave zeros behind: vpr_pose_head_fused)."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
     key = (idx, _raw_stream(idx) if stream_key is None else stream_key, name)
-    ent = _WORKSPACES.get(key)
-    if ent is None or ent[0].numel() < nbytes:
-        if ent is not None and ent[1]:
-            _GRAPH_PINNED.append(ent[0])
-        alloc = torch.zeros if zero else torch.empty
-        ent = _WORKSPACES[key] = [alloc(max(int(nbytes), 256), dtype=torch.uint8, device=device), False]
-    if not ent[1] and capturing():
-        ent[1] = True
-    return ent[0]
+    return _WORKSPACES.get(key, _alloc_bytes, (nbytes, device, zero), need=nbytes)
+
+
+def zero_rows_bf16(M: int, C: int, device: torch.device) -> torch.Tensor:
+    """Cached [M, C] bf16 matrix per (device, current stream, shape), zero when created: the backbone's raw-token buffer,
+    whose cls rows nothing ever writes."""
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    return _ZERO_ROWS.get((idx, _raw_stream(idx), M, C), _alloc_zero_rows, (M, C, device))
 
 
 def drop_stream_caches(raw_stream: int) -> None:
-    """Forget every workspace keyed by this stream handle (graphed.GraphedForward.close(): its private stream is gone,
-    and so are the graphs that addressed the buffers)."""
-    for key in [k for k in _WORKSPACES if k[1] == raw_stream]:
-        del _WORKSPACES[key]
+    """Forget every stream-keyed entry (workspaces, raw-token buffers) of this stream handle, pinned ones included
+    (graphed.GraphedForward.close(): its private stream is gone, and so are the graphs that addressed the buffers)."""
+    for c in _STREAM_KEYED:
+        c.drop(lambda k: k[1] == raw_stream)
 
 
 # ------------------------------------------------------------------------------------------ SALAD
@@ -99,14 +125,14 @@ class SaladWeights:
     b2_t: torch.Tensor
     dustbin: float = 1.0
 
+    matrix_dtype = torch.bfloat16       # class-level (no annotation: not a field)
+    _workspace = ("salad", "vpr_salad_workspace_bytes", True)      # workspace name, its size query, zero-filled when new
+
     def validate(self) -> Tuple[int, int, int, int, int]:
         for n in ("w1_sc", "w2_s", "w2_c", "w1_t", "w2_t"):
-            _need(getattr(self, n), torch.bfloat16, n, 2)
+            _need(getattr(self, n), self.matrix_dtype, n, 2)
         for n in ("b1_sc", "b2_s", "b2_c", "b1_t", "b2_t"):
             _need(getattr(self, n), torch.float32, n, 1)
-        return self._shapes()
-
-    def _shapes(self) -> Tuple[int, int, int, int, int]:
         hidden2, C = self.w1_sc.shape
         hidden = hidden2 // 2
         m, l, t = self.w2_s.shape[0], self.w2_c.shape[0], self.w2_t.shape[0]
@@ -124,14 +150,19 @@ class SaladWeights:
         return _lib.SaladWeightsC(*ptrs, fs.data_ptr() if fs is not None else None, fc.data_ptr() if fc is not None else None)
 
 
-_SALAD_FRAGS: dict = {}
+_SALAD_FRAGS = cache(16)
 salad_use_fragments = True      # False: hand the C ABI null *_frag pointers (the kernel then reads W2 row-major; tests / A/B)
+
+
+def _pack_w2_fragments(src: torch.Tensor) -> torch.Tensor:
+    frag = torch.empty_like(src)
+    _call("vpr_salad_pack_w2_fragments", _ptr(src), src.shape[0], src.shape[1], _ptr(frag), _stream())
+    return frag
 
 
 def _salad_w2_fragments(w: "SaladWeights"):
     """(w2_s, w2_c) in MFMA fragment order (vpr_salad_pack_w2_fragments), packed once per (storage, version) like the pose
-    head's planes: entries keep their source tensors alive (no recycled-address hits) and are pinned once a HIP graph
-    has been captured on them."""
+    head's planes."""
     out = []
     if not salad_use_fragments:
         return None, None
@@ -140,41 +171,58 @@ def _salad_w2_fragments(w: "SaladWeights"):
         if src.dtype != torch.bfloat16 or not src.is_cuda or n_out % 16 or hidden % 256:
             out.append(None)
             continue
-        key = (src.data_ptr(), src._version, n_out, hidden, str(src.device))
-        hit = _SALAD_FRAGS.get(key)
-        if hit is None:
-            while len(_SALAD_FRAGS) >= 16:
-                old = _SALAD_FRAGS.pop(next(iter(_SALAD_FRAGS)))
-                if old[2]:
-                    _GRAPH_PINNED.append(old)
-            frag = torch.empty_like(src)
-            st = _lib.lib().vpr_salad_pack_w2_fragments(_ptr(src), n_out, hidden, _ptr(frag), _stream())
-            _lib.check(st, "vpr_salad_pack_w2_fragments")
-            hit = _SALAD_FRAGS[key] = [frag, src, False]
-        if not hit[2] and capturing():
-            hit[2] = True
-        out.append(hit[0])
+        out.append(_SALAD_FRAGS.get(tensor_key(src), _pack_w2_fragments, (src,), (src,)))
     return out[0], out[1]
+
+
+def _tokens(tokens, dtype: torch.dtype, what: str):
+    """[B, 1+n, C] (cls first) or a (patch [B,n,C], cls [B,C]) pair, of `dtype` -> (patch pointer, patch image stride, cls
+    pointer, cls stride, B, n, C, device); strides in elements."""
+    if isinstance(tokens, torch.Tensor):
+        _need(tokens, dtype, "tokens", 3)
+        B, tpi, C = tokens.shape
+        p = tokens.data_ptr()
+        return ctypes.c_void_p(p + tokens.element_size() * C), tpi * C, ctypes.c_void_p(p), tpi * C, B, tpi - 1, C, tokens.device
+    patch, cls = tokens
+    _need(patch, dtype, "patch", 3)
+    _need(cls, dtype, "cls", 2)
+    B, n, C = patch.shape
+    if tuple(cls.shape) != (B, C):
+        raise RuntimeError(f"{what}: cls must be [B, C] = {(B, C)}, got {tuple(cls.shape)}")
+    return _ptr(patch), n * C, _ptr(cls), C, B, n, C, patch.device
+
+
+def _salad_setup(w: SaladWeights, B: int, n: int, device: torch.device, Ct: Optional[int] = None, want_bf16: Optional[bool] = None,
+                 out: Optional[torch.Tensor] = None, owner_raw_stream: Optional[int] = None):
+    """What every aggregation entry needs: validated weights (with Ct given, checked against the token width), the
+    workspace (of stream `owner_raw_stream`, default the current one) and, unless want_bf16 is None, the outputs.
+    -> ((C, hidden, m, l, t), workspace, descriptor f32 [B, t+l*m] (`out` if given), bf16 copy or None)."""
+    C, hidden, m, l, t = dims = w.validate()
+    if Ct is not None and Ct != C:
+        raise RuntimeError(f"tokens have C={Ct}, weights expect {C}")
+    name, size_query, zero = w._workspace
+    ws = workspace(name, getattr(_lib.lib(), size_query)(B, n, C, m, l, t, hidden), device, owner_raw_stream, zero)
+    if want_bf16 is None:
+        return dims, ws, None, None
+    if out is None:
+        out = torch.empty((B, t + l * m), dtype=torch.float32, device=device)
+    else:
+        _need(out, torch.float32, "out", 2)
+        if tuple(out.shape) != (B, t + l * m):
+            raise RuntimeError(f"out must be [B, t+l*m] = {(B, t + l * m)}, got {tuple(out.shape)}")
+    out16 = torch.empty((B, t + l * m), dtype=torch.bfloat16, device=device) if want_bf16 else None
+    return dims, ws, out, out16
 
 
 def salad_aggregate(tokens: torch.Tensor, w: SaladWeights, sinkhorn_iters: int = 3,
                     want_bf16: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """tokens [B, 1+n, C] bf16 (cls first) -> (descriptor f32 [B, t+l*m], bf16 copy or None)."""
     _need(tokens, torch.bfloat16, "tokens", 3)
-    C, hidden, m, l, t = w.validate()
     B, tpi, Ct = tokens.shape
-    if Ct != C:
-        raise RuntimeError(f"tokens have C={Ct}, weights expect {C}")
-    n = tpi - 1
-    L = _lib.lib()
-    nbytes = L.vpr_salad_workspace_bytes(B, n, C, m, l, t, hidden)
-    ws = workspace("salad", nbytes, tokens.device, zero=True)
-    out = torch.empty((B, t + l * m), dtype=torch.float32, device=tokens.device)
-    out16 = torch.empty((B, t + l * m), dtype=torch.bfloat16, device=tokens.device) if want_bf16 else None
+    (C, hidden, m, l, t), ws, out, out16 = _salad_setup(w, B, tpi - 1, tokens.device, Ct, want_bf16)
     cw = w.c_struct()
-    st = L.vpr_salad_aggregate(_ptr(tokens), B, tpi, C, ctypes.byref(cw), float(w.dustbin), m, l, t, hidden,
-                               int(sinkhorn_iters), _ptr(out), _ptr(out16), _ptr(ws), ws.numel(), _stream())
-    _lib.check(st, "vpr_salad_aggregate")
+    _call("vpr_salad_aggregate", _ptr(tokens), B, tpi, C, ctypes.byref(cw), float(w.dustbin), m, l, t, hidden,
+          int(sinkhorn_iters), _ptr(out), _ptr(out16), _ptr(ws), ws.numel(), _stream())
     return out, out16
 
 
@@ -195,15 +243,12 @@ def salad_stage_token(cls: torch.Tensor, w: SaladWeights, n: int, owner_raw_stre
     salad_aggregate_split(..., token_done=True) for the same batch, ordered after this call by the caller).  The DINOv2
     backbone calls it from its cls-row side stream, where the cls tokens are final ~0.3 ms before the patch tokens."""
     _need(cls, torch.bfloat16, "cls", 2)
-    C, hidden, m, l, t = w.validate()
     B, Ct = cls.shape
+    (C, hidden, m, l, t), ws, _, _ = _salad_setup(w, B, n, cls.device, owner_raw_stream=owner_raw_stream)
     if Ct != C:
         raise RuntimeError(f"cls {tuple(cls.shape)} does not match weights with C={C}")
-    L = _lib.lib()
-    ws = workspace("salad", L.vpr_salad_workspace_bytes(B, n, C, m, l, t, hidden), cls.device, stream_key=owner_raw_stream, zero=True)
     cw = w.c_struct()
-    st = L.vpr_salad_stage_token(_ptr(cls), C, B, n, C, ctypes.byref(cw), m, l, t, hidden, _ptr(ws), ws.numel(), _stream())
-    _lib.check(st, "vpr_salad_stage_token")
+    _call("vpr_salad_stage_token", _ptr(cls), C, B, n, C, ctypes.byref(cw), m, l, t, hidden, _ptr(ws), ws.numel(), _stream())
 
 
 def salad_aggregate_split(patch: torch.Tensor, cls: torch.Tensor, w: SaladWeights, sinkhorn_iters: int = 3,
@@ -217,62 +262,35 @@ def salad_aggregate_split(patch: torch.Tensor, cls: torch.Tensor, w: SaladWeight
     the pipeline hides the token MLP for free by running it on the backbone's cls-row stream (salad_stage_token)."""
     _need(patch, torch.bfloat16, "patch", 3)
     _need(cls, torch.bfloat16, "cls", 2)
-    C, hidden, m, l, t = w.validate()
     B, n, Ct = patch.shape
+    (C, hidden, m, l, t), ws, out, out16 = _salad_setup(w, B, n, patch.device, want_bf16=want_bf16)
     if Ct != C or tuple(cls.shape) != (B, C):
         raise RuntimeError(f"patch {tuple(patch.shape)} / cls {tuple(cls.shape)} do not match weights with C={C}")
-    L = _lib.lib()
-    ws = workspace("salad", L.vpr_salad_workspace_bytes(B, n, C, m, l, t, hidden), patch.device, zero=True)
-    out = torch.empty((B, t + l * m), dtype=torch.float32, device=patch.device)
-    out16 = torch.empty((B, t + l * m), dtype=torch.bfloat16, device=patch.device) if want_bf16 else None
     cw = w.c_struct()
+    mlps = (_ptr(patch), n * C, B, n, C, ctypes.byref(cw), m, l, t, hidden, _ptr(ws), ws.numel())
+    aggregate = (B, n, C, float(w.dustbin), m, l, t, hidden, int(sinkhorn_iters), _ptr(out), _ptr(out16), _ptr(ws), ws.numel())
     if token_done:
         raw = _stream()
-        st = L.vpr_salad_stage_mlps(_ptr(patch), n * C, B, n, C, ctypes.byref(cw), m, l, t, hidden, _ptr(ws), ws.numel(), raw)
-        _lib.check(st, "vpr_salad_stage_mlps")
-        st = L.vpr_salad_stage_aggregate(B, n, C, float(w.dustbin), m, l, t, hidden, int(sinkhorn_iters), _ptr(out), _ptr(out16),
-                                         _ptr(ws), ws.numel(), raw)
-        _lib.check(st, "vpr_salad_stage_aggregate")
+        _call("vpr_salad_stage_mlps", *mlps, raw)
+        _call("vpr_salad_stage_aggregate", *aggregate, raw)
         return out, out16
     if overlap is None:
         overlap = False     # measured (scripts/salad_ab.py): the fork + join of a side stream costs more than the 10 us it hides
     if not overlap:
-        st = L.vpr_salad_aggregate_split(_ptr(patch), _ptr(cls), B, n, C, ctypes.byref(cw), float(w.dustbin), m, l, t,
-                                         hidden, int(sinkhorn_iters), _ptr(out), _ptr(out16), _ptr(ws), ws.numel(), _stream())
-        _lib.check(st, "vpr_salad_aggregate_split")
+        _call("vpr_salad_aggregate_split", _ptr(patch), _ptr(cls), B, n, C, ctypes.byref(cw), float(w.dustbin), m, l, t,
+              hidden, int(sinkhorn_iters), _ptr(out), _ptr(out16), _ptr(ws), ws.numel(), _stream())
         return out, out16
     dev_idx = patch.device.index if patch.device.index is not None else torch.cuda.current_device()
-    main_raw = _raw_stream(dev_idx)
+    main_raw = ctypes.c_void_p(_raw_stream(dev_idx))
     main = torch.cuda.current_stream(patch.device)
-    side = _salad_side_stream(patch.device, main_raw)
+    side = _salad_side_stream(patch.device, main_raw.value)
     side.wait_stream(main)                                   # cls (and the workspace's previous consumer) are ready
-    st = L.vpr_salad_stage_token(_ptr(cls), C, B, n, C, ctypes.byref(cw), m, l, t, hidden, _ptr(ws), ws.numel(),
-                                 ctypes.c_void_p(side.cuda_stream))
-    _lib.check(st, "vpr_salad_stage_token")
-    st = L.vpr_salad_stage_mlps(_ptr(patch), n * C, B, n, C, ctypes.byref(cw), m, l, t, hidden, _ptr(ws), ws.numel(),
-                                ctypes.c_void_p(main_raw))
-    _lib.check(st, "vpr_salad_stage_mlps")
+    _call("vpr_salad_stage_token", _ptr(cls), C, B, n, C, ctypes.byref(cw), m, l, t, hidden, _ptr(ws), ws.numel(),
+          ctypes.c_void_p(side.cuda_stream))
+    _call("vpr_salad_stage_mlps", *mlps, main_raw)
     main.wait_stream(side)
-    st = L.vpr_salad_stage_aggregate(B, n, C, float(w.dustbin), m, l, t, hidden, int(sinkhorn_iters), _ptr(out), _ptr(out16),
-                                     _ptr(ws), ws.numel(), ctypes.c_void_p(main_raw))
-    _lib.check(st, "vpr_salad_stage_aggregate")
+    _call("vpr_salad_stage_aggregate", *aggregate, main_raw)
     return out, out16
-
-
-def _bf16_tokens(tokens, what: str):
-    """[B, 1+n, C] bf16 (cls first) or a (patch [B,n,C], cls [B,C]) bf16 pair -> (patch ptr, patch image stride, cls ptr,
-    cls stride, B, n, C, device); strides in elements."""
-    if isinstance(tokens, torch.Tensor):
-        _need(tokens, torch.bfloat16, "tokens", 3)
-        B, tpi, C = tokens.shape
-        return tokens.data_ptr() + 2 * C, tpi * C, tokens.data_ptr(), tpi * C, B, tpi - 1, C, tokens.device
-    patch, cls = tokens
-    _need(patch, torch.bfloat16, "patch", 3)
-    _need(cls, torch.bfloat16, "cls", 2)
-    B, n, C = patch.shape
-    if tuple(cls.shape) != (B, C):
-        raise RuntimeError(f"{what}: cls must be [B, C] = {(B, C)}, got {tuple(cls.shape)}")
-    return patch.data_ptr(), n * C, cls.data_ptr(), C, B, n, C, patch.device
 
 
 def salad_aggregate_train(tokens, w: SaladWeights, dropout_p: float, seed: int, pass_index: int, image_base: int = 0,
@@ -285,10 +303,8 @@ def salad_aggregate_train(tokens, w: SaladWeights, dropout_p: float, seed: int, 
     mask_out (uint8 [B*n, 2*hidden], optional) receives the mask, 1 = kept.  dropout_p = 0 gives the bits of
     salad_aggregate_split.  out (f32 [B, t+l*m], contiguous, optional): where the descriptor goes (e.g. rows of a
     fine-tuning buffer).  -> (descriptor f32 [B, t+l*m], bf16 copy or None)."""
-    patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, Ct, device = _bf16_tokens(tokens, "salad_aggregate_train")
-    C, hidden, m, l, t = w.validate()
-    if Ct != C:
-        raise RuntimeError(f"tokens have C={Ct}, weights expect {C}")
+    patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, Ct, device = _tokens(tokens, torch.bfloat16, "salad_aggregate_train")
+    (C, hidden, m, l, t), ws, out, out16 = _salad_setup(w, B, n, device, Ct, want_bf16, out)
     if not 0 <= int(seed) < 1 << 64:
         raise ValueError(f"salad_aggregate_train: seed must be an unsigned 64-bit integer, got {seed!r}")
     if not 0 <= int(pass_index) < 1 << 32:
@@ -297,34 +313,19 @@ def salad_aggregate_train(tokens, w: SaladWeights, dropout_p: float, seed: int, 
         _need(mask_out, torch.uint8, "mask_out", 2)
         if tuple(mask_out.shape) != (B * n, 2 * hidden):
             raise RuntimeError(f"mask_out must be [B*n, 2*hidden] = {(B * n, 2 * hidden)}, got {tuple(mask_out.shape)}")
-    L = _lib.lib()
-    ws = workspace("salad", L.vpr_salad_workspace_bytes(B, n, C, m, l, t, hidden), device, zero=True)
-    if out is None:
-        out = torch.empty((B, t + l * m), dtype=torch.float32, device=device)
-    else:
-        _need(out, torch.float32, "out", 2)
-        if tuple(out.shape) != (B, t + l * m):
-            raise RuntimeError(f"out must be [B, t+l*m] = {(B, t + l * m)}, got {tuple(out.shape)}")
-    out16 = torch.empty((B, t + l * m), dtype=torch.bfloat16, device=device) if want_bf16 else None
     cw = w.c_struct()
-    st = L.vpr_salad_aggregate_train(ctypes.c_void_p(patch_ptr), patch_stride, ctypes.c_void_p(cls_ptr), cls_stride, B, n, C,
-                                     ctypes.byref(cw), float(w.dustbin), m, l, t, hidden, int(sinkhorn_iters),
-                                     float(dropout_p), int(seed), int(pass_index), int(image_base), _ptr(out), _ptr(out16),
-                                     _ptr(mask_out), _ptr(ws), ws.numel(), _stream())
-    _lib.check(st, "vpr_salad_aggregate_train")
+    _call("vpr_salad_aggregate_train", patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, C,
+          ctypes.byref(cw), float(w.dustbin), m, l, t, hidden, int(sinkhorn_iters),
+          float(dropout_p), int(seed), int(pass_index), int(image_base), _ptr(out), _ptr(out16),
+          _ptr(mask_out), _ptr(ws), ws.numel(), _stream())
     return out, out16
 
 
 @dataclass
 class SaladWeightsF32(SaladWeights):
     """The same ten tensors, all f32 (vpr_salad_weights_f32): operands of the f32-accurate aggregation."""
-
-    def validate(self) -> Tuple[int, int, int, int, int]:
-        for n in ("w1_sc", "w2_s", "w2_c", "w1_t", "w2_t"):
-            _need(getattr(self, n), torch.float32, n, 2)
-        for n in ("b1_sc", "b2_s", "b2_c", "b1_t", "b2_t"):
-            _need(getattr(self, n), torch.float32, n, 1)
-        return self._shapes()
+    matrix_dtype = torch.float32
+    _workspace = ("salad_f32", "vpr_salad_f32_workspace_bytes", False)
 
     def c_struct(self) -> _lib.SaladWeightsF32C:
         return _lib.SaladWeightsF32C(*[getattr(self, n).data_ptr() for n, _ in _lib.SaladWeightsF32C._fields_])
@@ -334,34 +335,12 @@ def salad_aggregate_f32(tokens, w: SaladWeightsF32, sinkhorn_iters: int = 3,
                         want_bf16: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """The aggregation at the reference's precision: `tokens` = [B, 1+n, C] f32 (cls first) or a (patch [B,n,C], cls [B,C])
     pair of f32 tensors, f32 weights -> (descriptor f32 [B, t+l*m], bf16 copy or None).  vpr_salad_aggregate_f32."""
-    if isinstance(tokens, torch.Tensor):
-        _need(tokens, torch.float32, "tokens", 3)
-        B, tpi, Ct = tokens.shape
-        n = tpi - 1
-        patch_ptr, patch_stride = tokens.data_ptr() + 4 * Ct, tpi * Ct
-        cls_ptr, cls_stride = tokens.data_ptr(), tpi * Ct
-        device = tokens.device
-    else:
-        patch, cls = tokens
-        _need(patch, torch.float32, "patch", 3)
-        _need(cls, torch.float32, "cls", 2)
-        B, n, Ct = patch.shape
-        if tuple(cls.shape) != (B, Ct):
-            raise RuntimeError("salad_aggregate_f32: cls must be [B, C]")
-        patch_ptr, patch_stride, cls_ptr, cls_stride = patch.data_ptr(), n * Ct, cls.data_ptr(), Ct
-        device = patch.device
-    C, hidden, m, l, t = w.validate()
-    if Ct != C:
-        raise RuntimeError(f"tokens have C={Ct}, weights expect {C}")
-    L = _lib.lib()
-    ws = workspace("salad_f32", L.vpr_salad_f32_workspace_bytes(B, n, C, m, l, t, hidden), device)
-    out = torch.empty((B, t + l * m), dtype=torch.float32, device=device)
-    out16 = torch.empty((B, t + l * m), dtype=torch.bfloat16, device=device) if want_bf16 else None
+    patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, Ct, device = _tokens(tokens, torch.float32, "salad_aggregate_f32")
+    (C, hidden, m, l, t), ws, out, out16 = _salad_setup(w, B, n, device, Ct, want_bf16)
     cw = w.c_struct()
-    st = L.vpr_salad_aggregate_f32(ctypes.c_void_p(patch_ptr), patch_stride, ctypes.c_void_p(cls_ptr), cls_stride, B, n, C,
-                                   ctypes.byref(cw), float(w.dustbin), m, l, t, hidden, int(sinkhorn_iters),
-                                   _ptr(out), _ptr(out16), _ptr(ws), ws.numel(), _stream())
-    _lib.check(st, "vpr_salad_aggregate_f32")
+    _call("vpr_salad_aggregate_f32", patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, C,
+          ctypes.byref(cw), float(w.dustbin), m, l, t, hidden, int(sinkhorn_iters),
+          _ptr(out), _ptr(out16), _ptr(ws), ws.numel(), _stream())
     return out, out16
 
 
@@ -378,10 +357,8 @@ def salad_sinkhorn_aggregate(scores: torch.Tensor, feats: torch.Tensor, tokfeat:
         raise RuntimeError("salad_sinkhorn_aggregate: inconsistent shapes")
     out = torch.empty((B, t + l * m), dtype=torch.float32, device=scores.device)
     out16 = torch.empty_like(out, dtype=torch.bfloat16) if want_bf16 else None
-    st = _lib.lib().vpr_salad_sinkhorn_aggregate(_ptr(scores), _ptr(feats), _ptr(tokfeat), B, n, m, l, t,
-                                                 float(dustbin), int(sinkhorn_iters), _ptr(out), _ptr(out16),
-                                                 _stream())
-    _lib.check(st, "vpr_salad_sinkhorn_aggregate")
+    _call("vpr_salad_sinkhorn_aggregate", _ptr(scores), _ptr(feats), _ptr(tokfeat), B, n, m, l, t,
+          float(dustbin), int(sinkhorn_iters), _ptr(out), _ptr(out16), _stream())
     return out, out16
 
 
@@ -442,9 +419,7 @@ def gemm_nt_bf16(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] 
     a_group_rows > 0, row r of A lives at a + (r // a_group_rows) * a_group_stride + (r % a_group_rows) * a.stride(0)
     (elements) and m gives the row count M (default a.shape[0])."""
     fields, out = _gemm_fields(a, w, bias, relu, out_dtype, out, a_group_rows, a_group_stride, m)
-    fn = _lib.lib().vpr_gemm256_nt_bf16 if tile256 else _lib.lib().vpr_gemm_nt_bf16
-    st = fn(*fields, _stream())
-    _lib.check(st, "vpr_gemm256_nt_bf16" if tile256 else "vpr_gemm_nt_bf16")
+    _call("vpr_gemm256_nt_bf16" if tile256 else "vpr_gemm_nt_bf16", *fields, _stream())
     return out
 
 
@@ -460,8 +435,7 @@ def gemm_nt_group_bf16(problems) -> list:
                                    p.get("out"), p.get("a_group_rows", 0), p.get("a_group_stride", 0), p.get("m"))
         arr[i] = _lib.GemmProblemC(*[f.value if isinstance(f, ctypes.c_void_p) else f for f in fields])
         outs.append(out)
-    st = _lib.lib().vpr_gemm_nt_group_bf16(arr, len(problems), _stream())
-    _lib.check(st, "vpr_gemm_nt_group_bf16")
+    _call("vpr_gemm_nt_group_bf16", arr, len(problems), _stream())
     return outs
 
 
@@ -499,10 +473,17 @@ def knn_topk(q: torch.Tensor, gallery: torch.Tensor, k: int, index_base: int = 0
     back (one sync) and re-runs the flagged queries exhaustively, so the result is exact unconditionally."""
     _need(q, torch.bfloat16, "q", 2)
     _need(gallery, torch.bfloat16, "gallery", 2)
+    if gallery.shape[1] != q.shape[1]:
+        raise RuntimeError("knn_topk: q and gallery disagree on D")
+    return _knn_topk(q, None, gallery, None, k, index_base, ws, norm_bound, status, uncertified, exact_fallback, score_events)
+
+
+def _knn_topk(q, q_scale, gallery, gallery_scale, k, index_base, ws, norm_bound, status, uncertified, exact_fallback,
+              score_events) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The body of knn_topk (scales None: vpr_knn_topk_checked) and knn_topk_fp8 (vpr_knn_topk_fp8_checked) on checked
+    operands."""
     B, D = q.shape
     N = gallery.shape[0]
-    if gallery.shape[1] != D:
-        raise RuntimeError("knn_topk: q and gallery disagree on D")
     if ws is None:
         ws = knn_workspace(B, N, D, k, q.device)
     if exact_fallback and status is None:
@@ -511,14 +492,17 @@ def knn_topk(q: torch.Tensor, gallery: torch.Tensor, k: int, index_base: int = 0
     vals = torch.empty((B, k), dtype=torch.float32, device=q.device)
     idx = torch.empty((B, k), dtype=torch.int32, device=q.device)
     if score_events is not None:
-        _topk_two_stage(q, None, gallery, None, B, N, D, k, index_base, vals, idx, ws, norm_bound, status, uncertified,
-                        score_events)
+        _topk_two_stage(q, q_scale, gallery, gallery_scale, B, N, D, k, index_base, vals, idx, ws, norm_bound, status,
+                        uncertified, score_events)
     else:
-        st = _lib.lib().vpr_knn_topk_checked(_ptr(q), _ptr(gallery), B, N, D, int(k), int(index_base), _ptr(vals), _ptr(idx),
-                                             _ptr(ws), ws.numel(), float(norm_bound), _ptr(status), _ptr(uncertified), _stream())
-        _lib.check(st, "vpr_knn_topk_checked")
+        if q_scale is None:
+            name, operands = "vpr_knn_topk_checked", (_ptr(q), _ptr(gallery))
+        else:
+            name, operands = "vpr_knn_topk_fp8_checked", (_ptr(q), _ptr(q_scale), _ptr(gallery), _ptr(gallery_scale))
+        _call(name, *operands, B, N, D, int(k), int(index_base), _ptr(vals), _ptr(idx), _ptr(ws), ws.numel(),
+              float(norm_bound), _ptr(status), _ptr(uncertified), _stream())
     if exact_fallback:
-        _exhaustive_fixup(q, None, gallery, None, k, index_base, status, vals, idx)
+        _exhaustive_fixup(q, q_scale, gallery, gallery_scale, k, index_base, status, vals, idx)
     return vals, idx
 
 
@@ -529,13 +513,11 @@ def _topk_two_stage(q, q_scale, gallery, gallery_scale, B, N, D, k, index_base, 
             B, N, D, int(k))
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    st = _lib.lib().vpr_knn_topk_scores_stage(*args, _ptr(ws), ws.numel(), _stream())
+    _call("vpr_knn_topk_scores_stage", *args, _ptr(ws), ws.numel(), _stream())
     e1.record()
-    _lib.check(st, "vpr_knn_topk_scores_stage")
     score_events.append((e0, e1))
-    st = _lib.lib().vpr_knn_topk_select_stage(*args, int(index_base), _ptr(vals), _ptr(idx), _ptr(ws), ws.numel(),
-                                              float(norm_bound), _ptr(status), _ptr(uncertified), _stream())
-    _lib.check(st, "vpr_knn_topk_select_stage")
+    _call("vpr_knn_topk_select_stage", *args, int(index_base), _ptr(vals), _ptr(idx), _ptr(ws), ws.numel(),
+          float(norm_bound), _ptr(status), _ptr(uncertified), _stream())
 
 
 def knn_topk_exhaustive(q: torch.Tensor, gallery: torch.Tensor, k: int, index_base: int = 0,
@@ -557,10 +539,9 @@ def knn_topk_exhaustive(q: torch.Tensor, gallery: torch.Tensor, k: int, index_ba
         ws = knn_workspace(B, N, D, k, q.device)
     vals = torch.empty((B, k), dtype=torch.float32, device=q.device)
     idx = torch.empty((B, k), dtype=torch.int32, device=q.device)
-    st = _lib.lib().vpr_knn_topk_exhaustive(_ptr(q), _ptr(q_scale) if fp8 else None, _ptr(gallery),
-                                            _ptr(gallery_scale) if fp8 else None, int(fp8), B, N, D, int(k),
-                                            int(index_base), _ptr(vals), _ptr(idx), _ptr(ws), ws.numel(), _stream())
-    _lib.check(st, "vpr_knn_topk_exhaustive")
+    _call("vpr_knn_topk_exhaustive", _ptr(q), _ptr(q_scale) if fp8 else None, _ptr(gallery),
+          _ptr(gallery_scale) if fp8 else None, int(fp8), B, N, D, int(k),
+          int(index_base), _ptr(vals), _ptr(idx), _ptr(ws), ws.numel(), _stream())
     return vals, idx
 
 
@@ -583,8 +564,7 @@ def quantize_fp8_rows(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     rows, D = x.shape
     q = torch.empty((rows, D), dtype=torch.uint8, device=x.device)
     scale = torch.empty((rows,), dtype=torch.float32, device=x.device)
-    st = _lib.lib().vpr_quantize_fp8_rows(_ptr(x), rows, D, _ptr(q), _ptr(scale), _stream())
-    _lib.check(st, "vpr_quantize_fp8_rows")
+    _call("vpr_quantize_fp8_rows", _ptr(x), rows, D, _ptr(q), _ptr(scale), _stream())
     return q, scale
 
 
@@ -598,28 +578,10 @@ def knn_topk_fp8(q: torch.Tensor, q_scale: torch.Tensor, gallery: torch.Tensor, 
     _need(gallery, torch.uint8, "gallery", 2)
     _need(q_scale, torch.float32, "q_scale", 1)
     _need(gallery_scale, torch.float32, "gallery_scale", 1)
-    B, D = q.shape
-    N = gallery.shape[0]
-    if gallery.shape[1] != D or q_scale.numel() != B or gallery_scale.numel() != N:
+    if gallery.shape[1] != q.shape[1] or q_scale.numel() != q.shape[0] or gallery_scale.numel() != gallery.shape[0]:
         raise RuntimeError("knn_topk_fp8: inconsistent shapes")
-    if ws is None:
-        ws = knn_workspace(B, N, D, k, q.device)
-    if exact_fallback and status is None:
-        status = torch.empty((B,), dtype=torch.int32, device=q.device)
-    _check_args(B, q.device, status, uncertified)
-    vals = torch.empty((B, k), dtype=torch.float32, device=q.device)
-    idx = torch.empty((B, k), dtype=torch.int32, device=q.device)
-    if score_events is not None:
-        _topk_two_stage(q, q_scale, gallery, gallery_scale, B, N, D, k, index_base, vals, idx, ws, norm_bound, status,
-                        uncertified, score_events)
-    else:
-        st = _lib.lib().vpr_knn_topk_fp8_checked(_ptr(q), _ptr(q_scale), _ptr(gallery), _ptr(gallery_scale), B, N, D, int(k),
-                                                 int(index_base), _ptr(vals), _ptr(idx), _ptr(ws), ws.numel(),
-                                                 float(norm_bound), _ptr(status), _ptr(uncertified), _stream())
-        _lib.check(st, "vpr_knn_topk_fp8_checked")
-    if exact_fallback:
-        _exhaustive_fixup(q, q_scale, gallery, gallery_scale, k, index_base, status, vals, idx)
-    return vals, idx
+    return _knn_topk(q, q_scale, gallery, gallery_scale, k, index_base, ws, norm_bound, status, uncertified, exact_fallback,
+                     score_events)
 
 
 def knn_scores(q: torch.Tensor, gallery: torch.Tensor, ws: torch.Tensor) -> None:
@@ -627,8 +589,7 @@ def knn_scores(q: torch.Tensor, gallery: torch.Tensor, ws: torch.Tensor) -> None
     _need(q, torch.bfloat16, "q", 2)
     _need(gallery, torch.bfloat16, "gallery", 2)
     B, D = q.shape
-    st = _lib.lib().vpr_knn_scores(_ptr(q), _ptr(gallery), B, gallery.shape[0], D, _ptr(ws), ws.numel(), _stream())
-    _lib.check(st, "vpr_knn_scores")
+    _call("vpr_knn_scores", _ptr(q), _ptr(gallery), B, gallery.shape[0], D, _ptr(ws), ws.numel(), _stream())
 
 
 def knn_select(q: torch.Tensor, gallery: torch.Tensor, k: int, ws: torch.Tensor,
@@ -639,10 +600,8 @@ def knn_select(q: torch.Tensor, gallery: torch.Tensor, k: int, ws: torch.Tensor,
     _check_args(B, q.device, status, uncertified)
     vals = torch.empty((B, k), dtype=torch.float32, device=q.device)
     idx = torch.empty((B, k), dtype=torch.int32, device=q.device)
-    st = _lib.lib().vpr_knn_select_checked(_ptr(q), _ptr(gallery), B, gallery.shape[0], D, int(k), int(index_base),
-                                           _ptr(vals), _ptr(idx), _ptr(ws), ws.numel(), float(norm_bound),
-                                           _ptr(status), _ptr(uncertified), _stream())
-    _lib.check(st, "vpr_knn_select_checked")
+    _call("vpr_knn_select_checked", _ptr(q), _ptr(gallery), B, gallery.shape[0], D, int(k), int(index_base),
+          _ptr(vals), _ptr(idx), _ptr(ws), ws.numel(), float(norm_bound), _ptr(status), _ptr(uncertified), _stream())
     return vals, idx
 
 
@@ -666,13 +625,22 @@ def topk_merge(vals: torch.Tensor, idxs: torch.Tensor) -> Tuple[torch.Tensor, to
     R, B, k = vals.shape
     ov = torch.empty((B, k), dtype=torch.float32, device=vals.device)
     oi = torch.empty((B, k), dtype=torch.int32, device=vals.device)
-    st = _lib.lib().vpr_topk_merge(_ptr(vals), _ptr(idxs), R, B, k, _ptr(ov), _ptr(oi), _stream())
-    _lib.check(st, "vpr_topk_merge")
+    _call("vpr_topk_merge", _ptr(vals), _ptr(idxs), R, B, k, _ptr(ov), _ptr(oi), _stream())
     return ov, oi
 
 
 # ------------------------------------------------------------------------------------------ heads
-_POSE_PLANES: dict = {}
+_POSE_PLANES = cache(12)
+
+
+def _pack_w1_planes(W1: torch.Tensor, frag: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    hi = torch.empty(W1.shape, dtype=torch.bfloat16, device=W1.device)
+    lo = torch.empty(W1.shape, dtype=torch.bfloat16, device=W1.device)
+    if frag:
+        _call("vpr_pose_head_pack_w1_frag", _ptr(W1), W1.shape[0], W1.shape[1], _ptr(hi), _ptr(lo), _stream())
+    else:
+        _call("vpr_pose_head_pack_w1", _ptr(W1), W1.numel(), _ptr(hi), _ptr(lo), _stream())
+    return hi, lo
 
 
 def _pose_w1_planes(W1: torch.Tensor, frag: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -680,25 +648,7 @@ def _pose_w1_planes(W1: torch.Tensor, frag: bool = False) -> Tuple[torch.Tensor,
     or vpr_pose_head_pack_w1_frag (MFMA fragment order, for the single-launch kernel).
     The entry keeps a reference to W1: while it is cached its storage cannot be freed and handed to another weight
     of the same shape (a recycled address with version 0 would otherwise hit the stale planes)."""
-    key = (W1.data_ptr(), W1._version, tuple(W1.shape), str(W1.device), bool(frag))
-    hit = _POSE_PLANES.get(key)
-    if hit is None:
-        while len(_POSE_PLANES) >= 12:
-            old = _POSE_PLANES.pop(next(iter(_POSE_PLANES)))  # oldest first (dicts keep insertion order)
-            if old[3]:
-                _GRAPH_PINNED.append(old)                     # a captured graph reads these planes: never freed
-        hi = torch.empty(W1.shape, dtype=torch.bfloat16, device=W1.device)
-        lo = torch.empty(W1.shape, dtype=torch.bfloat16, device=W1.device)
-        if frag:
-            st = _lib.lib().vpr_pose_head_pack_w1_frag(_ptr(W1), W1.shape[0], W1.shape[1], _ptr(hi), _ptr(lo), _stream())
-            _lib.check(st, "vpr_pose_head_pack_w1_frag")
-        else:
-            st = _lib.lib().vpr_pose_head_pack_w1(_ptr(W1), W1.numel(), _ptr(hi), _ptr(lo), _stream())
-            _lib.check(st, "vpr_pose_head_pack_w1")
-        hit = _POSE_PLANES[key] = [hi, lo, W1, False]
-    if not hit[3] and capturing():
-        hit[3] = True
-    return hit[0], hit[1]
+    return _POSE_PLANES.get((tensor_key(W1), bool(frag)), _pack_w1_planes, (W1, frag), (W1,))
 
 
 def pose_head(x: torch.Tensor, W1: Optional[torch.Tensor], b1: Optional[torch.Tensor], W2: torch.Tensor,
@@ -732,21 +682,18 @@ def pose_head(x: torch.Tensor, W1: Optional[torch.Tensor], b1: Optional[torch.Te
     if fused_bytes > 0:
         hi, lo = _pose_w1_planes(W1, frag=True)
         ws = workspace("pose_fused", fused_bytes, x.device, zero=True)
-        st = L.vpr_pose_head_fused(_ptr(x), _ptr(hi), _ptr(lo), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(out), B, D, hidden,
-                                   n_out, int(sincos_offset), _ptr(ws), ws.numel(), _stream())
-        _lib.check(st, "vpr_pose_head_fused")
+        _call("vpr_pose_head_fused", _ptr(x), _ptr(hi), _ptr(lo), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(out), B, D, hidden,
+              n_out, int(sincos_offset), _ptr(ws), ws.numel(), _stream())
         return out
     if hidden > 0 and split and D % 32 == 0 and hidden % 16 == 0:
         hi, lo = _pose_w1_planes(W1)
         ws = workspace("pose", L.vpr_pose_head_split_workspace_bytes(B, D, hidden), x.device)
-        st = L.vpr_pose_head_split(_ptr(x), _ptr(hi), _ptr(lo), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(out), B, D, hidden,
-                                   n_out, int(sincos_offset), _ptr(ws), ws.numel(), _stream())
-        _lib.check(st, "vpr_pose_head_split")
+        _call("vpr_pose_head_split", _ptr(x), _ptr(hi), _ptr(lo), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(out), B, D, hidden,
+              n_out, int(sincos_offset), _ptr(ws), ws.numel(), _stream())
         return out
     ws = workspace("pose", L.vpr_pose_head_workspace_bytes(B, D, hidden, n_out), x.device)
-    st = L.vpr_pose_head(_ptr(x), _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(out), B, D, hidden, n_out,
-                         int(sincos_offset), _ptr(ws), ws.numel(), _stream())
-    _lib.check(st, "vpr_pose_head")
+    _call("vpr_pose_head", _ptr(x), _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(out), B, D, hidden, n_out,
+          int(sincos_offset), _ptr(ws), ws.numel(), _stream())
     return out
 
 
@@ -830,11 +777,9 @@ def head_train_epoch(X: torch.Tensor, Y: torch.Tensor, order: torch.Tensor, batc
             _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(m), _ptr(v), int(first_step), float(lr),
             float(betas[0]), float(betas[1]), float(eps), float(weight_decay), _loss_kind(loss), float(huber_delta), _ptr(losses))
     if p_drop == 0.0:
-        st = L.vpr_head_train_epoch(*args, _ptr(ws), ws.numel(), _stream())
-        _lib.check(st, "vpr_head_train_epoch")
+        _call("vpr_head_train_epoch", *args, _ptr(ws), ws.numel(), _stream())
     else:
-        st = L.vpr_head_train_epoch_dropout(*args, p_drop, seed, _ptr(ws), ws.numel(), _stream())
-        _lib.check(st, "vpr_head_train_epoch_dropout")
+        _call("vpr_head_train_epoch_dropout", *args, p_drop, seed, _ptr(ws), ws.numel(), _stream())
     for t in (W1, b1, W2, b2, m, v):
         torch.autograd.graph.increment_version(t)
     return losses
@@ -878,11 +823,9 @@ def head_train_step(X: torch.Tensor, Y: torch.Tensor, idx: Optional[torch.Tensor
             _ptr(W1), _ptr(b1), _ptr(W2), _ptr(b2), _ptr(m), _ptr(v), int(step), float(lr),
             float(betas[0]), float(betas[1]), float(eps), float(weight_decay), _loss_kind(loss), float(huber_delta), _ptr(loss_out))
     if p_drop == 0.0 and mask_out is None:
-        st = L.vpr_head_train_step(*args, _ptr(ws), ws.numel(), _stream())
-        _lib.check(st, "vpr_head_train_step")
+        _call("vpr_head_train_step", *args, _ptr(ws), ws.numel(), _stream())
     else:
-        st = L.vpr_head_train_step_dropout(*args, p_drop, seed, _ptr(mask_out), _ptr(ws), ws.numel(), _stream())
-        _lib.check(st, "vpr_head_train_step_dropout")
+        _call("vpr_head_train_step_dropout", *args, p_drop, seed, _ptr(mask_out), _ptr(ws), ws.numel(), _stream())
     for t in (W1, b1, W2, b2, m, v):          # written behind PyTorch's back: version-keyed caches (pose-head weight planes) must see it
         torch.autograd.graph.increment_version(t)
 
@@ -907,37 +850,41 @@ def ln_meanpool_head(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, e
             raise RuntimeError("ln_meanpool_head: head shapes")
     pooled = torch.empty((B, H), dtype=torch.float32, device=x.device) if (want_pooled or Wh is None) else None
     out = torch.empty((B, n_out), dtype=torch.float32, device=x.device) if Wh is not None else None
-    st = _lib.lib().vpr_ln_meanpool_head(_ptr(x), int(x.dtype == torch.bfloat16), B, T, H, _ptr(gamma), _ptr(beta),
-                                         float(eps), _ptr(pooled), _ptr(Wh), _ptr(bh), n_out, int(sincos_offset),
-                                         _ptr(out), _stream())
-    _lib.check(st, "vpr_ln_meanpool_head")
+    _call("vpr_ln_meanpool_head", _ptr(x), int(x.dtype == torch.bfloat16), B, T, H, _ptr(gamma), _ptr(beta),
+          float(eps), _ptr(pooled), _ptr(Wh), _ptr(bh), n_out, int(sincos_offset), _ptr(out), _stream())
     return pooled, out
 
 
 def f32_to_bf16(src: torch.Tensor) -> torch.Tensor:
     _need(src, torch.float32, "src")
     dst = torch.empty(src.shape, dtype=torch.bfloat16, device=src.device)
-    st = _lib.lib().vpr_f32_to_bf16(_ptr(src), _ptr(dst), src.numel(), _stream())
-    _lib.check(st, "vpr_f32_to_bf16")
+    _call("vpr_f32_to_bf16", _ptr(src), _ptr(dst), src.numel(), _stream())
     return dst
+
+
+def _ln_params(what: str, x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, pre_bias: Optional[torch.Tensor] = None) -> int:
+    """The parameter checks of the three LayerNorm wrappers (gamma / beta bf16 or f32, pre_bias f32, all [C]) -> C."""
+    if pre_bias is not None:
+        _need(pre_bias, torch.float32, "pre_bias", 1)
+    if gamma.dtype not in (torch.bfloat16, torch.float32) or beta.dtype != gamma.dtype:
+        raise RuntimeError(f"{what}: gamma/beta must both be bf16 or both f32")
+    _need(gamma, gamma.dtype, "gamma", 1)
+    _need(beta, beta.dtype, "beta", 1)
+    C = x.shape[-1]
+    if gamma.numel() != C or beta.numel() != C or (pre_bias is not None and pre_bias.numel() != C):
+        raise RuntimeError(f"{what}: parameter size")
+    return C
 
 
 def layernorm_bf16(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float) -> torch.Tensor:
     """LayerNorm over the last dim of a contiguous bf16 tensor (gamma/beta bf16 or f32) -> bf16."""
     _need(x, torch.bfloat16, "x")
-    if gamma.dtype not in (torch.bfloat16, torch.float32) or beta.dtype != gamma.dtype:
-        raise RuntimeError("layernorm_bf16: gamma/beta must both be bf16 or both f32")
-    _need(gamma, gamma.dtype, "gamma", 1)
-    _need(beta, beta.dtype, "beta", 1)
-    C = x.shape[-1]
-    if gamma.numel() != C or beta.numel() != C:
-        raise RuntimeError("layernorm_bf16: parameter size")
+    C = _ln_params("layernorm_bf16", x, gamma, beta)
     y = torch.empty_like(x)
     if x.numel() == 0:                       # no rows: nothing to launch (an empty tensor has no data pointer)
         return y
-    st = _lib.lib().vpr_layernorm_bf16(_ptr(x), _ptr(gamma), _ptr(beta), int(gamma.dtype == torch.bfloat16), float(eps),
-                                       _ptr(y), x.numel() // C, C, _stream())
-    _lib.check(st, "vpr_layernorm_bf16")
+    _call("vpr_layernorm_bf16", _ptr(x), _ptr(gamma), _ptr(beta), int(gamma.dtype == torch.bfloat16), float(eps),
+          _ptr(y), x.numel() // C, C, _stream())
     return y
 
 
@@ -948,8 +895,7 @@ def patchify_bf16(images: torch.Tensor, patch: int, kpad: int, lead_rows: int = 
     B, Cin, H, W = images.shape
     n = (H // patch) * (W // patch)
     out = torch.empty((B * (lead_rows + n), kpad), dtype=torch.bfloat16, device=images.device)
-    st = _lib.lib().vpr_patchify_bf16(_ptr(images), B, Cin, H, W, int(patch), int(kpad), int(lead_rows), _ptr(out), _stream())
-    _lib.check(st, "vpr_patchify_bf16")
+    _call("vpr_patchify_bf16", _ptr(images), B, Cin, H, W, int(patch), int(kpad), int(lead_rows), _ptr(out), _stream())
     return out
 
 
@@ -957,21 +903,12 @@ def bias_layernorm_bf16(x: torch.Tensor, pre_bias: torch.Tensor, gamma: torch.Te
                         eps: float) -> torch.Tensor:
     """LayerNorm(f32(x) + pre_bias) -> bf16; pre_bias [C] f32 is added before the statistics."""
     _need(x, torch.bfloat16, "x")
-    _need(pre_bias, torch.float32, "pre_bias", 1)
-    if gamma.dtype not in (torch.bfloat16, torch.float32) or beta.dtype != gamma.dtype:
-        raise RuntimeError("bias_layernorm_bf16: gamma/beta must both be bf16 or both f32")
-    _need(gamma, gamma.dtype, "gamma", 1)
-    _need(beta, beta.dtype, "beta", 1)
-    C = x.shape[-1]
-    if gamma.numel() != C or beta.numel() != C or pre_bias.numel() != C:
-        raise RuntimeError("bias_layernorm_bf16: parameter size")
+    C = _ln_params("bias_layernorm_bf16", x, gamma, beta, pre_bias)
     y = torch.empty_like(x)
     if x.numel() == 0:                       # no rows: nothing to launch (an empty tensor has no data pointer)
         return y
-    st = _lib.lib().vpr_bias_layernorm_bf16(_ptr(x), _ptr(pre_bias), _ptr(gamma), _ptr(beta),
-                                            int(gamma.dtype == torch.bfloat16), float(eps), _ptr(y),
-                                            x.numel() // C, C, _stream())
-    _lib.check(st, "vpr_bias_layernorm_bf16")
+    _call("vpr_bias_layernorm_bf16", _ptr(x), _ptr(pre_bias), _ptr(gamma), _ptr(beta),
+          int(gamma.dtype == torch.bfloat16), float(eps), _ptr(y), x.numel() // C, C, _stream())
     return y
 
 
@@ -982,18 +919,12 @@ def add_layernorm_bf16(x: torch.Tensor, res: torch.Tensor, gamma: torch.Tensor, 
     _need(res, torch.bfloat16, "res")
     if res.shape != x.shape:
         raise RuntimeError("add_layernorm_bf16: x and res shapes differ")
-    if gamma.dtype not in (torch.bfloat16, torch.float32) or beta.dtype != gamma.dtype:
-        raise RuntimeError("add_layernorm_bf16: gamma/beta must both be bf16 or both f32")
-    C = x.shape[-1]
-    if gamma.numel() != C or beta.numel() != C:
-        raise RuntimeError("add_layernorm_bf16: parameter size")
+    C = _ln_params("add_layernorm_bf16", x, gamma, beta)
     s, y = torch.empty_like(x), torch.empty_like(x)
     if x.numel() == 0:
         return s, y
-    st = _lib.lib().vpr_add_layernorm_bf16(_ptr(x), _ptr(res), _ptr(s), _ptr(gamma), _ptr(beta),
-                                           int(gamma.dtype == torch.bfloat16), float(eps), _ptr(y),
-                                           x.numel() // C, C, _stream())
-    _lib.check(st, "vpr_add_layernorm_bf16")
+    _call("vpr_add_layernorm_bf16", _ptr(x), _ptr(res), _ptr(s), _ptr(gamma), _ptr(beta),
+          int(gamma.dtype == torch.bfloat16), float(eps), _ptr(y), x.numel() // C, C, _stream())
     return s, y
 
 
@@ -1005,8 +936,7 @@ def attention_qkv_bf16(qkv: torch.Tensor, heads: int) -> torch.Tensor:
     if C3 != 3 * C or C % heads or C // heads != 64:
         raise RuntimeError("attention_qkv_bf16: needs head_dim 64 and a [B,T,3*H*64] input")
     out = torch.empty((B, T, C), dtype=torch.bfloat16, device=qkv.device)
-    st = _lib.lib().vpr_attention_qkv_bf16(_ptr(qkv), _ptr(out), B, T, heads, 64, 0.125, _stream())
-    _lib.check(st, "vpr_attention_qkv_bf16")
+    _call("vpr_attention_qkv_bf16", _ptr(qkv), _ptr(out), B, T, heads, 64, 0.125, _stream())
     return out
 
 
@@ -1019,9 +949,8 @@ def attention_qkv_split_bf16(qkv: torch.Tensor, B: int, T: int, body_tokens: int
     if C3 != 3 * C or C % heads or C // heads != 64 or rows != B * T or not (0 <= body_tokens <= T):
         raise RuntimeError("attention_qkv_split_bf16: needs head_dim 64 and a [B*T, 3*H*64] input")
     out = torch.empty((rows, C), dtype=torch.bfloat16, device=qkv.device)
-    st = _lib.lib().vpr_attention_qkv_split_bf16(_ptr(qkv), _ptr(out), B, T, int(body_tokens), B * int(body_tokens),
-                                                 heads, 64, 0.125, _stream())
-    _lib.check(st, "vpr_attention_qkv_split_bf16")
+    _call("vpr_attention_qkv_split_bf16", _ptr(qkv), _ptr(out), B, T, int(body_tokens), B * int(body_tokens),
+          heads, 64, 0.125, _stream())
     return out
 
 
@@ -1052,17 +981,12 @@ def skinny_linear_bf16(inp: torch.Tensor, weight: torch.Tensor, bias: Optional[t
             raise RuntimeError("skinny_linear_bf16: row_stats must be [N/16, M, 2] with N % 16 == 0")
         if stats_bias is not None:
             _need(stats_bias, torch.float32, "stats_bias", 1)
-        st = _lib.lib().vpr_skinny_linear_stats_bf16(_ptr(inp), inp.stride(0), _ptr(weight), weight.stride(0),
-                                                     _ptr(bias) if mode != 2 else None,
-                                                     int(bias is not None and bias.dtype == torch.bfloat16), int(mode),
-                                                     _ptr(out), out.stride(0), M, N, K, _ptr(stats_bias), _ptr(row_stats),
-                                                     _stream())
-        _lib.check(st, "vpr_skinny_linear_stats_bf16")
+        _call("vpr_skinny_linear_stats_bf16", _ptr(inp), inp.stride(0), _ptr(weight), weight.stride(0),
+              _ptr(bias) if mode != 2 else None, int(bias is not None and bias.dtype == torch.bfloat16), int(mode),
+              _ptr(out), out.stride(0), M, N, K, _ptr(stats_bias), _ptr(row_stats), _stream())
         return out
-    st = _lib.lib().vpr_skinny_linear_bf16(_ptr(inp), inp.stride(0), _ptr(weight), weight.stride(0), _ptr(bias) if mode != 2 else None,
-                                           int(bias is not None and bias.dtype == torch.bfloat16), int(mode),
-                                           _ptr(out), out.stride(0), M, N, K, _stream())
-    _lib.check(st, "vpr_skinny_linear_bf16")
+    _call("vpr_skinny_linear_bf16", _ptr(inp), inp.stride(0), _ptr(weight), weight.stride(0), _ptr(bias) if mode != 2 else None,
+          int(bias is not None and bias.dtype == torch.bfloat16), int(mode), _ptr(out), out.stride(0), M, N, K, _stream())
     return out
 
 
@@ -1111,9 +1035,7 @@ def bias_layernorm_cls_linear_bf16(x: torch.Tensor, pre_bias: Optional[torch.Ten
     if tuple(row_stats.shape) != (C // 16, n_cls, 2):
         raise RuntimeError("bias_layernorm_cls_linear_bf16: row_stats must be [C/16, n_cls, 2]")
     y = torch.empty_like(x)
-    st = _lib.lib().vpr_bias_layernorm_cls_linear_bf16(_ptr(x), _ptr(pre_bias), _ptr(gamma), _ptr(beta), float(eps), _ptr(y),
-                                                       M, C, int(cls_row0), n_cls, _ptr(row_stats), _ptr(consts.w_scaled),
-                                                       consts.w_scaled.stride(0), _ptr(consts.colsum), _ptr(consts.cprime),
-                                                       _ptr(consts.bprime), int(gelu), _ptr(out), out.stride(0), N, _stream())
-    _lib.check(st, "vpr_bias_layernorm_cls_linear_bf16")
+    _call("vpr_bias_layernorm_cls_linear_bf16", _ptr(x), _ptr(pre_bias), _ptr(gamma), _ptr(beta), float(eps), _ptr(y),
+          M, C, int(cls_row0), n_cls, _ptr(row_stats), _ptr(consts.w_scaled), consts.w_scaled.stride(0), _ptr(consts.colsum),
+          _ptr(consts.cprime), _ptr(consts.bprime), int(gelu), _ptr(out), out.stride(0), N, _stream())
     return y

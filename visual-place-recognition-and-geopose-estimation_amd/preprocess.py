@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ops import _need, _ptr, _stream, workspace
+from .ops import _call, _need, _ptr, _stream, workspace
 
 PRECISION_BITS = 22
 IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
@@ -106,11 +106,8 @@ class ResizeNormalize:
         O = self.out_size
         out = torch.empty((B, 3, O, O), dtype=self.out_dtype, device=dev)
         out_u8 = torch.empty((B, O, O, 3), dtype=torch.uint8, device=dev) if return_bytes else None
-        L = _lib.lib()
-        ws = workspace("preprocess", L.vpr_preprocess_workspace_bytes(B, H, O), dev)
-        st = L.vpr_preprocess_resize_normalize(_ptr(images_u8), B, H, W, O, O, _ptr(kx), _ptr(xb), ksx, _ptr(ky),
-                                               _ptr(yb), ksy, self._mean, self._std, _ptr(out),
-                                               int(self.out_dtype == torch.bfloat16), _ptr(out_u8), _ptr(ws),
-                                               ws.numel(), _stream())
-        _lib.check(st, "vpr_preprocess_resize_normalize")
+        ws = workspace("preprocess", _lib.lib().vpr_preprocess_workspace_bytes(B, H, O), dev)
+        _call("vpr_preprocess_resize_normalize", _ptr(images_u8), B, H, W, O, O, _ptr(kx), _ptr(xb), ksx, _ptr(ky),
+              _ptr(yb), ksy, self._mean, self._std, _ptr(out), int(self.out_dtype == torch.bfloat16), _ptr(out_u8),
+              _ptr(ws), ws.numel(), _stream())
         return (out, out_u8) if return_bytes else out
