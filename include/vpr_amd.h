@@ -294,11 +294,24 @@ int vpr_knn_topk_exhaustive(const void* q, const float* q_scale, const void* gal
                             int32_t* out_idx, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Per-row symmetric quantisation f32 -> e4m3: scale = max|x|/448 (1 for a zero row),
- * q = fp8_rne(x / scale).  x [rows, D] f32 (D % 4 == 0), q [rows, D] bytes, scale [rows] f32. */
+ * q = fp8_rne(x / scale).  x [rows, D] f32 (D % 4 == 0, 16-byte aligned), q [rows, D] bytes, scale [rows] f32.
+ * Arithmetic contract (compared byte for byte with oracle/knn.py::quantize_fp8_rows): scale is the IEEE f32 quotient
+ * fl(max|x| / 448), the byte is the OCP e4m3 round-to-nearest-even of the IEEE f32 quotient fl(x / scale) — ties to
+ * even in the normal and in the subnormal range (multiples of 2^-9 below 2^-6; magnitudes up to 2^-10 become zero),
+ * and the sign of a zero is kept (-0.0 -> 0x80; a row of zeros of either sign has scale 1).  f32 denormals are neither
+ * flushed on input nor on output: a row with max|x| below 448 * 2^-126 has a denormal scale with few significant bits
+ * and is quantised by that same rule (its maximum still maps to +-448).  NaN or Inf in x is out of contract.
+ * VPR_ERR_UNSUPPORTED for D % 4 != 0 or a misaligned x / q. */
 int vpr_quantize_fp8_rows(const float* x, long long rows, int D, uint8_t* q, float* scale, void* stream);
 
 /* Merge per-shard top-k lists (after an all-gather): vals/idxs [shards, B, k] -> [B, k],
- * same ordering contract.  Entries with idx < 0 are padding. */
+ * same ordering contract: (value desc, index asc) over the live entries of all shards, so equal values come out by
+ * the lower GLOBAL index wherever the shards hold them.  Live indices of one query are distinct.
+ * Padding: an entry with idx < 0 is padding whatever its value (the value is not looked at); with fewer than k live
+ * entries the tail of the output is (-inf, -1).  A live entry may hold -inf: it stays ahead of the padding.
+ * Zeros: values are ordered by their f32 bit pattern, so +0.0 sorts ABOVE -0.0 — the two are different keys, not a
+ * tie broken by index (the key is shared with the select stage of vpr_knn_topk).  NaN values are out of contract.
+ * Limits: 1 <= k <= 128 and shards * k <= 4096; beyond them VPR_ERR_UNSUPPORTED and the outputs are untouched. */
 int vpr_topk_merge(const float* vals, const int32_t* idxs, int shards, int B, int k,
                    float* out_val, int32_t* out_idx, void* stream);
 
@@ -315,7 +328,10 @@ int vpr_topk_merge(const float* vals, const int32_t* idxs, int shards, int B, in
  * x [B, D] f32; W1 [hidden, D]; b1 [hidden]; W2 [n_out, hidden or D]; b2 [n_out]; out [B, n_out].
  * A fused (lat, lon, sin, cos) head is n_out = 4 with row-concatenated W2 (block structure is
  * the caller's business) and sincos_offset = 2.  sincos_offset < 0 disables the normalise.
- * Requires D % 16 == 0, hidden % 32 == 0 (or 0), 1 <= n_out <= 8.
+ * A non-negative sincos_offset names a PAIR: it needs sincos_offset + 2 <= n_out.  Anything else (the last column
+ * alone, or past the end) is VPR_ERR_INVALID_ARG at every head entry point — vpr_pose_head, vpr_pose_head_split,
+ * vpr_pose_head_fused and, when a head is given, vpr_ln_meanpool_head — before anything is launched.
+ * Requires D % 16 == 0, hidden % 32 == 0 (or 0), 1 <= n_out <= 8.  The linear head (hidden = 0) takes any D >= 1.
  * ------------------------------------------------------------------------------------------ */
 size_t vpr_pose_head_workspace_bytes(int B, int D, int hidden, int n_out);
 
@@ -466,7 +482,8 @@ int vpr_salad_aggregate_train(const uint16_t* patch, long long patch_img_stride,
  * x [B, T, H] (bf16 if x_is_bf16 else f32); gamma, beta [H] f32; eps as in the model config.
  * pooled_out [B, H] f32 (may be NULL); Wh [n_out, H], bh [n_out], out [B, n_out] (Wh may be
  * NULL to skip the head, e.g. when an MLP head follows through vpr_pose_head).
- * H in {512, 768, 1024, 1536}; 0 <= n_out <= 8.
+ * H in {512, 768, 1024, 1536}; 0 <= n_out <= 8.  sincos_offset as for vpr_pose_head (a pair inside the head's
+ * outputs, or negative); it is not looked at when no head is given.
  * ------------------------------------------------------------------------------------------ */
 int vpr_ln_meanpool_head(const void* x, int x_is_bf16, int B, int T, int H,
                          const float* gamma, const float* beta, float eps,

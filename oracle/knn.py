@@ -56,17 +56,28 @@ def knn_topk_fp8(q_u8, q_scale, g_u8, g_scale, k: int, index_base: int = 0):
     return _order_topk(s.to(torch.float32), k, index_base)
 
 
+def f32_order_key(v: torch.Tensor) -> torch.Tensor:
+    """int64 key that orders f32 values as the kernels' packed key does: the total order of the bit patterns, i.e. the
+    numerical order with +0.0 ABOVE -0.0 (NaN is out of contract)."""
+    bits = v.contiguous().view(torch.int32).to(torch.int64)
+    return torch.where(bits >= 0, bits, -(bits & 0x7fffffff) - 1)
+
+
 def topk_merge(vals: torch.Tensor, idxs: torch.Tensor):
-    """vals/idxs [shards,B,k] -> [B,k] by (value desc, index asc); idx < 0 entries are padding."""
+    """vals/idxs [shards,B,k] -> [B,k] by (value desc, index asc), the contract of vpr_topk_merge (include/vpr_amd.h):
+    entries with idx < 0 are padding whatever their value and come out as (-inf, -1) behind every live entry (a live entry
+    may itself hold -inf); equal values are ordered by the lower global index, wherever the shards hold them; +0.0 sorts
+    above -0.0 (f32_order_key: they are different keys, not a tie); NaN values are out of contract."""
     R, B, k = vals.shape
-    v = vals.permute(1, 0, 2).reshape(B, R * k).clone()
+    v = vals.permute(1, 0, 2).reshape(B, R * k).clone().float()
     i = idxs.permute(1, 0, 2).reshape(B, R * k).to(torch.int64)
     v[i < 0] = float("-inf")
     key_i = torch.where(i < 0, torch.full_like(i, 2**40), i)
-    # sort by index first (stable), then by value (stable) -> (value desc, index asc)
+    i = torch.where(i < 0, torch.full_like(i, -1), i)
+    # sort by index first (stable), then by value (stable) -> (value desc, index asc); padding last among -inf
     o1 = torch.sort(key_i, dim=1, stable=True).indices
     v1, i1 = torch.gather(v, 1, o1), torch.gather(i, 1, o1)
-    o2 = torch.sort(-v1, dim=1, stable=True).indices[:, :k]
+    o2 = torch.sort(-f32_order_key(v1), dim=1, stable=True).indices[:, :k]
     ov, oi = torch.gather(v1, 1, o2), torch.gather(i1, 1, o2)
     return ov, oi.to(torch.int32)
 

@@ -59,6 +59,17 @@ def test_invalid_arguments_are_rejected_without_a_device(lib):
     assert lib.vpr_pose_head(p, p, p, p, p, p, 1, 65, 32, 2, -1, p, 4096, null) == -2    # D % 16
     assert lib.vpr_pose_head(p, p, p, p, p, p, 1, 64, 32, 9, -1, p, 4096, null) == -2    # n_out > 8
     assert lib.vpr_ln_meanpool_head(p, 0, 1, 4, 100, p, p, 1e-5, p, null, null, 0, -1, null, null) == -2   # H unsupported
+    # a non-negative sincos_offset needs sincos_offset + 2 <= n_out, at all five head entry points
+    for n_out, off in ((2, 1), (2, 2), (1, 0), (8, 7)):
+        assert lib.vpr_pose_head(p, p, p, p, p, p, 1, 64, 32, n_out, off, p, 4096, null) == -1
+        assert lib.vpr_pose_head(p, null, null, p, p, p, 1, 64, 0, n_out, off, p, 4096, null) == -1          # linear head
+        assert lib.vpr_pose_head_split(p, p, p, p, p, p, p, 1, 64, 32, n_out, off, p, 4096, null) == -1
+        assert lib.vpr_pose_head_fused(p, p, p, p, p, p, p, 1, 64, 32, n_out, off, p, 4096, null) == -1
+        assert lib.vpr_ln_meanpool_head(p, 0, 1, 4, 512, p, p, 1e-5, p, p, p, n_out, off, p, null) == -1
+    assert lib.vpr_ln_meanpool_head(p, 0, 1, 4, 100, p, p, 1e-5, p, null, null, 0, 3, null, null) == -2      # no head: the offset is not looked at
+    assert lib.vpr_topk_merge(p, p, 1, 1, 129, p, p, null) == -2                                             # k > 128
+    assert lib.vpr_topk_merge(p, p, 4097, 1, 1, p, p, null) == -2                                            # shards * k > 4096
+    assert lib.vpr_quantize_fp8_rows(p, 1, 6, p, p, null) == -2                                              # D % 4
     assert lib.vpr_gemm_nt_bf16(p, 64, 0, 0, p, 64, null, 0, p, 8, 0, 8, 8, 60, null) == -2   # K % 64
     a16 = ctypes.c_void_p((p.value + 15) // 16 * 16)
     b4 = ctypes.c_void_p(a16.value + 4)
@@ -96,6 +107,32 @@ def test_ops_refuse_cpu_tensors():
         ops.knn_topk(torch.zeros(1, 64, dtype=torch.bfloat16), torch.zeros(4, 64, dtype=torch.bfloat16), 1)
     with pytest.raises(RuntimeError, match="GPU tensor"):
         ops.pose_head(torch.zeros(1, 64), None, None, torch.zeros(2, 64), torch.zeros(2))
+
+
+def test_pair_offset_without_a_pair_raises_in_wrappers_fakes_and_oracle():
+    """sincos_offset + 2 <= n_out: ops.check_sincos_offset (what the wrappers call before anything else is judged), the
+    torch.ops.vpr fakes and the oracle all raise RuntimeError."""
+    import torch
+    from torch._subclasses.fake_tensor import FakeTensorMode
+    from vpr_amd import ops, torch_ops  # noqa: F401
+    from oracle import heads as oheads
+    for n_out, off in ((2, 1), (2, 2), (1, 0), (8, 7)):
+        with pytest.raises(RuntimeError, match="sincos_offset"):
+            ops.check_sincos_offset("pose_head", off, n_out)
+        with pytest.raises(RuntimeError, match="sincos_offset"):
+            oheads.mlp_head(torch.zeros(1, 4), None, None, torch.zeros(n_out, 4), torch.zeros(n_out), off)
+        with FakeTensorMode():
+            x, W2, b2 = torch.empty(3, 64), torch.empty(n_out, 64), torch.empty(n_out)
+            with pytest.raises(RuntimeError, match="sincos_offset"):
+                torch.ops.vpr.pose_head(x, None, None, W2, b2, off)
+            with pytest.raises(RuntimeError, match="sincos_offset"):
+                torch.ops.vpr.ln_meanpool_head(torch.empty(3, 4, 512), torch.empty(512), torch.empty(512), 1e-5,
+                                               torch.empty(n_out, 512), b2, off)
+    for n_out, off in ((2, 0), (8, 6), (1, -1), (3, -5)):
+        ops.check_sincos_offset("pose_head", off, n_out)
+    with FakeTensorMode():
+        assert torch.ops.vpr.pose_head(torch.empty(3, 64), None, None, torch.empty(2, 64), torch.empty(2), 0).shape == (3, 2)
+        assert torch.ops.vpr.ln_meanpool_head(torch.empty(3, 4, 512), torch.empty(512), torch.empty(512), 1e-5, None, None, 5)[0].shape == (3, 512)
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):

@@ -311,3 +311,129 @@ def test_gemm_ref_resolves_row_groups():
     w = torch.randn(5, K).to(torch.bfloat16)
     y, _, _ = ogemm.gemm_ref(flat, w, None, False, g, stride, lda, M)
     assert torch.equal(y, a.double() @ w.double().T)
+
+
+# ------------------------------------------------------------------------- head bounds (oracle/heads.py)
+def _head_ratio(out, x, W1, b1, W2, b2, split, slices):
+    from oracle import heads as oheads
+    ref = oheads.mlp_head(x, W1, b1, W2, b2)
+    bound = oheads.mlp_head_bound(x, W1, b1, W2, b2, split, slices=slices)
+    return ((out.double() - ref).abs() / bound).max().item()
+
+
+def test_mlp_head_bound_holds_for_f32_and_split_arithmetic_and_rejects_mistakes():
+    """On the inputs of the GPU edge tests (split-form K edges): plain torch f32 sits inside mlp_head_bound(split=False), the
+    CPU emulation of the (hi, lo) plane arithmetic inside mlp_head_bound(split=True), and each mistake falls outside.
+    A dropped lo plane (W1's, or x's as a broken split8 would) is an error of 2^-9 per product with random signs against a
+    budget of 2^-16 Σ|x||w|: the margin shrinks like 1 / sqrt(D) but holds on all five cases (it is lost near D = 1000)."""
+    from oracle import heads as oheads
+    for B, D, hidden, n_out, off, ks in oheads.SPLIT_K_EDGE_CASES:
+        x, W1, b1, W2, b2 = oheads.head_case_inputs(B, D, hidden, n_out, 1000 + D, off)
+        slices = oheads.split_case_slices(D, ks)
+        f32 = torch.relu(x @ W1.T + b1) @ W2.T + b2
+        assert _head_ratio(f32, x, W1, b1, W2, b2, False, slices) <= 1.0, D
+        for split in (False, True):
+            clean = oheads.mlp_head_emulated(x, W1, b1, W2, b2, split, slices)
+            assert _head_ratio(clean, x, W1, b1, W2, b2, split, slices) <= 1.0, (D, split)
+            mistakes = ["bias_after_relu", "drop_step", "slice_twice"]
+            if split:
+                mistakes += ["lo_zero", "x_lo_zero"]
+            for m in mistakes:
+                bad = oheads.mlp_head_emulated(x, W1, b1, W2, b2, split, slices, m)
+                assert _head_ratio(bad, x, W1, b1, W2, b2, split, slices) > 1.0, (D, split, m)
+        # a normalised pair: the bound stays finite (r far from 0) and the f32 evaluation inside it
+        if off >= 0:
+            ref = oheads.mlp_head(x, W1, b1, W2, b2, off)
+            bound = oheads.mlp_head_bound(x, W1, b1, W2, b2, False, off, slices)
+            assert torch.isfinite(bound).all() and float(oheads.mlp_head(x, W1, b1, W2, b2)[:, off:off + 2].norm(dim=1).min()) > 0.05
+            got = oheads._normalize_pair(f32.clone(), off)
+            assert ((got.double() - ref).abs() <= bound).all()
+
+
+def test_normalize_pair_refuses_an_offset_without_a_pair():
+    from oracle import heads as oheads
+    out = torch.ones(2, 3, dtype=torch.float64)
+    for off in (2, 3, 7):
+        with pytest.raises(RuntimeError):
+            oheads._normalize_pair(out, off)
+    assert torch.equal(oheads._normalize_pair(out, -1), out)
+    assert (oheads._normalize_pair(out, 1)[:, 1:].norm(dim=1) - 1).abs().max().item() < 1e-15
+
+
+@pytest.mark.parametrize("B,D,hidden,n_out", [(3, 32, 16, 4), (5, 1056, 208, 8), (2, 224, 48, 1), (4, 257, 0, 8)])
+def test_exact_head_operands_are_exact_in_any_order(B, D, hidden, n_out):
+    """f32 evaluation under a shuffled summation order (K-steps permuted, several slab counts, split planes or not) equals
+    the f64 result bit for bit; the three kinds of hidden unit are all there; every lo plane is zero."""
+    from oracle import heads as oheads
+    x, W1, b1, W2, b2 = oheads.exact_head_operands(B, D, hidden, n_out, 7)
+    ref = oheads.mlp_head(x, W1, b1, W2, b2)
+    assert torch.equal(ref.float().double(), ref)
+    g = torch.Generator().manual_seed(0)
+    if hidden == 0:
+        for _ in range(3):
+            p = torch.randperm(D, generator=g)
+            acc = torch.zeros(B, n_out)
+            for d in p.tolist():
+                acc = acc + x[:, d:d + 1] * W2[:, d][None, :]
+            assert torch.equal((acc + b2).double(), ref)
+        return
+    z = x.double() @ W1.double().T + b1.double()
+    assert (z > 0).any() and (z < 0).any() and (z == 0).any()
+    assert (z[:, 0::4] > 0).all() and (z[:, 1::4] < 0).all() and (z[0, 2::4] == 0).all() and (z[:, 3::4] == 0).all()
+    assert not oheads._split_planes(x)[1].any() and not oheads._split_planes(W1)[1].any()
+    nsteps = -(-D // 32)
+    for slices in (1, 2, 5):
+        for split in (False, True):
+            perm = torch.randperm(nsteps, generator=g).tolist()
+            got = oheads.mlp_head_emulated(x, W1, b1, W2, b2, split, slices, perm=perm)
+            assert torch.equal(got.double(), ref), (slices, split)
+    h = torch.relu(z).float()                                   # second layer, one product at a time in a shuffled order
+    acc = torch.zeros(B, n_out)
+    for j in torch.randperm(hidden, generator=g).tolist():
+        acc = acc + h[:, j:j + 1] * W2[:, j][None, :]
+    assert torch.equal((acc + b2).double(), ref)
+
+
+def test_ln_meanpool_bound_holds_for_two_pass_f32_and_rejects_one_pass_variance():
+    from oracle import heads as oheads
+    g = torch.Generator().manual_seed(5)
+    eps = 1e-5
+    for T, H in ((17, 512), (65, 1024), (33, 1536)):
+        gamma, beta = 1 + 0.1 * torch.randn(H, generator=g), 0.1 * torch.randn(H, generator=g)
+        Wh, bh = torch.randn(4, H, generator=g) / H ** 0.5, torch.tensor([0.1, -0.2, 1.5, -2.0])
+        for kind in ("unit", "offset1000"):
+            x = oheads.ln_case_rows(kind, 2, T, H, g)
+            pooled_ref, out_ref = oheads.ln_meanpool_head(x, gamma, beta, eps, Wh, bh, 2)
+            pb, ob = oheads.ln_meanpool_bound(x, gamma, beta, eps, Wh, bh, 2)
+            if kind == "unit":          # the bound is not slack: torch f32 comes within a factor 50 of it, and it is ~10x below 2e-5
+                tight = (((torch.nn.functional.layer_norm(x, (H,), gamma, beta, eps).mean(1).double() - pooled_ref).abs() / pb).max().item())
+                assert tight >= 0.02 and pb.median().item() < 4e-6, (T, H, tight, pb.median().item())
+            y = torch.nn.functional.layer_norm(x, (H,), gamma, beta, eps)              # torch f32: two-pass statistics
+            pooled = y.mean(1)
+            out = oheads._normalize_pair(pooled @ Wh.T + bh, 2)
+            assert ((pooled.double() - pooled_ref).abs() <= pb).all(), (T, H, kind)
+            assert ((out.double() - out_ref).abs() <= ob).all(), (T, H, kind)
+            if kind == "offset1000":                                                   # E[x^2] - mean^2 in f32: var is noise
+                mean = x.mean(-1, keepdim=True)
+                var = ((x * x).mean(-1, keepdim=True) - mean * mean).clamp_min(0)
+                bad = (((x - mean) * torch.rsqrt(var + eps)) * gamma + beta).mean(1)
+                assert ((bad.double() - pooled_ref).abs() > pb).any(), (T, H)
+
+
+def test_merge_and_quantise_oracles_known_answers():
+    """oracle/knn.py on hand-worked cases: the merge orders (value desc, index asc) with padding last as (-inf, -1) and +0.0
+    above -0.0; the quantiser rounds e4m3 ties to even in the normal and the subnormal range."""
+    inf = float("inf")
+    vals = torch.tensor([[[0.5, inf, -0.0]], [[0.5, 0.0, -inf]]])
+    idxs = torch.tensor([[[9, -3, 1]], [[4, 7, 2]]], dtype=torch.int32)
+    v, i = oknn.topk_merge(vals, idxs)
+    assert i.tolist() == [[4, 9, 7]] and v.tolist() == [[0.5, 0.5, 0.0]]
+    v, i = oknn.topk_merge(vals[:, :, 1:], idxs[:, :, 1:])
+    assert i.tolist() == [[7, 1]] and torch.signbit(v).tolist() == [[False, True]]
+    v, i = oknn.topk_merge(vals[:1, :, :], idxs[:1, :, :])
+    assert i.tolist() == [[9, 1, -1]] and v[0, 2].item() == -inf
+    x = torch.tensor([[448.0, 17.0, 19.0, 232.0, 248.0, 432.0, 2.0 ** -10, 3 * 2.0 ** -10, -0.0, -(2.0 ** -10), 15 * 2.0 ** -10, 0.0]])
+    q, s = oknn.quantize_fp8_rows(x)
+    assert s.tolist() == [1.0]
+    assert q.view(torch.float8_e4m3fn).float().tolist() == [[448.0, 16.0, 20.0, 224.0, 256.0, 448.0, 0.0, 2.0 ** -8, -0.0, -0.0, 2.0 ** -6, 0.0]]
+    assert q[0, 8].item() == 0x80 and q[0, 9].item() == 0x80 and q[0, 11].item() == 0

@@ -712,6 +712,9 @@ __global__ __launch_bounds__(256) void pose_pack_frag_kernel(const float* __rest
   }
 }
 
+// A non-negative sincos_offset names the pair [offset, offset + 1]: both must be outputs (include/vpr_amd.h).
+static bool sincos_offset_ok(int sincos_offset, int n_out) { return sincos_offset < 0 || sincos_offset + 2 <= n_out; }
+
 struct PoseFusedPlan { int ks, ntiles, mtiles, sps; size_t off_part, off_part2, total; };
 static bool pose_fused_plan(int B, int D, int hidden, PoseFusedPlan* p);
 
@@ -789,6 +792,7 @@ extern "C" int vpr_pose_head_fused(const float* x, const uint16_t* W1_hi_frag, c
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (!x || !W1_hi_frag || !W1_lo_frag || !b1 || !W2 || !b2 || !out || !workspace || B <= 0 || D <= 0 || hidden <= 0 || n_out < 1)
     return VPR_ERR_INVALID_ARG;
+  if (!sincos_offset_ok(sincos_offset, n_out)) return VPR_ERR_INVALID_ARG;
   if (n_out > 8) return VPR_ERR_UNSUPPORTED;
   PoseFusedPlan p;
   if (!pose_fused_plan(B, D, hidden, &p)) return VPR_ERR_UNSUPPORTED;
@@ -824,6 +828,7 @@ extern "C" int vpr_pose_head(const float* x, const float* W1, const float* b1, c
                              int sincos_offset, void* workspace, size_t workspace_bytes, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (!x || !W2 || !b2 || !out || B <= 0 || D <= 0 || hidden < 0 || n_out < 1) return VPR_ERR_INVALID_ARG;
+  if (!sincos_offset_ok(sincos_offset, n_out)) return VPR_ERR_INVALID_ARG;
   if (n_out > 8) return VPR_ERR_UNSUPPORTED;
   if (hidden == 0) {
     VPR_TRY_LAUNCH(launch_kernel(pose_linear_kernel, dim3(B), dim3(256), 0, stream, x, W2, b2, out, D, n_out, sincos_offset));
@@ -864,6 +869,7 @@ extern "C" int vpr_ln_meanpool_head(const void* x, int x_is_bf16, int B, int T, 
   if (!x || !gamma || !beta || B <= 0 || T <= 0 || n_out < 0) return VPR_ERR_INVALID_ARG;
   if (n_out > 8) return VPR_ERR_UNSUPPORTED;
   if (n_out > 0 && Wh && (!bh || !out)) return VPR_ERR_INVALID_ARG;
+  if (n_out > 0 && Wh && !sincos_offset_ok(sincos_offset, n_out)) return VPR_ERR_INVALID_ARG;
   if (!pooled_out && !(Wh && n_out > 0)) return VPR_ERR_INVALID_ARG;
   if (reinterpret_cast<uintptr_t>(x) & 15) return VPR_ERR_UNSUPPORTED;
   switch (H) {
@@ -898,6 +904,7 @@ extern "C" int vpr_pose_head_split(const float* x, const uint16_t* W1_hi, const 
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (!x || !W1_hi || !W1_lo || !b1 || !W2 || !b2 || !out || !workspace || B <= 0 || D <= 0 || hidden <= 0 || n_out < 1)
     return VPR_ERR_INVALID_ARG;
+  if (!sincos_offset_ok(sincos_offset, n_out)) return VPR_ERR_INVALID_ARG;
   if (n_out > 8 || (D % 32) || (hidden % 16)) return VPR_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(W1_hi) | reinterpret_cast<uintptr_t>(W1_lo) |
        reinterpret_cast<uintptr_t>(workspace)) & 15)

@@ -633,6 +633,12 @@ def topk_merge(vals: torch.Tensor, idxs: torch.Tensor) -> Tuple[torch.Tensor, to
 _POSE_PLANES = cache(12)
 
 
+def check_sincos_offset(what: str, sincos_offset: int, n_out: int) -> None:
+    """The rule of include/vpr_amd.h: a non-negative sincos_offset names the output pair [offset, offset + 1]."""
+    if sincos_offset >= 0 and sincos_offset + 2 > n_out:
+        raise RuntimeError(f"{what}: sincos_offset {sincos_offset} needs sincos_offset + 2 <= n_out = {n_out}")
+
+
 def _pack_w1_planes(W1: torch.Tensor, frag: bool) -> Tuple[torch.Tensor, torch.Tensor]:
     hi = torch.empty(W1.shape, dtype=torch.bfloat16, device=W1.device)
     lo = torch.empty(W1.shape, dtype=torch.bfloat16, device=W1.device)
@@ -676,6 +682,7 @@ def pose_head(x: torch.Tensor, W1: Optional[torch.Tensor], b1: Optional[torch.Te
         raise RuntimeError("pose_head: W2 must be [n_out, D] for the linear head")
     if b2.numel() != n_out:
         raise RuntimeError("pose_head: b2 size")
+    check_sincos_offset("pose_head", int(sincos_offset), n_out)
     L = _lib.lib()
     out = torch.empty((B, n_out), dtype=torch.float32, device=x.device)
     fused_bytes = L.vpr_pose_head_fused_workspace_bytes(B, D, hidden) if (hidden > 0 and split and fused) else 0
@@ -848,6 +855,7 @@ def ln_meanpool_head(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, e
         n_out = Wh.shape[0]
         if Wh.shape[1] != H or bh.numel() != n_out:
             raise RuntimeError("ln_meanpool_head: head shapes")
+        check_sincos_offset("ln_meanpool_head", int(sincos_offset), n_out)
     pooled = torch.empty((B, H), dtype=torch.float32, device=x.device) if (want_pooled or Wh is None) else None
     out = torch.empty((B, n_out), dtype=torch.float32, device=x.device) if Wh is not None else None
     _call("vpr_ln_meanpool_head", _ptr(x), int(x.dtype == torch.bfloat16), B, T, H, _ptr(gamma), _ptr(beta),

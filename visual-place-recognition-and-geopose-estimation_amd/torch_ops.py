@@ -179,6 +179,7 @@ def pose_head(x: Tensor, W1: Optional[Tensor], b1: Optional[Tensor], W2: Tensor,
 
 @pose_head.register_fake
 def _(x, W1, b1, W2, b2, sincos_offset):
+    ops.check_sincos_offset("pose_head", sincos_offset, W2.shape[0])
     return x.new_empty((x.shape[0], W2.shape[0]), dtype=torch.float32)
 
 
@@ -196,6 +197,8 @@ def ln_meanpool_head(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, Wh: Opt
 @ln_meanpool_head.register_fake
 def _(x, gamma, beta, eps, Wh, bh, sincos_offset):
     B, _, H = x.shape
+    if Wh is not None:
+        ops.check_sincos_offset("ln_meanpool_head", sincos_offset, Wh.shape[0])
     return x.new_empty((B, H), dtype=torch.float32), x.new_empty((B, 0 if Wh is None else Wh.shape[0]), dtype=torch.float32)
 
 
