@@ -376,12 +376,14 @@ int vpr_pose_head_fused(const float* x, const uint16_t* W1_hi_frag, const uint16
  * Replaces, per batch, dinov2salad/dinov2salad_finetuning.py:119-125 (`preds = model(inputs)`, `loss_fn(preds, targets)`,
  * `optimizer.zero_grad()`, `loss.backward()`, `optimizer.step()`) with `optimizer = torch.optim.AdamW(lr=1e-5)` (:95) and
  * `loss_fn = nn.MSELoss()` (:96), for a frozen extractor whose descriptors were computed once.
- * X [rows, x_stride] f32 descriptors, Y [rows, y_stride] f32 (standardised) targets; idx [B] int32 device = the rows of this
+ * X [rows, x_stride] f32 descriptors, Y [rows, y_stride] f32 (standardised) targets: x_stride >= D and y_stride >= n_out floats
+ * between rows, the padding and every row the batch does not name are never read; idx [B] int32 device = the rows of this
  * batch (NULL: rows 0..B-1; the caller guarantees 0 <= idx < rows).  W1 [hidden, D], b1 [hidden], W2 [n_out, hidden],
  * b2 [n_out]: f32, updated IN PLACE.  m, v: AdamW moments, vpr_head_train_state_floats() floats each, laid out
  * [W1 | b1 | W2 | b2], zero before step 1, updated in place.  step = 1, 2, ... (number of this update: bias corrections).
  * Hyper-parameters are doubles, as Python holds them; every derived scalar (1 - lr*wd, lr / (1 - beta1^step), ...) is formed in
- * double and rounded to f32 once, and the update follows torch.optim.AdamW's order of operations.
+ * double and rounded to f32 once, and the update follows torch.optim.AdamW's order of operations.  A parameter whose gradient
+ * and moments are zero (a dead ReLU unit) divides 0 by eps: with eps = 0 that is 0 / 0 = NaN, as in torch.
  * loss_kind: VPR_LOSS_MSE (nn.MSELoss, the script above) or VPR_LOSS_HUBER with huber_delta > 0 (nn.HuberLoss(delta): the loss of
  * dinov2salad_finetuning_2.py:154 / swin_transformer/swin_attempt_2.py:158 — 0.5 d^2 for |d| < delta, delta (|d| - 0.5 delta) beyond;
  * mean over the B * n_out elements); huber_delta is ignored for MSE.

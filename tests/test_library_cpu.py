@@ -193,3 +193,19 @@ def test_tuning_switches_come_from_the_environment_of_the_loading_process():
     env.pop("VPR_POSE_KS", None)
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, check=True).stdout.split()
     assert out[0] == "1" and out[1] == "None" and "208, 2, 0" in " ".join(out[2:])
+
+
+def test_head_train_slice_count_matches_the_oracle_restatement(lib):
+    """oracle/finetune.py restates head_train_slices (its error bounds need the slab count).  The first region of the
+    training workspace is align256(ks * B * hidden * 4) bytes, so the library's ks shows in the total."""
+    from oracle import finetune as oft
+    shapes = [(B, D, hidden, 2) for D, hidden in oft.FORWARD_EDGES for B in oft.FORWARD_BATCHES] + list(oft.UPDATE_EDGES)
+    shapes += [(6, 8448, 512, 2), (64, 8448, 1024, 4), (33, 256, 64, 8), (5, 64, 32, 2)]
+    seen = set()
+    for B, D, hidden, n_out in shapes:
+        total = lib.vpr_head_train_workspace_bytes(B, D, hidden, n_out)
+        assert total > 0, (B, D, hidden, n_out)
+        ks = oft.head_train_slices(B, D, hidden)
+        seen.add(ks)
+        assert oft.head_train_first_region(total, B, hidden, n_out) == -(-ks * B * hidden * 4 // 256) * 256, (B, D, hidden, n_out, ks)
+    assert {1, 64} <= seen and len(seen) >= 6, seen          # the clamp at one slice, the cap, and several in between

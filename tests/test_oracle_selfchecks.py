@@ -437,3 +437,140 @@ def test_merge_and_quantise_oracles_known_answers():
     assert s.tolist() == [1.0]
     assert q.view(torch.float8_e4m3fn).float().tolist() == [[448.0, 16.0, 20.0, 224.0, 256.0, 448.0, 0.0, 2.0 ** -8, -0.0, -0.0, 2.0 ** -6, 0.0]]
     assert q[0, 8].item() == 0x80 and q[0, 9].item() == 0x80 and q[0, 11].item() == 0
+
+
+# ------------------------------------------------------------------------------- head-training bounds (oracle/finetune.py)
+from oracle import finetune as oft
+
+_GRADS = ("W1", "b1", "W2", "b2")
+
+
+def _ratios(got, ref, bound):
+    """max |got - ref| / bound per tensor (0 / 0 counts as 0: an element whose bound is 0 must be exact)."""
+    out = {}
+    for k in ("loss",) + _GRADS:
+        err = np.abs(np.asarray(got[k], dtype=np.float64) - ref[k])
+        b = np.asarray(bound[k], dtype=np.float64)
+        out[k] = float(np.max(np.where(err == 0, 0.0, err / np.maximum(b, 1e-300))))
+    return out
+
+
+def _torch_f32_grads(x, y, W1, b1, W2, b2):
+    t = [torch.from_numpy(np.array(a)).requires_grad_(i >= 2) for i, a in enumerate((x, y, W1, b1, W2, b2))]
+    loss = torch.nn.functional.mse_loss(torch.relu(t[0] @ t[2].T + t[3]) @ t[4].T + t[5], t[1])
+    loss.backward()
+    return dict(loss=float(loss.detach()), **{k: a.grad.numpy() for k, a in zip(_GRADS, t[2:])})
+
+
+@pytest.mark.parametrize("targets", ["far", "near"])
+@pytest.mark.parametrize("D,hidden", oft.FORWARD_EDGES)
+def test_head_grad_bounds_hold_torch_f32(D, hidden, targets):
+    for B in oft.FORWARD_BATCHES:
+        ops_ = oft.train_case_inputs(B, D, hidden, 2, 100 + B, targets)
+        ref, bound = oft.head_grad_bounds(*ops_)
+        r = _ratios(_torch_f32_grads(*ops_), ref, bound)
+        print(f"\n[torch f32 / bound D={D} hidden={hidden} B={B} {targets}] " + " ".join(f"{k} {v:.2e}" for k, v in r.items()))
+        assert max(r.values()) <= 1.0, r
+
+
+def test_head_grad_bounds_hold_update_edges_and_emulation():
+    for B, D, hidden, n_out in oft.UPDATE_EDGES:
+        ops_ = oft.train_case_inputs(B, D, hidden, n_out, 200 + B)
+        ref, bound = oft.head_grad_bounds(*ops_)
+        for name, got in (("torch", _torch_f32_grads(*ops_)), ("slabs", oft.head_grads_f32(*ops_))):
+            r = _ratios(got, ref, bound)
+            print(f"\n[{name} f32 / bound B={B} D={D} hidden={hidden} n_out={n_out}] " + " ".join(f"{k} {v:.2e}" for k, v in r.items()))
+            assert max(r.values()) <= 1.0, r
+
+
+def _dropout_case(B, D, hidden, n_out, p, seed):
+    ops_ = oft.train_case_inputs(B, D, hidden, n_out, seed)
+    mask = np.random.default_rng(seed + 1).random((B, hidden)) >= p
+    return ops_, mask
+
+
+@pytest.mark.parametrize("mutate,case,tensor", [
+    ("row_tail", ("far", 9, 1040, 32, 3), "W1"),
+    ("drop_slice", ("near", 16, 4160, 32, 2), "W1"),
+    ("slab_twice", ("near", 16, 4160, 32, 2), "W1"),
+    ("gscale_pad", ("far", 17, 1040, 32, 3), "b2"),
+])
+def test_head_grad_bounds_reject_mistakes(mutate, case, tensor):
+    targets, B, D, hidden, n_out = case
+    ops_ = oft.train_case_inputs(B, D, hidden, n_out, 7, targets)
+    ref, bound = oft.head_grad_bounds(*ops_)
+    good, bad = _ratios(oft.head_grads_f32(*ops_), ref, bound), _ratios(oft.head_grads_f32(*ops_, mutate=mutate), ref, bound)
+    print(f"\n[{mutate} at {case}] err / bound {tensor}: right {good[tensor]:.2e}, mistaken {bad[tensor]:.2e}")
+    assert max(good.values()) <= 1.0 and bad[tensor] > 1.0
+
+
+def test_head_grad_bounds_dropout_and_missing_scale():
+    for p in (0.3, 0.9):
+        ops_, mask = _dropout_case(17, 1040, 96, 3, p, 11)
+        ref, bound = oft.head_grad_bounds(*ops_, mask=mask, dropout_p=p)
+        good = _ratios(oft.head_grads_f32(*ops_, mask=mask, dropout_p=p), ref, bound)
+        bad = _ratios(oft.head_grads_f32(*ops_, mask=mask, dropout_p=p, mutate="no_drop_s"), ref, bound)
+        print(f"\n[dropout p={p}] err / bound: right {max(good.values()):.2e}; s left out of dz: W1 {bad['W1']:.2e} b1 {bad['b1']:.2e}")
+        assert max(good.values()) <= 1.0 and bad["W1"] > 1.0 and bad["b1"] > 1.0
+        assert bad["W2"] <= 1.0 and bad["b2"] <= 1.0            # the mistake is confined to dz
+
+
+@pytest.mark.parametrize("B,D,hidden,n_out", [(16, 1040, 64, 4), (64, 4160, 32, 1)])
+def test_exact_train_operands_are_exact_and_catch_the_mask(B, D, hidden, n_out):
+    ops_ = oft.exact_train_operands(B, D, hidden, n_out, 5)
+    value, grads = oft.loss_and_grads(oft.HeadState(*ops_[2:]), ops_[0], ops_[1])
+    got = oft.head_grads_f32(*ops_)
+    assert got["loss"] == value
+    for k, g in zip(_GRADS, grads):
+        assert np.array_equal(got[k].astype(np.float64), g), k
+    kind = np.arange(hidden) % 4
+    assert not grads[0][kind == 1].any() and not grads[1][kind == 1].any()
+    bad = oft.head_grads_f32(*ops_, mutate="mask_ge")
+    nbad = int((bad["W1"].astype(np.float64) != grads[0]).sum())
+    print(f"\n[exact operands B={B} D={D} hidden={hidden}] h >= 0 as the mask changes {nbad} elements of gW1")
+    assert nbad > 0 and bad["W1"][kind == 1].any()
+
+
+def _adam_state(n, seed):
+    rng = np.random.default_rng(seed)
+    g = (10.0 ** rng.uniform(-6, 0, n) * rng.choice([-1.0, 1.0], n)).astype(np.float32)      # 1e-6 .. 1: eps = 1e-3 is first order
+    m = (g * rng.uniform(0.2, 2.0, n) * rng.choice([-1.0, 1.0, 1.0], n)).astype(np.float32)
+    v = (g.astype(np.float64) ** 2 * rng.uniform(0.1, 4.0, n)).astype(np.float32)
+    p = rng.standard_normal(n).astype(np.float32) * np.float32(0.05)
+    return p, m, v, g
+
+
+def _adam_ratio(got, p, m, v, g, c):
+    ref, bound = oft.adamw_element(p, m, v, g, c), oft.adamw_element_bound(p, m, v, g, c)
+    return [float(np.max(np.abs(a.astype(np.float64) - r) / b)) for a, r, b in zip(got, ref, bound)]
+
+
+@pytest.mark.parametrize("betas", [(0.9, 0.999), (0.5, 0.9), (0.0, 0.999)])
+def test_adamw_bound_holds_numpy_f32_in_both_contraction_forms(betas):
+    p, m, v, g = _adam_state(20000, 3)
+    worst = 0.0
+    for step in (1, 2, 10, 1000, 100000):
+        for eps in (1e-8, 1e-3):
+            for wd, lr in ((0.0, 1e-5), (0.01, 1e-1), (0.5, 1e-1), (0.5, 0.0)):
+                c = oft.adamw_consts(step, lr, betas, eps, wd)
+                for fused in (False, True):
+                    r = _adam_ratio(oft.adamw_f32(p, m, v, g, c, fused=fused), p, m, v, g, c)
+                    worst = max(worst, max(r))
+                    assert max(r) <= 1.0, (step, eps, wd, lr, fused, r)
+    print(f"\n[numpy f32 AdamW / bound betas={betas}] worst {worst:.2e}")
+
+
+@pytest.mark.parametrize("mistake", ["eps_inside", "decay_after", "bc_prev", "swap_betas"])
+def test_adamw_bound_rejects_mistakes(mistake):
+    p, m, v, g = _adam_state(20000, 4)
+    hyper = dict(step=2, lr=1e-1, betas=(0.9, 0.999), eps=1e-3, weight_decay=0.5)
+    c = oft.adamw_consts(**hyper)
+    wrong = dict(hyper)
+    if mistake == "bc_prev":
+        wrong["step"] = 1
+    if mistake == "swap_betas":
+        wrong["betas"] = (0.999, 0.9)
+    got = oft.adamw_f32(p, m, v, g, oft.adamw_consts(**wrong), mutate=mistake if mistake in ("eps_inside", "decay_after") else None)
+    good, bad = _adam_ratio(oft.adamw_f32(p, m, v, g, c), p, m, v, g, c), _adam_ratio(got, p, m, v, g, c)
+    print(f"\n[AdamW {mistake}] err / bound (p, m, v): right {good}, mistaken {bad}")
+    assert max(good) <= 1.0 and bad[0] > 1.0

@@ -729,8 +729,8 @@ def _loss_kind(loss: str) -> int:
 
 
 def _head_train_check(X, Y, W1, b1, W2, b2, m, v):
-    _need(X, torch.float32, "X", 2)
-    _need(Y, torch.float32, "Y", 2)
+    _need_rows(X, torch.float32, "X")           # rows may be padded: stride(0) goes to C as x_stride / y_stride
+    _need_rows(Y, torch.float32, "Y")
     _need(W1, torch.float32, "W1", 2)
     _need(b1, torch.float32, "b1", 1)
     _need(W2, torch.float32, "W2", 2)
@@ -765,6 +765,7 @@ def head_train_epoch(X: torch.Tensor, Y: torch.Tensor, order: torch.Tensor, batc
     """One pass over the rows listed in `order` (int32, device) in batches of `batch_size` (vpr_head_train_epoch: the whole
     launch sequence enqueued by ONE library call).  Returns the batch losses [ceil(n / batch_size)] (device tensor; nothing
     waits for the GPU).  The caller guarantees 0 <= order < X.shape[0]: the kernels gather rows by these indices unchecked.
+    X and Y may have padded rows (unit column stride, X.stride(0) % 4 == 0), as for head_train_step.
     dropout_p > 0: nn.Dropout(dropout_p) in training mode after the ReLU, masks drawn from (dropout_seed, step, position in
     the batch, hidden unit) as include/vpr_amd.h specifies (vpr_head_train_epoch_dropout)."""
     D, hidden, n_out = _head_train_check(X, Y, W1, b1, W2, b2, m, v)
@@ -799,7 +800,8 @@ def head_train_step(X: torch.Tensor, Y: torch.Tensor, idx: Optional[torch.Tensor
                     dropout_p: float = 0.0, dropout_seed: int = 0, mask_out: Optional[torch.Tensor] = None) -> None:
     """One batch of head-only fine-tuning on cached descriptors (vpr_head_train_step): forward, MSELoss, backward and
     AdamW update of Linear(D,hidden)-ReLU-Linear(hidden,n_out), in place on W1 / b1 / W2 / b2 / m / v.
-    X [rows, D] f32, Y [rows, n_out] f32, idx [B] int32 (rows of the batch; None = all rows of X in order).  loss_out: a
+    X [rows, D] f32, Y [rows, n_out] f32, unit column stride, rows may be padded (X.stride(0) % 4 == 0: the library refuses
+    anything else); idx [B] int32 (rows of the batch; None = all rows of X in order).  loss_out: a
     one-element f32 tensor (e.g. losses[i:i+1]) that receives the batch loss.  loss: "mse" (nn.MSELoss) or "huber"
     (nn.HuberLoss(delta=huber_delta)).  No host synchronisation.
     dropout_p > 0: Linear -> ReLU -> Dropout(dropout_p) -> Linear in training mode (vpr_head_train_step_dropout; the mask

@@ -209,7 +209,8 @@ def head_train_epoch(X: Tensor, Y: Tensor, order: Tensor, batch_size: int, W1: T
                      weight_decay: float, loss: str = "mse", huber_delta: float = 1.0) -> Tensor:
     """One pass of head-only fine-tuning over the cached descriptor rows listed in `order` (int32), batches of `batch_size`:
     forward, MSELoss (or HuberLoss), backward and AdamW of Linear(D,hidden)-ReLU-Linear(hidden,n_out) per batch, IN PLACE on the
-    parameters and on the moment buffers (ops.head_train_state).  Returns the batch losses.  dinov2salad_finetuning.py:113-128
+    parameters and on the moment buffers (ops.head_train_state).  X and Y may have padded rows (unit column stride; X.stride(0) % 4
+    == 0).  Returns the batch losses.  dinov2salad_finetuning.py:113-128
     (one epoch of the loop) on descriptors computed once.  vpr_head_train_epoch."""
     return ops.head_train_epoch(X, Y, order, batch_size, W1, b1, W2, b2, m, v, first_step, lr, (beta1, beta2), eps, weight_decay,
                                 loss, huber_delta)
