@@ -1,4 +1,4 @@
-"""ctypes binding of libvpr_amd.so — one prototype per entry point of include/vpr_amd.h.
+"""ctypes binding of libvpr_amd.so — one prototype per entry point of include/vpr_amd.h and of its extension headers.
 
 There is no fallback: if the library is missing, `lib()` raises with the build command.
 """
@@ -139,6 +139,16 @@ PROTOTYPES = {
     "vpr_f32_to_bf16": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p]),
 }
 
+# Additive extensions of ABI 6, one header each beside include/vpr_amd.h (present iff the symbol is exported); bound after
+# PROTOTYPES, which stays the exact symbol list of vpr_amd.h.
+POSE_TOP1, POSE_WEIGHTED = 0, 1
+EXTENSION_PROTOTYPES = {
+    # include/vpr_amd_retrieval.h: vals idx B k | labels n_labels | mode temperature | q_targets tau | scaler (host) |
+    # pose64 pose4 hit_tau hit_region | stream
+    "vpr_retrieval_pose": (c_int, [_P, _P, c_int, c_int, _P, c_longlong, c_int, c_double, _P, c_double, _P,
+                                   _P, _P, _P, _P, _P]),
+}
+
 
 def library_path() -> str:
     """The in-tree library; VPR_AMD_LIBRARY points an A/B run at another build of it (scripts/ab_libs.sh)."""
@@ -156,7 +166,7 @@ def lib() -> ctypes.CDLL:
                 "Build it with `python -c \"import __graft_entry__ as g; g.build()\"` "
                 "or `make -C visual-place-recognition-and-geopose-estimation_amd/csrc`.")
         handle = ctypes.CDLL(path)
-        for name, (restype, argtypes) in PROTOTYPES.items():
+        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(EXTENSION_PROTOTYPES.items()):
             fn = getattr(handle, name)   # AttributeError if a declared symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

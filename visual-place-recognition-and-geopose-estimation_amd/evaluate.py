@@ -328,10 +328,45 @@ def build_gallery_from_images(extractor: DinoV2Salad, csv_path: str, image_dir: 
     return len(names)
 
 
+def retrieval_metrics(vals: torch.Tensor, idx: torch.Tensor, labels: np.ndarray, targets: np.ndarray, regions: np.ndarray,
+                      angles: np.ndarray, tau: float, mode: str, on_device: bool = False, temperature: float = 0.01) -> dict:
+    """The metric block of calculate_retrieval_scores from the top-k lists vals / idx [Q, k] (device), the gallery's label
+    table [N, 4] and the queries' targets [Q, 2] (lat, lon), Region_IDs [Q] and angles [Q] (degrees).
+    on_device=False: gallery.label_transfer and recall_at_k over positives_by_distance / positives_by_region on the host
+    ([Q, N] intermediates).  on_device=True: pose and both first-hit ranks from ONE torch.ops.vpr.retrieval_pose call over
+    all Q rows; nothing of size [Q, N] is built, and the recalls are recall_from_first_hit of those ranks (the same
+    numbers).  The label table and the queries' (lat, lon, Region_ID) are copied to the device for the call."""
+    from . import gallery as G
+    kk = idx.shape[1]
+    targets = np.asarray(targets, dtype=np.float64)
+    if on_device:
+        from . import torch_ops  # noqa: F401  registers torch.ops.vpr.*
+        q = np.concatenate([targets, np.asarray(regions, dtype=np.float64)[:, None]], axis=1)
+        pose_d, _, hit_tau, hit_region = torch.ops.vpr.retrieval_pose(
+            vals.contiguous(), idx.contiguous(), G.device_labels(labels, vals.device), mode, temperature,
+            torch.from_numpy(q).to(vals.device), float(tau), None)
+        pose, ht, hr = pose_d.cpu().numpy(), hit_tau.cpu().numpy(), hit_region.cpu().numpy()
+        r1_tau, rk_tau = postproc.recall_from_first_hit(ht, 1), postproc.recall_from_first_hit(ht, kk)
+        r1_region = postproc.recall_from_first_hit(hr, 1)
+        top = idx.cpu().numpy()
+    else:
+        pose = G.label_transfer(vals, idx, labels, mode=mode, temperature=temperature)
+        top = idx.cpu().numpy()
+        pos_d = G.positives_by_distance(targets, labels[:, :2], tau)
+        pos_r = G.positives_by_region(regions, labels[:, 3])
+        r1_tau, rk_tau = postproc.recall_at_k(top[:, :1], pos_d), postproc.recall_at_k(top, pos_d)
+        r1_region = postproc.recall_at_k(top[:, :1], pos_r)
+    return {"topk_scores": vals.cpu().numpy(), "topk_indices": top, "pose": pose,
+            "final_loss": postproc.final_loss(pose[:, :2], targets),
+            "maae": postproc.mean_absolute_angular_error(pose[:, 2], np.asarray(angles, dtype=np.float64)),
+            "recall_at_1_tau": r1_tau, f"recall_at_{kk}_tau": rk_tau, "recall_at_1_region": r1_region}
+
+
 @torch.no_grad()
 def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv_path: str, image_dir: str, *, k: int = 10,
                                tau: float = 25.0, mode: str = "top1", batch_size: int = 64, device: str = "cuda", graph: bool = True,
-                               image_size: int = 224, rank: int = 0, world: int = 1, group=None, verbose: bool = True) -> dict:
+                               image_size: int = 224, rank: int = 0, world: int = 1, group=None, verbose: bool = True,
+                               on_device: bool = False) -> dict:
     """Validation split through descriptor -> sharded cosine top-k -> label transfer:
       pose      (lat, lon, angle) of the best match, or the softmax-weighted mean of the k matches (gallery.label_transfer);
       final_loss on lat/lon with the validation scripts' formula (dinov2salad_validation.py:101), MAAE on the angle
@@ -339,7 +374,9 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
       Recall@1 / Recall@k with positives = gallery rows within `tau` label units of the query (Euclidean on the projected
                 lat/lon) and, separately, rows of the same Region_ID.
     With world > 1 every rank runs this with its shard (load_gallery_shard) and its share of the queries is gathered by
-    ShardedGallery.search_local_queries; the metrics are then those of this rank's queries."""
+    ShardedGallery.search_local_queries; the metrics are then those of this rank's queries.
+    on_device: the metrics come from the k neighbours alone, on the GPU (retrieval_metrics) — for galleries where the host
+    path's [Q, N] arrays do not fit."""
     from . import gallery as G
     from .retrieval import ShardedGallery
     dev = torch.device(device)
@@ -360,18 +397,11 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
         v, i = sg.search_local_queries(d16, kk)
         sel = torch.tensor(idxs, device=dev)
         vals[sel], idx[sel] = v, i
-    labels = shard.labels
-    pose = G.label_transfer(vals, idx, labels, mode=mode)
-    targets = df[["latitude", "longitude"]].to_numpy(dtype=np.float64)
-    top = idx.cpu().numpy()
-    pos_d = G.positives_by_distance(targets, labels[:, :2], tau)
-    pos_r = G.positives_by_region(df["Region_ID"].to_numpy(), labels[:, 3])
-    res = {"filenames": names, "topk_scores": vals.cpu().numpy(), "topk_indices": top, "pose": pose,
-           "final_loss": postproc.final_loss(pose[:, :2], targets),
-           "maae": postproc.mean_absolute_angular_error(pose[:, 2], df["angle"].to_numpy(dtype=np.float64)),
-           "recall_at_1_tau": postproc.recall_at_k(top[:, :1], pos_d), f"recall_at_{kk}_tau": postproc.recall_at_k(top, pos_d),
-           "recall_at_1_region": postproc.recall_at_k(top[:, :1], pos_r),
-           "uncertified_queries": sg.uncertified_queries()}        # flagged on the device (and re-run exactly), for the record
+    res = {"filenames": names}
+    res.update(retrieval_metrics(vals, idx, shard.labels, df[["latitude", "longitude"]].to_numpy(dtype=np.float64),
+                                 df["Region_ID"].to_numpy(), df["angle"].to_numpy(dtype=np.float64), tau, mode,
+                                 on_device=on_device))
+    res["uncertified_queries"] = sg.uncertified_queries()        # flagged on the device (and re-run exactly), for the record
     if verbose:
         print(f"final_loss: {res['final_loss']}")
         print(f"Mean Absolute Angular Error (MAAE): {res['maae']:.4f} degrees")

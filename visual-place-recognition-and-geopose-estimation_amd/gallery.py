@@ -34,6 +34,7 @@ class GalleryShard:
     n_total: int
     index_base: int
     dtype: str
+    labels_dev: Optional[torch.Tensor] = None   # [N, 4] float64 on the GPU: the same table for ops.retrieval_pose (device_labels)
 
 
 def save_gallery(path: str, descriptors: torch.Tensor, labels: np.ndarray, scales: Optional[torch.Tensor] = None,
@@ -63,7 +64,21 @@ def save_gallery(path: str, descriptors: torch.Tensor, labels: np.ndarray, scale
                    "label_columns": list(LABEL_COLUMNS)}, f)
 
 
-def load_gallery_shard(path: str, device: torch.device, rank: int = 0, world: int = 1) -> GalleryShard:
+def device_labels(labels: np.ndarray, device: torch.device) -> torch.Tensor:
+    """The label side table as ops.retrieval_pose reads it: [N, 4] float64 (latitude, longitude, angle, Region_ID) on
+    `device`.  It is the FULL table, replicated on every rank (the merged top-k holds global rows): 32 MB at 1M rows."""
+    labels = np.ascontiguousarray(labels, dtype=np.float64)
+    if labels.ndim != 2 or labels.shape[1] != len(LABEL_COLUMNS):
+        raise ValueError(f"labels must be [N,{len(LABEL_COLUMNS)}] = {LABEL_COLUMNS}")
+    return torch.from_numpy(labels).to(device)
+
+
+_device_labels = device_labels       # load_gallery_shard's flag of the same name shadows the function inside it
+
+
+def load_gallery_shard(path: str, device: torch.device, rank: int = 0, world: int = 1,
+                       device_labels: bool = False) -> GalleryShard:
+    """device_labels: also place the label table on `device` (GalleryShard.labels_dev), for the on-device retrieval pose."""
     with open(os.path.join(path, "meta.json")) as f:
         meta = json.load(f)
     if meta.get("version") != 1:
@@ -78,7 +93,8 @@ def load_gallery_shard(path: str, device: torch.device, rank: int = 0, world: in
         sc = np.load(os.path.join(path, "scales.npy"), mmap_mode="r")
         scales = torch.from_numpy(np.array(sc[lo:hi])).to(device)
     labels = np.load(os.path.join(path, "labels.npy"))
-    return GalleryShard(rows, scales, labels, meta["n"], lo, meta["dtype"])
+    labels_dev = _device_labels(labels, device) if device_labels else None
+    return GalleryShard(rows, scales, labels, meta["n"], lo, meta["dtype"], labels_dev)
 
 
 def labels_from_csv(csv_path: str) -> Tuple[np.ndarray, List[str]]:

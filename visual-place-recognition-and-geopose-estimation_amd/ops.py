@@ -629,6 +629,48 @@ def topk_merge(vals: torch.Tensor, idxs: torch.Tensor) -> Tuple[torch.Tensor, to
     return ov, oi
 
 
+_POSE_MODES = {"top1": _lib.POSE_TOP1, "weighted": _lib.POSE_WEIGHTED}
+
+
+def retrieval_pose(vals: torch.Tensor, idx: torch.Tensor, labels_dev: torch.Tensor, mode: str = "top1",
+                   temperature: float = 0.01, q_targets: Optional[torch.Tensor] = None, tau: float = 0.0,
+                   scaler=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Geopose and first-hit ranks of the merged top-k, on the device (include/vpr_amd_retrieval.h).
+    vals f32 / idx int32 [B, k] (k <= 64), labels_dev f64 [N, 4] = (lat, lon, angle_deg, Region_ID) (gallery.device_labels),
+    q_targets f64 [B, 3] = each query's (lat, lon, Region_ID) or None, scaler = four host numbers (mean_lat, mean_lon,
+    scale_lat, scale_lon) or None.  Returns (pose64 f64 [B, 3] = lat, lon, angle_deg; pose4 f32 [B, 4] = standardised
+    lat / lon, sin, cos; hit_tau int32 [B]; hit_region int32 [B]); the hits are -1 without q_targets."""
+    _need(vals, torch.float32, "vals", 2)
+    _need(idx, torch.int32, "idx", 2)
+    _need(labels_dev, torch.float64, "labels_dev", 2)
+    if vals.shape != idx.shape:
+        raise RuntimeError("retrieval_pose: vals and idx shapes differ")
+    if labels_dev.shape[1] != 4:
+        raise RuntimeError("retrieval_pose: labels_dev must be [N, 4] = (lat, lon, angle_deg, Region_ID)")
+    if mode not in _POSE_MODES:
+        raise RuntimeError("retrieval_pose: mode must be 'top1' or 'weighted'")
+    B, k = vals.shape
+    if q_targets is not None:
+        _need(q_targets, torch.float64, "q_targets", 2)
+        if q_targets.shape != (B, 3):
+            raise RuntimeError("retrieval_pose: q_targets must be [B, 3] = (lat, lon, Region_ID)")
+    sc = None
+    if scaler is not None:
+        scaler = [float(x) for x in scaler]
+        if len(scaler) != 4:
+            raise RuntimeError("retrieval_pose: scaler must be (mean_lat, mean_lon, scale_lat, scale_lon)")
+        sc = (ctypes.c_double * 4)(*scaler)                           # read during the call: a temporary is enough
+    dev = vals.device
+    pose64 = torch.empty((B, 3), dtype=torch.float64, device=dev)
+    pose4 = torch.empty((B, 4), dtype=torch.float32, device=dev)
+    hit_tau = torch.empty((B,), dtype=torch.int32, device=dev)
+    hit_region = torch.empty((B,), dtype=torch.int32, device=dev)
+    _call("vpr_retrieval_pose", _ptr(vals), _ptr(idx), B, k, _ptr(labels_dev), labels_dev.shape[0], _POSE_MODES[mode],
+          float(temperature), _ptr(q_targets), float(tau), sc, _ptr(pose64), _ptr(pose4), _ptr(hit_tau), _ptr(hit_region),
+          _stream())
+    return pose64, pose4, hit_tau, hit_region
+
+
 # ------------------------------------------------------------------------------------------ heads
 _POSE_PLANES = cache(12)
 

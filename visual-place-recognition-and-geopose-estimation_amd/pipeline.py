@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 
 from .modules import DinoV2Salad, FusedGeoPoseHead
-from .retrieval import GraphedRetrieval, ShardedGallery
+from .retrieval import GraphedRetrieval, ShardedGallery, pose_labels, pose_scaler
 
 
 @dataclass
@@ -22,15 +22,24 @@ class StepOutput:
     topk_scores: torch.Tensor          # [B, k] f32
     topk_indices: torch.Tensor         # [B, k] int32 (global gallery rows)
     pose: torch.Tensor                 # [B, 4] f32: standardised (lat, lon), unit (sin, cos)
+    retrieval_pose: Optional[torch.Tensor] = None   # [B, 4] f32, same format, transferred from the neighbours' labels
 
 
 class VPRGeoPosePipeline:
     def __init__(self, extractor: DinoV2Salad, head: FusedGeoPoseHead, gallery: ShardedGallery, k: int = 10,
-                 overlap_head: Optional[bool] = None, graph_retrieval: bool = False):
+                 overlap_head: Optional[bool] = None, graph_retrieval: bool = False, labels=None,
+                 retrieval_mode: str = "top1", temperature: float = 0.01, scaler=None):
         """graph_retrieval: the retrieval leg of every step — {query all-gather, local shard search, packed top-k
         all-gather, merge} — is ONE HIP-graph replay (retrieval.GraphedRetrieval, captured at the first step of a given
         batch size; every rank must step in lockstep, as with the eager collectives).  BASELINE config 5's "hipGraph-
-        captured per-batch retrieval"."""
+        captured per-batch retrieval".
+        labels: the gallery's full [N, 4] label table (gallery.device_labels, or a host array copied to the device once):
+        every step also transfers the neighbours' labels to a pose on the device (torch.ops.vpr.retrieval_pose, inside the
+        graph when graph_retrieval) — StepOutput.retrieval_pose, in the head's 4-wide format under `scaler` (four numbers
+        or a postproc.LatLonScaler; None = no standardisation).  retrieval_mode "top1" | "weighted" with `temperature`, as
+        gallery.label_transfer.  Without labels the step is unchanged and the field stays None."""
+        self.labels = None if labels is None else pose_labels(labels, gallery.rows.device)
+        self.retrieval_mode, self.temperature, self.scaler = retrieval_mode, temperature, pose_scaler(scaler)
         self.extractor, self.head, self.gallery, self.k = extractor, head, gallery, k
         self.graph_retrieval = graph_retrieval
         self._graphed = {}
@@ -52,7 +61,7 @@ class VPRGeoPosePipeline:
     def step(self, images: torch.Tensor) -> StepOutput:
         desc, desc16 = self.extractor.features(images, want_bf16=True, events=self.salad_events)
         g = self.gallery
-        pose = None
+        pose = rpose = None
         if self.overlap_head:
             main = torch.cuda.current_stream(desc.device)
             side = self._side_stream(desc.device, main)
@@ -64,7 +73,8 @@ class VPRGeoPosePipeline:
             key = (desc16.shape[0], torch.cuda.current_stream(desc.device).cuda_stream)   # one graph (and its buffers) per lane
             gr = self._graphed.get(key)
             if gr is None:
-                gr = self._graphed[key] = GraphedRetrieval(g, desc16.shape[0], self.k)
+                gr = self._graphed[key] = GraphedRetrieval(g, desc16.shape[0], self.k, self.labels, self.retrieval_mode,
+                                                           self.temperature, self.scaler)
             if self.knn_events is not None:                # a graph has no seam for events: the whole replay is timed
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
@@ -73,6 +83,8 @@ class VPRGeoPosePipeline:
                 e1.record()
                 self.knn_events.append((e0, e1))
             v, i = v.clone(), i.clone()                    # the graph's output buffers are rewritten by the next replay
+            if self.labels is not None:
+                rpose = gr.pose4.clone()
         else:
             q_all = g.gather_queries(desc16)
             # knn_events: same kernels, run as the two stages of the call with HIP events around the score stage
@@ -80,9 +92,12 @@ class VPRGeoPosePipeline:
             if g.collective:
                 b = desc.shape[0]
                 v, i = v[g.rank * b:(g.rank + 1) * b], i[g.rank * b:(g.rank + 1) * b]
+            if self.labels is not None:
+                _, rpose, _, _ = torch.ops.vpr.retrieval_pose(v.contiguous(), i.contiguous(), self.labels, self.retrieval_mode,
+                                                              self.temperature, None, 0.0, self.scaler)
         if self.overlap_head:
             main.wait_stream(side)
             pose.record_stream(main)
         else:
             pose = self.head(desc)
-        return StepOutput(desc, v, i, pose)
+        return StepOutput(desc, v, i, pose, rpose)

@@ -86,3 +86,10 @@ def recall_at_k(topk_idx: np.ndarray, positives) -> float:
         pos = {int(pos)} if np.isscalar(pos) else {int(p) for p in pos}
         hits += bool(pos.intersection(int(r) for r in row))
     return hits / max(1, len(topk_idx))
+
+
+def recall_from_first_hit(hit: np.ndarray, j: int) -> float:
+    """Recall@j from each query's first-hit rank (vpr_retrieval_pose: the smallest position of a positive among its
+    neighbours, -1 for none): mean(0 <= hit < j).  Equals recall_at_k(topk_idx[:, :j], positives)."""
+    hit = np.asarray(hit)
+    return int(np.count_nonzero((hit >= 0) & (hit < j))) / max(1, len(hit))

@@ -58,6 +58,24 @@ class HipEngine:
         return torch.ops.vpr.topk_merge(vals, idxs)
 
 
+def pose_labels(labels, device) -> torch.Tensor:
+    """The label table for torch.ops.vpr.retrieval_pose: a [N, 4] float64 tensor on `device` (gallery.device_labels /
+    GalleryShard.labels_dev) is taken as it is; a host array is copied there once."""
+    if not isinstance(labels, torch.Tensor):
+        import numpy as np
+        labels = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.float64))
+    return labels.to(device=device, dtype=torch.float64).contiguous()
+
+
+def pose_scaler(scaler):
+    """None, four numbers (mean_lat, mean_lon, scale_lat, scale_lon), or a postproc.LatLonScaler -> the op's `scaler`."""
+    if scaler is None:
+        return None
+    if hasattr(scaler, "mean_"):
+        return [float(scaler.mean_[0]), float(scaler.mean_[1]), float(scaler.scale_[0]), float(scaler.scale_[1])]
+    return [float(x) for x in scaler]
+
+
 def all_gather_topk(v: torch.Tensor, i: torch.Tensor, world: int, group=None):
     """Per-shard (vals f32, idx i32) [B,k] -> [world, B, k] on every rank with ONE all-gather: the
     two arrays travel as one int32 buffer [B, 2k] (values bit-cast), since at these sizes
@@ -161,10 +179,17 @@ class GraphedRetrieval:
     retrieval").  Static shapes: B_local queries per rank, k, this shard.  The kernels take stream-ordered arguments
     and pre-allocated workspaces; RCCL's collectives are captured like any other stream work (every rank must
     capture and replay in lockstep).  With one rank and no forced collectives the graph holds the local search only.
-    Replay: copy the queries into `self.q`, `replay()`, read `self.vals` / `self.idx` (this rank's B_local rows)."""
+    Replay: copy the queries into `self.q`, `replay()`, read `self.vals` / `self.idx` (this rank's B_local rows).
+    labels (the full [N, 4] label table, gallery.device_labels): the graph also runs torch.ops.vpr.retrieval_pose on this
+    rank's merged rows; `self.pose64` ([B_local, 3] f64: lat, lon, angle_deg) and `self.pose4` ([B_local, 4] f32, the fused
+    head's format under `scaler`) are rewritten by every replay like vals / idx.  Without labels both stay None."""
 
-    def __init__(self, gallery: ShardedGallery, batch_local: int, k: int):
+    def __init__(self, gallery: ShardedGallery, batch_local: int, k: int, labels=None, mode: str = "top1",
+                 temperature: float = 0.01, scaler=None):
         self.g, self.k, self.b = gallery, k, batch_local
+        self.labels = None if labels is None else pose_labels(labels, gallery.rows.device)
+        self.mode, self.temperature, self.scaler = mode, temperature, pose_scaler(scaler)
+        self.pose64 = self.pose4 = None
         if gallery.exact_fallback:
             raise RuntimeError("GraphedRetrieval: exact_fallback reads the certificate back on the host — not capturable")
         if gallery.collective and dist.get_backend(gallery.group) != "nccl":
@@ -208,7 +233,11 @@ class GraphedRetrieval:
         q_all = g.gather_queries(self.q)
         v, i = g.search(q_all, self.k, self.ws)
         lo = g.rank * self.b if g.collective else 0
-        return v[lo:lo + self.b], i[lo:lo + self.b]
+        v, i = v[lo:lo + self.b], i[lo:lo + self.b]
+        if self.labels is not None:
+            self.pose64, self.pose4, _, _ = torch.ops.vpr.retrieval_pose(v, i, self.labels, self.mode, self.temperature,
+                                                                         None, 0.0, self.scaler)
+        return v, i
 
     def __call__(self, q_local: torch.Tensor):
         self.q.copy_(q_local)

@@ -7,6 +7,7 @@ that seam, so the HIP hot path is visible to PyTorch's dispatcher like any other
     torch.ops.vpr.salad_aggregate / salad_aggregate_split / salad_aggregate_f32
     torch.ops.vpr.salad_aggregate_train                (training mode: Dropout active in the score / cluster MLPs)
     torch.ops.vpr.knn_topk / knn_topk_fp8 / topk_merge
+    torch.ops.vpr.retrieval_pose                       (geopose and first-hit ranks from the merged top-k)
     torch.ops.vpr.pose_head / ln_meanpool_head
     torch.ops.vpr.head_train_epoch                     (head-only fine-tuning pass; mutates parameters and AdamW moments)
     torch.ops.vpr.head_train_epoch_dropout             (the same pass with Dropout(p) after the ReLU, training mode)
@@ -169,6 +170,22 @@ def _(vals, idxs):
     return vals.new_empty((B, k), dtype=torch.float32), vals.new_empty((B, k), dtype=torch.int32)
 
 
+@torch.library.custom_op("vpr::retrieval_pose", mutates_args=())
+def retrieval_pose(vals: Tensor, idx: Tensor, labels_dev: Tensor, mode: str = "top1", temperature: float = 0.01,
+                   q_targets: Optional[Tensor] = None, tau: float = 0.0,
+                   scaler: Optional[List[float]] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Merged top-k [B, k] + device label table f64 [N, 4] -> (pose f64 [B, 3] = lat, lon, angle_deg; pose f32 [B, 4] in the
+    fused head's format; first-hit rank within tau int32 [B]; first same-Region_ID rank int32 [B]).  vpr_retrieval_pose."""
+    return ops.retrieval_pose(vals, idx, labels_dev, mode, temperature, q_targets, tau, scaler)
+
+
+@retrieval_pose.register_fake
+def _(vals, idx, labels_dev, mode="top1", temperature=0.01, q_targets=None, tau=0.0, scaler=None):
+    B = vals.shape[0]
+    return (vals.new_empty((B, 3), dtype=torch.float64), vals.new_empty((B, 4), dtype=torch.float32),
+            vals.new_empty((B,), dtype=torch.int32), vals.new_empty((B,), dtype=torch.int32))
+
+
 # ------------------------------------------------------------------------------------------------------------ heads
 @torch.library.custom_op("vpr::pose_head", mutates_args=())
 def pose_head(x: Tensor, W1: Optional[Tensor], b1: Optional[Tensor], W2: Tensor, b2: Tensor, sincos_offset: int) -> Tensor:
@@ -240,4 +257,4 @@ def _(X, Y, order, batch_size, W1, b1, W2, b2, m, v, first_step, lr, beta1, beta
 
 
 OPS = ("head_train_epoch", "head_train_epoch_dropout", "salad_aggregate", "salad_aggregate_split", "salad_aggregate_f32", "salad_aggregate_train", "knn_topk", "knn_topk_fp8", "quantize_fp8_rows",
-       "topk_merge", "pose_head", "ln_meanpool_head")
+       "topk_merge", "pose_head", "ln_meanpool_head", "retrieval_pose")
