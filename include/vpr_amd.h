@@ -219,9 +219,10 @@ int vpr_knn_topk(const uint16_t* q, const uint16_t* gallery, int B, int N, int D
 /* Stage entry points of vpr_knn_topk (same workspace layout), so the dominant kernel can be
  * timed by itself (bench.py roofline) and tested by itself.
  *   scores:  S[b, n] = <q_b, g_n>  (bf16 MFMA, f32 accumulate)  -> workspace
- *            B <= 64: the HBM-streaming kernel (one gallery pass, 208- or 256-row tiles by shard size); B > 64 (the
- *            all-gathered batch of a multi-GPU job): an MFMA GEMM, 128 x 128 tiles or — 256-row query tiles at least 3/4
- *            full and >= 256 tiles — the 256 x 256-tile kernel.  vpr_knn_scores_kernel_name() tells which.
+ *            Fewer than 65 queries (VPR_KNN_GEMM_MIN_B): the HBM-streaming kernel (one gallery pass per 64 queries,
+ *            208- or 256-row tiles by shard size); more (the all-gathered batch of a multi-GPU job): an MFMA GEMM on
+ *            128 x 128 tiles, or — 256-row query tiles at least 3/4 full, and bf16: >= 192 tiles x K slices, e4m3: D >= 256 — on
+ *            256 x 256 tiles.  vpr_knn_scores_kernel_name() tells which.
  *   select:  per-query candidate selection + exact rescoring + final ordering + certificate (see "Checked forms") */
 int vpr_knn_scores(const uint16_t* q, const uint16_t* gallery, int B, int N, int D,
                    void* workspace, size_t workspace_bytes, void* stream);
@@ -229,11 +230,12 @@ int vpr_knn_select(const uint16_t* q, const uint16_t* gallery, int B, int N, int
                    int index_base, float* out_val, int32_t* out_idx,
                    void* workspace, size_t workspace_bytes, void* stream);
 /* Name (as a kernel trace shows it, without the argument list) of the kernel vpr_knn_topk[_fp8] launches for the
- * score stage of a B-query batch against an N-row shard of 8448-d descriptors: lets bench.py tie its roofline line to
- * profiles/ by name.  <= 64 queries: knn_scores_kernel<fp8, tile rows, 2, flags> (208-row tiles, K split over up to
- * 16 slabs below 106k rows; 256-row tiles above; above 131k rows — several tiles per workgroup — flags 52: score
- * tiles leave as whole row segments through LDS with nt stores); more queries: gemm_nt / gemm256 (split-K for small
- * shards). */
+ * score stage of a B-query batch against an N-row shard of 8448-d descriptors, under the tuning switches as they are
+ * now (the call's own description, so the two cannot disagree): lets bench.py and scripts/ find the kernel's row in a
+ * trace.  Streaming route: knn_scores_kernel<fp8, tile rows, workgroups per CU, flags>, by default 208-row tiles (K
+ * split over up to 16 slabs) below 106k rows and 256-row tiles above, flags 4 (nt gallery loads); above 131k rows —
+ * several tiles per workgroup — flags 52: score tiles leave as whole row segments through LDS (32) with nt stores (16).
+ * GEMM routes: gemm_nt_kernel<...> / gemm_nt_fp8_kernel / gemm256_kernel<fp8, 10> (split-K for small shards). */
 const char* vpr_knn_scores_kernel_name(int is_fp8, int B, int N);
 /* Device pointer + leading dimension of the score matrix inside a workspace (for tests). */
 float* vpr_knn_scores_ptr(void* workspace, int B, int N, int D, int k, int* ld_out);

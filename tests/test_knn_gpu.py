@@ -539,6 +539,37 @@ def test_knn_staged_score_stores_equal_direct(dev, tune, B, N, D, fp8, variant):
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1]) and torch.equal(outs[0][2], outs[1][2])
 
 
+@pytest.mark.parametrize("B,N,D,fp8", [(33, 1003, 128, False), (64, 131, 128, True), (50, 120_001, 128, True),
+                                       (50, 150_001, 128, False), (33, 1003, 1024, False)])
+def test_knn_variants_equal_the_default(dev, tune, B, N, D, fp8):
+    """include/vpr_amd.h promises that VPR_KNN_VARIANT 1..7 only pick another tile height, residency, cache policy or
+    store path of the streaming score kernel: against the switch unset the score matrix, the values and the indices are
+    bit-identical.  Shapes: a ragged small shard, fewer rows than one tile, a tall-tile shard (N > 106 496 at 256 CUs:
+    256-row tiles) and a multi-tile one (N > 131 072: staged nt stores by default); the D = 1024 shard is wide enough
+    (16 K-steps) for the K split, which D = 128 never takes."""
+    from vpr_amd import ops
+    k = 5
+    if fp8:
+        q, qs = _fp8_rows(B, D, 93)
+        g, gs = _fp8_rows(N, D, 94)
+        args = (q.to(dev), qs.to(dev), g.to(dev), gs.to(dev), k, 0)
+        fn = ops.knn_topk_fp8
+    else:
+        args = (_unit_rows(B, D, 93).to(dev), _unit_rows(N, D, 94).to(dev), k, 0)
+        fn = ops.knn_topk
+    tune("VPR_KNN_GEMM_MIN_B", "100000")
+    outs = {}
+    for var in (None, 1, 2, 3, 4, 5, 6, 7):
+        tune("VPR_KNN_VARIANT", var)
+        ws = ops.knn_workspace(B, N, D, k, dev)
+        ws.zero_()
+        v, i = fn(*args, ws)
+        outs[var] = (ops.knn_scores_view(ws, B, N, D, k).clone(), v, i)
+    for var in range(1, 8):
+        for name, got, want in zip(("scores", "values", "indices"), outs[var], outs[None]):
+            assert torch.equal(got, want), (var, name)
+
+
 # ----------------------------------------------------------------- the error model behind the certificate
 @pytest.mark.parametrize("fp8", [False, True])
 @pytest.mark.parametrize("route,B,N", [("stream", 64, 120_000), ("stream K-split", 64, 3000), ("gemm128", 150, 3000),

@@ -182,6 +182,116 @@ def test_tuning_switches_are_read_once_at_load(lib, monkeypatch):
     assert lib.vpr_tuning_set(None, 1, 0) == -1
 
 
+def test_score_kernel_name_is_the_kernel_the_launch_code_picks(lib):
+    """vpr_knn_scores_kernel_name describes the call the way the score stage does.  Without a device the library counts
+    256 CUs (an MI355X), so 100k / 120k / 140k rows sit below, between and above the tall-tile (N > 106 496) and
+    multi-tile (N > 131 072) rules.  Every VPR_KNN_VARIANT of the release library, both operand types; then the GEMM
+    routes, whose names come from gemm_nt.hip / gemm256.hip."""
+    from vpr_amd import _lib
+    nt, staged, staged_nt = 4, 36, 52
+    by_shard = lambda flags: [(208, 2, flags), (256, 2, flags), (256, 2, flags)]
+    expected = {
+        None: [(208, 2, nt), (256, 2, nt), (256, 2, staged_nt)], 0: [(208, 2, nt), (256, 2, nt), (256, 2, staged_nt)],
+        1: [(208, 2, 0)] * 3, 2: [(144, 3, nt)] * 3, 3: [(256, 2, nt)] * 3, 4: [(208, 2, nt)] * 3,
+        5: by_shard(nt), 6: by_shard(staged), 7: by_shard(staged_nt),
+    }
+    switches = ("VPR_KNN_VARIANT", "VPR_KNN_GEMM_MIN_B", "VPR_KNN_GEMM_KSPLIT", "VPR_KNN_FP8_GEMM256", "VPR_GEMM_NT_STAGES")
+    before = {s: _lib.tuning_get(s) for s in switches}
+    try:
+        for s in switches:
+            _lib.tuning_set(s, None)
+        for variant, triples in expected.items():
+            _lib.tuning_set("VPR_KNN_VARIANT", variant)
+            for N, (rows, wgpc, flags) in zip((100_000, 120_000, 140_000), triples):
+                for fp8 in (0, 1):
+                    want = f"vpr::knn_scores_kernel<{'true' if fp8 else 'false'}, {rows}, {wgpc}, {flags}>"
+                    assert lib.vpr_knn_scores_kernel_name(fp8, 64, N).decode() == want, (variant, N, fp8)
+        _lib.tuning_set("VPR_KNN_VARIANT", None)
+        assert lib.vpr_knn_scores_kernel_name(0, 150, 3000) == b"vpr::gemm_nt_kernel<128, 2, 2, 2>"
+        _lib.tuning_set("VPR_GEMM_NT_STAGES", 3)
+        assert lib.vpr_knn_scores_kernel_name(0, 150, 3000) == b"vpr::gemm_nt_kernel<128, 2, 2, 3>"
+        assert lib.vpr_knn_scores_kernel_name(1, 150, 3000) == b"vpr::gemm_nt_fp8_kernel"       # the switch is bf16 only
+        _lib.tuning_set("VPR_GEMM_NT_STAGES", None)
+        assert lib.vpr_knn_scores_kernel_name(0, 150, 40) == b"vpr::gemm_nt_kernel<64, 4, 1, 2>"
+        assert lib.vpr_knn_scores_kernel_name(1, 150, 3000) == b"vpr::gemm_nt_fp8_kernel"
+        assert lib.vpr_knn_scores_kernel_name(0, 512, 6378) == b"vpr::gemm256_kernel<false, 10>"
+        assert lib.vpr_knn_scores_kernel_name(1, 512, 6378) == b"vpr::gemm256_kernel<true, 10>"
+        assert lib.vpr_knn_scores_kernel_name(0, 0, 1000) == b""
+    finally:
+        for s, v in before.items():
+            _lib.tuning_set(s, v)
+
+
+def test_knn_invalid_calls_keep_their_statuses(lib):
+    """One fault per call, every call refused before anything is launched: the status each kNN entry point answers.
+    The stage / one-call / exhaustive forms call a non-positive size an invalid argument (-1); vpr_knn_scores,
+    vpr_knn_select and vpr_knn_select_checked have always called it unsupported (-2).  Everything else agrees."""
+    raw = (ctypes.c_char * (1 << 20))()
+    base = (ctypes.addressof(raw) + 255) // 256 * 256
+    P = ctypes.c_void_p(base)                       # 256-byte aligned, stands in for every pointer
+    null, off2, WS = ctypes.c_void_p(0), ctypes.c_void_p(base + 2), 512 << 10
+    INVALID, UNSUPPORTED, WORKSPACE = -1, -2, -3
+
+    # call(name, **overrides): the base call B=1, N=10, k=1, D=64 (bf16) / 128 (fp8) with the given arguments replaced
+    def call(name, fp8=False, **kw):
+        a = dict(q=P, qs=P if fp8 else null, g=P, gs=P if fp8 else null, B=1, N=10, D=128 if fp8 else 64, k=1,
+                 val=P, idx=P, ws=P, bytes=WS, bound=1.002, status=null, unc=null)
+        a.update(kw)
+        shape, out, ws = (a["B"], a["N"], a["D"], a["k"]), (0, a["val"], a["idx"]), (a["ws"], a["bytes"])
+        cert = (a["bound"], a["status"], a["unc"])
+        bf16, f8, any_ = (a["q"], a["g"]), (a["q"], a["qs"], a["g"], a["gs"]), (a["q"], a["qs"], a["g"], a["gs"], int(fp8))
+        args = {
+            "vpr_knn_topk": bf16 + shape + out + ws, "vpr_knn_topk_checked": bf16 + shape + out + ws + cert,
+            "vpr_knn_topk_fp8": f8 + shape + out + ws, "vpr_knn_topk_fp8_checked": f8 + shape + out + ws + cert,
+            "vpr_knn_topk_scores_stage": any_ + shape + ws, "vpr_knn_topk_select_stage": any_ + shape + out + ws + cert,
+            "vpr_knn_topk_exhaustive": any_ + shape + out + ws,
+            "vpr_knn_scores": bf16 + shape[:3] + ws, "vpr_knn_select": bf16 + shape + out + ws,
+            "vpr_knn_select_checked": bf16 + shape + out + ws + cert,
+        }[name]
+        return getattr(lib, name)(*args, null)
+
+    bf16_new = ["vpr_knn_topk", "vpr_knn_topk_checked", "vpr_knn_topk_scores_stage", "vpr_knn_topk_select_stage",
+                "vpr_knn_topk_exhaustive"]
+    fp8_new = ["vpr_knn_topk_fp8", "vpr_knn_topk_fp8_checked", "vpr_knn_topk_scores_stage", "vpr_knn_topk_select_stage",
+               "vpr_knn_topk_exhaustive"]
+    old = ["vpr_knn_scores", "vpr_knn_select", "vpr_knn_select_checked"]
+    has_k = lambda n: n != "vpr_knn_scores"
+    has_out = lambda n: n not in ("vpr_knn_scores", "vpr_knn_topk_scores_stage")
+    seen = []
+
+    def expect(name, status, **kw):
+        got = call(name, **kw)
+        seen.append((name, kw, got, status))
+
+    for fp8, names in ((False, bf16_new + old), (True, fp8_new)):
+        for n in names:
+            bad_shape = UNSUPPORTED if n in old else INVALID
+            for dim in ("B", "N", "D", "k"):
+                for v in (0, -1):
+                    if dim != "k" or has_k(n):
+                        expect(n, bad_shape, fp8=fp8, **{dim: v})
+            if has_k(n):
+                expect(n, UNSUPPORTED, fp8=fp8, k=65)
+            for D in ((64, 192) if fp8 else (65, 100)):
+                expect(n, UNSUPPORTED, fp8=fp8, D=D)
+            if fp8:
+                expect(n, UNSUPPORTED, fp8=fp8, D=100)
+                expect(n, INVALID, fp8=fp8, qs=null)
+                expect(n, INVALID, fp8=fp8, gs=null)
+            for ptr in ("q", "g", "ws") + (("val", "idx") if has_out(n) else ()):
+                expect(n, INVALID, fp8=fp8, **{ptr: null})
+            expect(n, WORKSPACE, fp8=fp8, bytes=16)
+            expect(n, UNSUPPORTED, fp8=fp8, q=off2)
+            expect(n, UNSUPPORTED, fp8=fp8, g=off2)
+    for n in ("vpr_knn_select_checked", "vpr_knn_topk_select_stage"):
+        for bound in (0.0, -1.0):
+            expect(n, INVALID, bound=bound)
+            expect(n, INVALID, bound=bound, B=0)             # the bound is judged before the shape
+    wrong = [s for s in seen if s[2] != s[3]]
+    assert not wrong, wrong
+    assert len(seen) > 250
+
+
 def test_tuning_switches_come_from_the_environment_of_the_loading_process():
     """A fresh process with VPR_KNN_VARIANT=1 in its environment loads a library that reports 1 (and picks that kernel)."""
     import subprocess

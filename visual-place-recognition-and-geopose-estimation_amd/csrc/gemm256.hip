@@ -527,6 +527,15 @@ __global__ __launch_bounds__(512, 2) void gemm256_fuse2_kernel(GemmProblem pr, F
 
 constexpr size_t G2_LDS = 128 * (G2_BN * 4 + 16);   // >= the two K-tile buffers (128 KB); sized by the f32 epilogue staging
 
+const char* gemm256_kernel_name(bool fp8) {      // what launch_gemm256 (bf16) / launch_gemm256_fp8 launch
+  if (fp8) return "vpr::gemm256_kernel<true, 10>";
+#ifdef VPR_ABLATION
+  const int depth = tune_or(TUNE_GEMM256_DEPTH, 10);
+  if (depth == 6 || depth == 2) return depth == 6 ? "vpr::gemm256_kernel<false, 6>" : "vpr::gemm256_kernel<false, 2>";
+#endif
+  return "vpr::gemm256_kernel<false, 10>";
+}
+
 int launch_gemm256(const GemmProblem& in, hipStream_t stream) {
   GemmProblem g = in;
   if (!g.A || !g.W || !g.C || g.M <= 0 || g.N <= 0 || g.K <= 0) return VPR_ERR_INVALID_ARG;

@@ -302,6 +302,18 @@ static int gemm_check(const GemmProblem& g) {
   return VPR_OK;
 }
 
+// launch_gemm_nt's two decisions, shared with gemm_nt_kernel_name: 128-column tiles (else one 64-column tile), and the A/B
+// switch VPR_GEMM_NT_STAGES, 3 = three-deep ring (96 KB: one workgroup per CU).  Measured on the kNN score tile, 2 vs 3
+// stages: 128 x 50k 217 / 291 us, 512 x 12.5k 141 / 205 us — two workgroups per CU beat the deeper ring.
+static bool gemm_nt_wide(int N) { return N > 64; }
+static bool gemm_nt_three_stages() { return tune_or(TUNE_GEMM_NT_STAGES, 2) == 3; }
+
+const char* gemm_nt_kernel_name(bool fp8, int N) {
+  if (fp8) return "vpr::gemm_nt_fp8_kernel";
+  if (!gemm_nt_wide(N)) return "vpr::gemm_nt_kernel<64, 4, 1, 2>";
+  return gemm_nt_three_stages() ? "vpr::gemm_nt_kernel<128, 2, 2, 3>" : "vpr::gemm_nt_kernel<128, 2, 2, 2>";
+}
+
 int launch_gemm_nt(const uint16_t* A, int lda, int a_group_rows, long long a_group_stride,
                    const uint16_t* W, int ldw, const float* bias, int relu, void* C, int ldc,
                    int out_is_bf16, int M, int N, int K, hipStream_t stream) {
@@ -309,11 +321,9 @@ int launch_gemm_nt(const uint16_t* A, int lda, int a_group_rows, long long a_gro
   const int st = gemm_check(g);
   if (st != VPR_OK) return st;
   g.tiles_m = (M + 127) / 128;
-  if (N > 64) {
+  if (gemm_nt_wide(N)) {
     g.tiles_n = (N + 127) / 128;
-    // A/B switch: 3 = three-deep ring (96 KB: one workgroup per CU).  Measured on the kNN score tile, 2 vs 3
-    // stages: 128 x 50k 217 / 291 us, 512 x 12.5k 141 / 205 us — two workgroups per CU beat the deeper ring.
-    if (tune_or(TUNE_GEMM_NT_STAGES, 2) == 3) {
+    if (gemm_nt_three_stages()) {
       constexpr size_t lds3 = 3 * (128 + 128) * TILE_ROW_BYTES;
       static PerDeviceFlag attr = {};
       VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(gemm_nt_kernel<128, 2, 2, 3>), lds3, attr));

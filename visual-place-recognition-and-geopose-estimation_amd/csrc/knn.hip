@@ -980,31 +980,24 @@ static bool knn_plan(int B, int N, int D, int k, KnnPlan* p) {
   return true;
 }
 
-static int num_cus() { return device_cu_count(); }      // per device (vpr_internal.h)
-
 struct KnnOperands {          // bf16: scales are null; fp8: per-row f32 scales
   const void* q; const void* g; const float* q_scale; const float* g_scale; bool fp8;
 };
 
-static int knn_check(const KnnOperands& o, int D) {
-  if (!o.q || !o.g) return VPR_ERR_INVALID_ARG;
-  if (o.fp8 && (!o.q_scale || !o.g_scale)) return VPR_ERR_INVALID_ARG;
-  if (o.fp8 && (D % 128) != 0) return VPR_ERR_UNSUPPORTED;           // 128-B K-steps
-  if ((reinterpret_cast<uintptr_t>(o.q) | reinterpret_cast<uintptr_t>(o.g)) & 15) return VPR_ERR_UNSUPPORTED;
-  return VPR_OK;
-}
+// Where the select stage puts the answer and how it certifies it (status / uncertified may be null).
+struct KnnOutputs {
+  int index_base; float* val; int32_t* idx; float gallery_norm_bound; int32_t* status; int32_t* uncertified;
+};
 
-// rows per workgroup of the fully resident grid (2 per CU) above one 208-row tile
-static bool knn_tall_tiles(int N) {
-  const int slots = num_cus() * 2;
-  return (N + slots - 1) / slots > 208;
-}
+// f(std::true_type{}) for e4m3 operands, f(std::false_type{}) for bf16: o.fp8 as a template argument.
+template <typename F>
+static int knn_dispatch_fp8(bool fp8, F&& f) { return fp8 ? f(std::true_type{}) : f(std::false_type{}); }
 
-// more than one 256-row tile per workgroup of the resident grid (N > 131k rows)
-static bool knn_multi_tile(int N) {
-  const int slots = num_cus() * 2;
-  return (N + slots - 1) / slots > 256;
-}
+// rows per workgroup of the fully resident grid (2 per CU): above one 208-row tile (N > 106k rows at 256 CUs); more than
+// one 256-row tile (N > 131k rows)
+static int knn_rows_per_wg(int N) { return (N + device_cu_count() * 2 - 1) / (device_cu_count() * 2); }
+static bool knn_tall_tiles(int N) { return knn_rows_per_wg(N) > 208; }
+static bool knn_multi_tile(int N) { return knn_rows_per_wg(N) > 256; }
 
 // 256-row query tiles pay when at least 3/4 of their rows are real queries (256 gathered queries = 4 GPUs, 512 = 8 GPUs);
 // VPR_KNN_FP8_GEMM256=0 forces the 128 x 128 kernel (A/B).
@@ -1021,8 +1014,15 @@ static int knn_ksplit(const KnnPlan& p, int row_bytes) {
   return ks < 1 ? 1 : ks;
 }
 
-// Which kernel scores a [B] x [N] problem, and into how many K-slice slabs (the level-0 select adds them).  One rule,
-// used by the score stage, the select stage and vpr_knn_scores_kernel_name.
+// Which kernel scores a [B] x [N] problem, and into how many K-slice slabs (the level-0 select adds them).
+// More than one 64-query tile against a shard (the all-gathered batch of a multi-GPU job) moves towards a
+// compute-bound GEMM: the streaming kernel makes one gallery pass per 64 queries, the 128x128-tile MFMA GEMM one per
+// 128.  Measured, stream vs GEMM: 128 x 50k 367 / 222 us, 192 x 33k 406 / 300, 256 x 25k 477 / 185, 512 x 12.5k
+// 702 / 151 (scripts/knn_b_sweep.py).  >= 192 of every 256 gathered queries real (256 at 4 GPUs, 512 at 8): the
+// 256 x 256-tile kernel with its LDS-DMA stream kept in flight across barriers (gemm256.hip); a 128-query batch would
+// leave half of such a tile row empty.
+// ksplit_ok: the caller's select stage will add the slabs (vpr_knn_topk*); the stand-alone score entry point writes
+// the one score matrix its contract promises.
 enum KnnRoute { ROUTE_STREAM, ROUTE_GEMM128, ROUTE_GEMM256 };
 static KnnRoute knn_route(const KnnPlan& p, bool fp8, int B, int N, int D, bool ksplit_ok, int* nslab) {
   const int gemm_min_b = tune_or(TUNE_KNN_GEMM_MIN_B, 65);     // A/B switch for the stream / GEMM crossover
@@ -1043,119 +1043,166 @@ static KnnRoute knn_route(const KnnPlan& p, bool fp8, int B, int N, int D, bool 
   return ROUTE_GEMM256;
 }
 
-// ksplit_ok: the caller's select stage will add the slabs (vpr_knn_topk*); the stand-alone score entry point writes
-// the one score matrix its contract promises.
-int knn_scores(const KnnOperands& o, int B, int N, int D, void* ws, size_t ws_bytes, int k_for_plan,
-               hipStream_t stream, bool ksplit_ok = false) {
+// ---- the streaming score kernel: which instantiation --------------------------------------------------------------
+// Bits of knn_scores_kernel's fourth template argument.
+enum KnnStreamFlags {
+  // -DVPR_ABLATION builds only (timing: WRONG or no scores): no MFMA / no query staging after the first K-step; no score stores
+  KNN_ABL_ONE_KSTEP = 1, KNN_ABL_ONE_QSTAGE = 2, KNN_ABL_NO_STORES = 8,
+  KNN_NT_LOADS = 4,          // nt cache policy on the gallery stream (read once; keeps the query tile and the score matrix in
+                             // L2 / Infinity Cache): +4.6 % on the bare stream, +5.2 % on this kernel at 100k rows
+  KNN_NT_STORES = 16,        // nt policy on the score stores
+  KNN_STAGED_STORES = 32,    // the score tile leaves through the idle stage buffers as whole row segments
+};
+
+struct KnnStreamKernel { int rows, wgpc, flags; };      // tile rows, workgroups per CU, flag bits
+
+// VPR_KNN_VARIANT -> kernel.  0 is the shipped policy; 1..7 compute the same scores bit for bit and exist for A/B
+// tuning in one process:
+//   unset / 0   208-row tiles (13 row blocks, 2 workgroups per CU); 256 rows when knn_tall_tiles(N); staged + nt score
+//               stores when knn_multi_tile(N)
+//   1           (208, 2, 0)   default cache policy (round 1's kernel)
+//   2           (144, 3, nt)  the round-1 first cut: 9 row blocks, 3 workgroups per CU
+//   3           (256, 2, nt)  16 row blocks, all of the LDS, whatever the shard size
+//   4           (208, 2, nt)  13 row blocks whatever the shard size (A/B against the tall tiles)
+//   5 / 6 / 7   tile rows as 0, with direct / staged / staged + nt score stores forced
+//   11..14      -DVPR_ABLATION builds only (they skip work: WRONG scores, timing only): no MFMA / no query staging /
+//               neither after the first K-step; 14 = tile rows as 0, no score stores
+//   other       (208, 2, nt)
+// Tall tiles: shards whose workgroups own more than one 208-row tile (N > 106k) take 256-row tiles: 16 row blocks,
+// 2 x 80 KB = the whole 160 KB of LDS, fewer tiles and 20 % less query re-staging: +2.3 % at 500k bf16 rows, +1.4 % on the
+// 1M-row e4m3 call; a 125k-row shard becomes one 244-row tile per workgroup instead of two of 122 (scripts/knn_ab.py,
+// knn_ab_fp8.py).
+// Store path: shards whose workgroups own several tiles (N > 131k) write each tile's scores as whole row segments staged
+// through the idle stage buffers (one 1-KiB float4 store per query row, nt policy) instead of dword stores of four
+// 64-byte segments: the stores of a large shard cost far more than their 1.5-3 % share of the bytes (no-store ablation,
+// score stage: 1M e4m3 rows 1518 -> 1245 us, 500k bf16 1391 -> 1252, 125k e4m3 170 -> 159, 100k bf16 ~0).  Staged + nt:
+// 1M e4m3 1497 -> 1342 us, 500k bf16 1374 -> 1300, 250k bf16 668 -> 642; single-tile shards: no difference, they keep
+// the direct stores.
+static KnnStreamKernel knn_stream_kernel(int variant, int N) {
+  const int by_shard = knn_tall_tiles(N) ? 256 : 208;
+  switch (variant) {
+    case 0: return {by_shard, 2, KNN_NT_LOADS | (knn_multi_tile(N) ? KNN_STAGED_STORES | KNN_NT_STORES : 0)};
+    case 1: return {208, 2, 0};
+    case 2: return {144, 3, KNN_NT_LOADS};
+    case 3: return {256, 2, KNN_NT_LOADS};
+    case 5: return {by_shard, 2, KNN_NT_LOADS};
+    case 6: return {by_shard, 2, KNN_NT_LOADS | KNN_STAGED_STORES};
+    case 7: return {by_shard, 2, KNN_NT_LOADS | KNN_STAGED_STORES | KNN_NT_STORES};
+#ifdef VPR_ABLATION
+    case 11: return {208, 2, KNN_NT_LOADS | KNN_ABL_ONE_KSTEP};
+    case 12: return {208, 2, KNN_NT_LOADS | KNN_ABL_ONE_QSTAGE};
+    case 13: return {208, 2, KNN_NT_LOADS | KNN_ABL_ONE_KSTEP | KNN_ABL_ONE_QSTAGE};
+    case 14: return {by_shard, 2, KNN_NT_LOADS | KNN_ABL_NO_STORES};
+#endif
+    default: return {208, 2, KNN_NT_LOADS};             // 4, and every value without a meaning
+  }
+}
+
+// The instantiations that exist, each for both operand types: (tile rows, workgroups per CU, flags); 36 = nt loads +
+// staged stores, 52 = the same with nt stores.  The launch and the printed name both come from this list.
+#ifdef VPR_ABLATION     // timing-only kernels: never in the shipped library
+#define VPR_KNN_ABLATION_KERNELS(X) X(208, 2, 5) X(208, 2, 6) X(208, 2, 7) X(208, 2, 12) X(256, 2, 12)
+#else
+#define VPR_KNN_ABLATION_KERNELS(X)
+#endif
+#define VPR_KNN_STREAM_KERNELS(X)                                                                       \
+  X(208, 2, 4) X(256, 2, 4) X(144, 3, 4) X(208, 2, 0) X(208, 2, 36) X(208, 2, 52) X(256, 2, 36) X(256, 2, 52) \
+  VPR_KNN_ABLATION_KERNELS(X)
+
+struct KnnCall;
+struct KnnStreamEntry {
+  KnnStreamKernel k;
+  const char* name[2];      // [fp8], as a kernel trace prints it
+  int (*launch)(const KnnCall& c, dim3 grid, float* S, hipStream_t stream);
+};
+
+// One resolved description of a call: built once (knn_describe / knn_resolve), read by every stage.
+struct KnnCall {
+  KnnOperands o; char* ws; int B, N, D, k, row_bytes;
   KnnPlan p;
-  if (!ws) return VPR_ERR_INVALID_ARG;
-  if (!knn_plan(B, N, D, k_for_plan, &p)) return VPR_ERR_UNSUPPORTED;
-  const int st = knn_check(o, D);
-  if (st != VPR_OK) return st;
-  if (ws_bytes < p.total) return VPR_ERR_WORKSPACE;
-  float* S = reinterpret_cast<float*>(static_cast<char*>(ws) + p.off_S);
-  // More than one 64-query tile against a shard (the all-gathered batch of a multi-GPU job) moves
-  // towards a compute-bound GEMM: the streaming kernel makes one gallery pass per 64 queries, the
-  // 128x128-tile MFMA GEMM one per 128.  Measured, stream vs GEMM: 128 x 50k 367 / 222 us,
-  // 192 x 33k 406 / 300, 256 x 25k 477 / 185, 512 x 12.5k 702 / 151 (scripts/knn_b_sweep.py).
-  // >= 192 of every 256 gathered queries real (256 at 4 GPUs, 512 at 8): the 256 x 256-tile kernel with its LDS-DMA
-  // stream kept in flight across barriers (gemm256.hip); a 128-query batch would leave half of such a tile row empty.
-  int nslab = 1;
-  const KnnRoute route = knn_route(p, o.fp8, B, N, D, ksplit_ok, &nslab);
+  KnnRoute route;
+  int nslab;                       // score slabs the score stage writes and the level-0 select adds
+  const KnnStreamEntry* stream;    // ROUTE_STREAM: the kernel
+};
+
+template <int TR, int WGPC, int FLAGS>
+static int knn_launch_stream(const KnnCall& c, dim3 grid, float* S, hipStream_t stream) {
+  return knn_dispatch_fp8(c.o.fp8, [&](auto fp8) {
+    static PerDeviceFlag attr = {};                    // one per instantiation
+    const auto kernel = knn_scores_kernel<decltype(fp8)::value, TR, WGPC, FLAGS>;
+    constexpr size_t lds = (size_t)2 * (TR + KNN_QT) * TILE_ROW_BYTES;
+    if (lds > 65536) VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(kernel), lds, attr));
+    return launch_kernel(kernel, grid, dim3(256), lds, stream, c.o.q, c.o.g, c.o.q_scale, c.o.g_scale, S, c.B, c.N,
+                         c.row_bytes, c.p.ldS);
+  });
+}
+
+static const KnnStreamEntry* knn_stream_entry(const KnnStreamKernel& k) {
+  static const KnnStreamEntry table[] = {
+#define VPR_KNN_ENTRY(TR, W, A)                                                                         \
+    {{TR, W, A}, {"vpr::knn_scores_kernel<false, " #TR ", " #W ", " #A ">", "vpr::knn_scores_kernel<true, " #TR ", " #W ", " #A ">"}, \
+     knn_launch_stream<TR, W, A>},
+    VPR_KNN_STREAM_KERNELS(VPR_KNN_ENTRY)
+#undef VPR_KNN_ENTRY
+  };
+  for (const KnnStreamEntry& e : table)
+    if (e.k.rows == k.rows && e.k.wgpc == k.wgpc && e.k.flags == k.flags) return &e;
+  return nullptr;
+}
+
+// Plan, route, slab count and stream kernel of a [B] x [N] x [D] problem: everything that follows from the shape and the
+// tuning switches alone (vpr_knn_scores_kernel_name stops here).
+static int knn_describe(bool fp8, int B, int N, int D, int k, bool ksplit_ok, KnnCall* c) {
+  if (!knn_plan(B, N, D, k, &c->p)) return VPR_ERR_UNSUPPORTED;
+  c->B = B; c->N = N; c->D = D; c->k = k; c->row_bytes = fp8 ? D : D * 2;
+  c->route = knn_route(c->p, fp8, B, N, D, ksplit_ok, &c->nslab);
+  c->stream = c->route == ROUTE_STREAM ? knn_stream_entry(knn_stream_kernel(tune_or(TUNE_KNN_VARIANT, 0), N)) : nullptr;
+  return c->route == ROUTE_STREAM && !c->stream ? VPR_ERR_UNSUPPORTED : VPR_OK;      // outside the list: cannot happen
+}
+
+// The argument checks of every entry point, in one order, then the description.  out: null for a score-only call.
+// bad_shape: the status of a non-positive B, N, D or k — VPR_ERR_INVALID_ARG, except at vpr_knn_scores / vpr_knn_select
+// / vpr_knn_select_checked, which have always answered VPR_ERR_UNSUPPORTED (tests/test_library_cpu.py pins both).
+static int knn_resolve(const KnnOperands& o, int B, int N, int D, int k, void* ws, size_t ws_bytes, const KnnOutputs* out,
+                       bool ksplit_ok, int bad_shape, KnnCall* c) {
+  if (out && (!(out->gallery_norm_bound > 0.f) || !out->val || !out->idx)) return VPR_ERR_INVALID_ARG;
+  if (B <= 0 || N <= 0 || D <= 0 || k <= 0) return bad_shape;
+  if (!ws || !o.q || !o.g || (o.fp8 && (!o.q_scale || !o.g_scale))) return VPR_ERR_INVALID_ARG;
+  VPR_TRY_LAUNCH(knn_describe(o.fp8, B, N, D, k, ksplit_ok, c));
+  if (o.fp8 && (D % 128) != 0) return VPR_ERR_UNSUPPORTED;           // 128-B K-steps
+  if ((reinterpret_cast<uintptr_t>(o.q) | reinterpret_cast<uintptr_t>(o.g)) & 15) return VPR_ERR_UNSUPPORTED;
+  if (ws_bytes < c->p.total) return VPR_ERR_WORKSPACE;
+  c->o = o; c->ws = static_cast<char*>(ws);
+  return VPR_OK;
+}
+
+// Score stage: S[b, n] = <q_b, g_n> into the workspace, c.nslab K-slice slabs of [B][ldS] f32.
+static int knn_scores(const KnnCall& c, hipStream_t stream) {
+  const KnnOperands& o = c.o; const KnnPlan& p = c.p;
+  const int B = c.B, N = c.N, D = c.D;
+  float* S = reinterpret_cast<float*>(c.ws + p.off_S);
   const long long slab_stride = (long long)B * p.ldS;
-  if (route == ROUTE_GEMM256 && o.fp8)
+  if (c.route == ROUTE_GEMM256 && o.fp8)
     return launch_gemm256_fp8(static_cast<const uint8_t*>(o.q), D, o.q_scale, static_cast<const uint8_t*>(o.g), D,
-                              o.g_scale, S, p.ldS, B, N, D, stream, nslab, slab_stride);
-  if (route == ROUTE_GEMM128 && o.fp8)      // block-scaled fp8 MFMA GEMM (twice the bf16 rate), scales in its epilogue
+                              o.g_scale, S, p.ldS, B, N, D, stream, c.nslab, slab_stride);
+  if (c.route == ROUTE_GEMM128 && o.fp8)      // block-scaled fp8 MFMA GEMM (twice the bf16 rate), scales in its epilogue
     return launch_gemm_nt_fp8(static_cast<const uint8_t*>(o.q), D, o.q_scale, static_cast<const uint8_t*>(o.g), D,
                               o.g_scale, S, p.ldS, B, N, D, stream);
-  if (route == ROUTE_GEMM256) {
+  if (c.route == ROUTE_GEMM256) {
     GemmProblem g{static_cast<const uint16_t*>(o.q), D, 0, 0, static_cast<const uint16_t*>(o.g), D, nullptr, 0,
                   S, p.ldS, 0, B, N, D, 0, 0};
-    g.ksplit = nslab; g.slab_stride = slab_stride;
+    g.ksplit = c.nslab; g.slab_stride = slab_stride;
     return launch_gemm256(g, stream);
   }
-  if (route == ROUTE_GEMM128)
+  if (c.route == ROUTE_GEMM128)
     return launch_gemm_nt(static_cast<const uint16_t*>(o.q), D, 0, 0, static_cast<const uint16_t*>(o.g), D, nullptr,
                           0, S, p.ldS, 0, B, N, D, stream);
-  // Tile height / residency / cache-policy variants (same arithmetic, same results); 0 is the default, the
-  // others exist for A/B tuning in one process (VPR_KNN_VARIANT).  The ablation variants of round 1 (11-13: they
-  // skip work and return wrong scores) are compiled only with -DVPR_ABLATION.
-  const int variant = tune_or(TUNE_KNN_VARIANT, 0);
-  int tr = 208, wgpc = 2;                         // default: 13 row blocks, 2 workgroups per CU
-  if (variant == 2) { tr = 144; wgpc = 3; }
-  // Shards whose workgroups own more than one 208-row tile (N > 106k) take 256-row tiles: 16 row blocks, 2 x 80 KB = the
-  // whole 160 KB of LDS, fewer tiles and 20 % less query re-staging: +2.3 % at 500k bf16 rows, +1.4 % on the 1M-row e4m3
-  // call; a 125k-row shard becomes one 244-row tile per workgroup instead of two of 122 (scripts/knn_ab.py, knn_ab_fp8.py).
-  if (variant == 3 || ((variant == 0 || (variant >= 5 && variant <= 7) || variant == 14) && knn_tall_tiles(N))) { tr = 256; wgpc = 2; }
-  // Score-store path.  Shards whose workgroups own several tiles (N > 131k) write each tile's scores as whole row
-  // segments staged through the idle stage buffers (one 1-KiB float4 store per query row, nt policy) instead of dword
-  // stores of four 64-byte segments: the stores of a large shard cost far more than their 1.5-3 % share of the bytes
-  // (no-store ablation, score stage: 1M e4m3 rows 1518 -> 1245 us, 500k bf16 1391 -> 1252, 125k e4m3 170 -> 159,
-  // 100k bf16 ~0).  Staged + nt: 1M e4m3 1497 -> 1342 us, 500k bf16 1374 -> 1300, 250k bf16 668 -> 642; single-tile
-  // shards: no difference, they keep the direct stores.  Variants 5 / 6 / 7 force direct / staged / staged + nt.
-  const bool staged = variant == 6 || variant == 7 || (variant == 0 && knn_multi_tile(N));
-  const bool staged_nt = variant != 6;
-  const int slots = num_cus() * wgpc;
-  // Fully resident, balanced grid; never more workgroups than 16-row blocks of gallery.
-  int nwg = slots;
+  // Streaming kernel.  Fully resident, balanced grid; never more workgroups than 16-row blocks of gallery.
+  int nwg = device_cu_count() * c.stream->k.wgpc;
   const int max_useful = (N + 15) / 16;
   if (nwg > max_useful) nwg = max_useful;
-  const size_t lds = (size_t)2 * (tr + KNN_QT) * TILE_ROW_BYTES;
-  const int rb = o.fp8 ? D : D * 2;
-  const int ksplit = nslab;
-  if (ksplit > 1) nwg = p.nrt;                    // tall tiles: the K split supplies the parallelism
-  const dim3 grid(nwg, p.Bpad / KNN_QT, ksplit);
-#define VPR_KNN_LAUNCH(F8, TR, W, A)                                                                   \
-  do {                                                                                                 \
-    static PerDeviceFlag attr = {};                                                                    \
-    if (lds > 65536)                                                                                   \
-      VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(knn_scores_kernel<F8, TR, W, A>), lds, attr)); \
-    VPR_TRY_LAUNCH(launch_kernel(knn_scores_kernel<F8, TR, W, A>, grid, dim3(256), lds, stream, o.q, o.g, \
-                                 o.q_scale, o.g_scale, S, B, N, rb, p.ldS));                           \
-  } while (0)
-  // ABL bit 2 (value 4) = nt cache policy on the gallery stream (read once; keeps the query tile and the score
-  // matrix in L2 / Infinity Cache): +4.6 % on the bare stream, +5.2 % on this kernel at 100k rows.
-  if (staged) {                                   // 4 | 32 (| 16)
-#define VPR_KNN_STAGED(F8)                                                                           \
-    do {                                                                                               \
-      if (tr == 256) { if (staged_nt) VPR_KNN_LAUNCH(F8, 256, 2, 52); else VPR_KNN_LAUNCH(F8, 256, 2, 36); } \
-      else { if (staged_nt) VPR_KNN_LAUNCH(F8, 208, 2, 52); else VPR_KNN_LAUNCH(F8, 208, 2, 36); }          \
-    } while (0)
-    if (o.fp8) VPR_KNN_STAGED(true); else VPR_KNN_STAGED(false);
-#undef VPR_KNN_STAGED
-    return VPR_OK;
-  }
-#ifdef VPR_ABLATION
-  if (variant == 14) {                            // timing only: no score stores
-    if (o.fp8) { if (tr == 256) VPR_KNN_LAUNCH(true, 256, 2, 12); else VPR_KNN_LAUNCH(true, 208, 2, 12); }
-    else { if (tr == 256) VPR_KNN_LAUNCH(false, 256, 2, 12); else VPR_KNN_LAUNCH(false, 208, 2, 12); }
-    return VPR_OK;
-  }
-#endif
-  if (o.fp8) {
-    if (variant == 2) VPR_KNN_LAUNCH(true, 144, 3, 4);
-    else if (tr == 256) VPR_KNN_LAUNCH(true, 256, 2, 4);
-    else if (variant == 1) VPR_KNN_LAUNCH(true, 208, 2, 0);
-    else VPR_KNN_LAUNCH(true, 208, 2, 4);
-  } else {
-    switch (variant) {
-      case 1: VPR_KNN_LAUNCH(false, 208, 2, 0); break;    // default cache policy (round 1's kernel)
-      case 2: VPR_KNN_LAUNCH(false, 144, 3, 4); break;    // the round-1 first cut: 9 blocks, 3 per CU
-      case 3: VPR_KNN_LAUNCH(false, 256, 2, 4); break;    // 16 blocks, all of the LDS
-      case 4: VPR_KNN_LAUNCH(false, 208, 2, 4); break;    // 13 blocks whatever the shard size (A/B against the tall tiles)
-#ifdef VPR_ABLATION     // timing-only builds (WRONG scores): never in the shipped library
-      case 11: VPR_KNN_LAUNCH(false, 208, 2, 5); break;   // ablation: no MFMA after the first K-step
-      case 12: VPR_KNN_LAUNCH(false, 208, 2, 6); break;   // ablation: no query staging after the first K-step
-      case 13: VPR_KNN_LAUNCH(false, 208, 2, 7); break;   // ablation: both (pure gallery stream + barriers)
-#endif
-      default:
-        if (tr == 256) VPR_KNN_LAUNCH(false, 256, 2, 4); else VPR_KNN_LAUNCH(false, 208, 2, 4);
-        break;
-    }
-  }
-#undef VPR_KNN_LAUNCH
-  return VPR_OK;
+  if (c.nslab > 1) nwg = p.nrt;                   // tall tiles: the K split supplies the parallelism
+  return c.stream->launch(c, dim3(nwg, p.Bpad / KNN_QT, c.nslab), S, stream);
 }
 
 // Default norm bounds of the unchecked entry points: L2-normalised descriptors.  A bf16-rounded unit vector has norm
@@ -1170,41 +1217,27 @@ static float knn_err_rel(int D, float gallery_norm_bound) {
   return 1.1f * (float)D * 5.9604645e-8f * gallery_norm_bound;
 }
 
-int knn_select(const KnnOperands& o, int B, int N, int D, int k, int index_base, float* out_val,
-               int32_t* out_idx, void* ws, size_t ws_bytes, hipStream_t stream,
-               float gallery_norm_bound = NORM_BOUND_BF16, int32_t* status = nullptr, int32_t* uncertified = nullptr,
-               bool ksplit_scores = false) {
-  if (!(gallery_norm_bound > 0.f)) return VPR_ERR_INVALID_ARG;
-  const float err_rel = knn_err_rel(D, gallery_norm_bound);
-  KnnPlan p;
-  if (!ws || !out_val || !out_idx) return VPR_ERR_INVALID_ARG;
-  if (!knn_plan(B, N, D, k, &p)) return VPR_ERR_UNSUPPORTED;
-  const int st = knn_check(o, D);
-  if (st != VPR_OK) return st;
-  if (ws_bytes < p.total) return VPR_ERR_WORKSPACE;
-  char* w = static_cast<char*>(ws);
-  const float* cur_v = reinterpret_cast<float*>(w + p.off_S);
+// Select stage: adds the c.nslab score slabs the score stage of this call left, selects, rescores exactly, orders.
+static int knn_select(const KnnCall& c, const KnnOutputs& out, hipStream_t stream) {
+  const KnnOperands& o = c.o; const KnnPlan& p = c.p;
+  const int B = c.B, N = c.N, k = c.k, rb = c.row_bytes;
+  const float err_rel = knn_err_rel(c.D, out.gallery_norm_bound);
+  const float* cur_v = reinterpret_cast<float*>(c.ws + p.off_S);
   const int32_t* cur_i = nullptr;
   long long ld = p.ldS;
   int L = N;
-  const int rb = o.fp8 ? D : D * 2;
-  // slabs to add: whatever the score stage of this problem wrote
-  int nslab = 1;
-  knn_route(p, o.fp8, B, N, D, ksplit_scores, &nslab);
   const long long slab_stride = (long long)B * p.ldS;
+  // the fused final kernel takes over as soon as the candidates of a query fit one workgroup
+  // (its LDS = 36 KB of select state + the query row, kept under the 64 KB default limit)
+  const auto fits_fused = [&](int lev) { return lev > 0 && L <= SEL_CAP && (size_t)rb <= 24 * 1024; };
   int lev = 0;
-  for (; lev < p.nlevel; ++lev) {
-    // the fused final kernel takes over as soon as the candidates of a query fit one workgroup
-    // (its LDS = 36 KB of select state + the query row, kept under the 64 KB default limit)
-    if (lev > 0 && L <= SEL_CAP && (size_t)rb <= 24 * 1024) break;
-    float* ov = reinterpret_cast<float*>(w + p.off_cv[lev & 1]);
-    int32_t* oi = reinterpret_cast<int32_t*>(w + p.off_ci[lev & 1]);
-    if (lev == 0 && p.kp <= 32)
-      VPR_TRY_LAUNCH(launch_kernel(knn_select_stream_kernel<1024>, dim3(p.nchunk[0], B), dim3(256), 0, stream,
-                                   cur_v, N, ld, p.ch0, ov, oi, p.kp, p.nchunk[0], nslab, slab_stride));
-    else if (lev == 0)
-      VPR_TRY_LAUNCH(launch_kernel(knn_select_stream_kernel<4096>, dim3(p.nchunk[0], B), dim3(256), 0, stream,
-                                   cur_v, N, ld, p.ch0, ov, oi, p.kp, p.nchunk[0], nslab, slab_stride));
+  for (; lev < p.nlevel && !fits_fused(lev); ++lev) {
+    float* ov = reinterpret_cast<float*>(c.ws + p.off_cv[lev & 1]);
+    int32_t* oi = reinterpret_cast<int32_t*>(c.ws + p.off_ci[lev & 1]);
+    if (lev == 0)
+      VPR_TRY_LAUNCH(launch_kernel(p.kp <= 32 ? knn_select_stream_kernel<1024> : knn_select_stream_kernel<4096>,
+                                   dim3(p.nchunk[0], B), dim3(256), 0, stream, cur_v, N, ld, p.ch0, ov, oi, p.kp,
+                                   p.nchunk[0], c.nslab, slab_stride));
     else
       VPR_TRY_LAUNCH(launch_kernel(knn_select_kernel, dim3(p.nchunk[lev], B), dim3(256), 0, stream,
                                    cur_v, cur_i, L, ld, ov, oi, p.kp, p.nchunk[lev]));
@@ -1212,30 +1245,23 @@ int knn_select(const KnnOperands& o, int B, int N, int D, int k, int index_base,
     L = p.nchunk[lev] * p.kp;
     ld = L;
   }
-  if (lev > 0 && L <= SEL_CAP && (size_t)rb <= 24 * 1024) {
+  if (fits_fused(lev)) {
     const int level0 = lev == 1 ? 1 : 0;       // the lists in hand are level 0's [nchunk][kp] rank-ordered lists
-    if (o.fp8)
-      VPR_TRY_LAUNCH(launch_kernel(knn_final_fused_kernel<true>, dim3(B), dim3(FF_NT), (size_t)rb, stream, cur_v,
-                                   cur_i, L, o.q, o.g, o.q_scale, o.g_scale, rb, k, p.kp, index_base, out_val, out_idx,
-                                   err_rel, level0, status, uncertified));
-    else
-      VPR_TRY_LAUNCH(launch_kernel(knn_final_fused_kernel<false>, dim3(B), dim3(FF_NT), (size_t)rb, stream, cur_v,
-                                   cur_i, L, o.q, o.g, o.q_scale, o.g_scale, rb, k, p.kp, index_base, out_val, out_idx,
-                                   err_rel, level0, status, uncertified));
-    return VPR_OK;
+    return knn_dispatch_fp8(o.fp8, [&](auto fp8) {
+      return launch_kernel(knn_final_fused_kernel<decltype(fp8)::value>, dim3(B), dim3(FF_NT), (size_t)rb, stream, cur_v,
+                           cur_i, L, o.q, o.g, o.q_scale, o.g_scale, rb, k, p.kp, out.index_base, out.val, out.idx,
+                           err_rel, level0, out.status, out.uncertified);
+    });
   }
   // general path: the last select level left the [B][kp] list; rescore and order it
-  float* exact = reinterpret_cast<float*>(w + p.off_cv[p.nlevel & 1]);
-  float* qn = reinterpret_cast<float*>(w + p.off_qn);
-  if (o.fp8)
-    VPR_TRY_LAUNCH(launch_kernel(knn_rescore_kernel<true>, dim3(p.kp, B), dim3(256), 0, stream, cur_i, o.q, o.g,
-                                 o.q_scale, o.g_scale, D, p.kp, exact, qn));
-  else
-    VPR_TRY_LAUNCH(launch_kernel(knn_rescore_kernel<false>, dim3(p.kp, B), dim3(256), 0, stream, cur_i, o.q, o.g,
-                                 o.q_scale, o.g_scale, D * 2, p.kp, exact, qn));
-  VPR_TRY_LAUNCH(launch_kernel(knn_order_kernel, dim3(B), dim3(128), 0, stream, cur_i, exact, k, p.kp,
-                               index_base, out_val, out_idx, cur_v, qn, err_rel, status, uncertified));
-  return VPR_OK;
+  float* exact = reinterpret_cast<float*>(c.ws + p.off_cv[p.nlevel & 1]);
+  float* qn = reinterpret_cast<float*>(c.ws + p.off_qn);
+  VPR_TRY_LAUNCH(knn_dispatch_fp8(o.fp8, [&](auto fp8) {
+    return launch_kernel(knn_rescore_kernel<decltype(fp8)::value>, dim3(p.kp, B), dim3(256), 0, stream, cur_i, o.q, o.g,
+                         o.q_scale, o.g_scale, rb, p.kp, exact, qn);
+  }));
+  return launch_kernel(knn_order_kernel, dim3(B), dim3(128), 0, stream, cur_i, exact, k, p.kp, out.index_base, out.val,
+                       out.idx, cur_v, qn, err_rel, out.status, out.uncertified);
 }
 
 // Per-row symmetric quantisation to OCP e4m3: scale = max|x| / 448 (1 for an all-zero row),
@@ -1274,24 +1300,14 @@ extern "C" size_t vpr_knn_workspace_bytes(int B, int N, int D, int k) {
 }
 
 extern "C" const char* vpr_knn_scores_kernel_name(int is_fp8, int B, int N) {
-  // the dispatch of vpr_knn_topk* (knn_route) at the descriptor width of the path, D = 8448: what a kernel trace
-  // (rocprofv3) will show for this call
-  KnnPlan p;
-  if (!knn_plan(B, N, 8448, 10, &p)) return "";
-  int nslab = 1;
-  const KnnRoute route = knn_route(p, is_fp8 != 0, B, N, 8448, true, &nslab);
-  if (route == ROUTE_GEMM256) return is_fp8 ? "vpr::gemm256_kernel<true, 10>" : "vpr::gemm256_kernel<false, 10>";     // (names as rocprofv3 prints them)
-  if (route == ROUTE_GEMM128) return is_fp8 ? "vpr::gemm_nt_fp8_kernel" : "vpr::gemm_nt_kernel<128, 2, 2, 2>";
-  const int variant = tune_or(TUNE_KNN_VARIANT, 0);
-  const bool tall = variant == 3 || (variant == 0 && knn_tall_tiles(N));
-  if (variant == 0 && knn_multi_tile(N))
-    return is_fp8 ? "vpr::knn_scores_kernel<true, 256, 2, 52>" : "vpr::knn_scores_kernel<false, 256, 2, 52>";
-  if (is_fp8) {
-    return variant == 2 ? "vpr::knn_scores_kernel<true, 144, 3, 4>" : tall ? "vpr::knn_scores_kernel<true, 256, 2, 4>"
-         : variant == 1 ? "vpr::knn_scores_kernel<true, 208, 2, 0>" : "vpr::knn_scores_kernel<true, 208, 2, 4>";
-  }
-  return variant == 2 ? "vpr::knn_scores_kernel<false, 144, 3, 4>" : tall ? "vpr::knn_scores_kernel<false, 256, 2, 4>"
-       : variant == 1 ? "vpr::knn_scores_kernel<false, 208, 2, 0>" : "vpr::knn_scores_kernel<false, 208, 2, 4>";
+  // the score stage of vpr_knn_topk* at the descriptor width of the path, D = 8448, described exactly as a call
+  // describes it: what a kernel trace (rocprofv3) will show for this call
+  const bool fp8 = is_fp8 != 0;
+  KnnCall c;
+  if (knn_describe(fp8, B, N, 8448, 10, true, &c) != VPR_OK) return "";
+  if (c.route == ROUTE_GEMM256) return gemm256_kernel_name(fp8);
+  if (c.route == ROUTE_GEMM128) return gemm_nt_kernel_name(fp8, N);
+  return c.stream->name[fp8];
 }
 
 extern "C" float* vpr_knn_scores_ptr(void* workspace, int B, int N, int D, int k, int* ld_out) {
@@ -1301,52 +1317,48 @@ extern "C" float* vpr_knn_scores_ptr(void* workspace, int B, int N, int D, int k
   return reinterpret_cast<float*>(static_cast<char*>(workspace) + p.off_S);
 }
 
-extern "C" int vpr_knn_scores(const uint16_t* q, const uint16_t* gallery, int B, int N, int D,
-                              void* workspace, size_t workspace_bytes, void* stream) {
-  // The plan's score-matrix offset does not depend on k; size checks use the caller's bytes.
-  const KnnOperands o{q, gallery, nullptr, nullptr, false};
-  return knn_scores(o, B, N, D, workspace, workspace_bytes, 1, static_cast<hipStream_t>(stream));
+// Every entry point but the exhaustive one: resolve the call once and run the stages asked for on that one description,
+// so the select adds exactly the slabs the score stage wrote.  out == null: score stage only; scores == false: select
+// stage only, on what a score stage of the same call (ksplit_ok: same value) left in the workspace.
+static int knn_run(const KnnOperands& o, int B, int N, int D, int k, bool scores, const KnnOutputs* out, void* workspace,
+                   size_t workspace_bytes, void* stream, bool ksplit_ok, int bad_shape) {
+  KnnCall c;
+  VPR_TRY_LAUNCH(knn_resolve(o, B, N, D, k, workspace, workspace_bytes, out, ksplit_ok, bad_shape, &c));
+  if (scores) VPR_TRY_LAUNCH(knn_scores(c, static_cast<hipStream_t>(stream)));
+  return out ? knn_select(c, *out, static_cast<hipStream_t>(stream)) : VPR_OK;
 }
 
-extern "C" int vpr_knn_select(const uint16_t* q, const uint16_t* gallery, int B, int N, int D, int k,
-                              int index_base, float* out_val, int32_t* out_idx, void* workspace,
-                              size_t workspace_bytes, void* stream) {
-  const KnnOperands o{q, gallery, nullptr, nullptr, false};
-  return knn_select(o, B, N, D, k, index_base, out_val, out_idx, workspace, workspace_bytes,
-                    static_cast<hipStream_t>(stream));
+// The stand-alone stages: one plain score matrix (no K-split).  The plan's score-matrix offset does not depend on k.
+extern "C" int vpr_knn_scores(const uint16_t* q, const uint16_t* gallery, int B, int N, int D,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+  return knn_run({q, gallery, nullptr, nullptr, false}, B, N, D, 1, true, nullptr, workspace, workspace_bytes, stream,
+                 false, VPR_ERR_UNSUPPORTED);
 }
 
 extern "C" int vpr_knn_select_checked(const uint16_t* q, const uint16_t* gallery, int B, int N, int D, int k,
                                       int index_base, float* out_val, int32_t* out_idx, void* workspace,
                                       size_t workspace_bytes, float gallery_norm_bound, int32_t* status,
                                       int32_t* uncertified, void* stream) {
-  const KnnOperands o{q, gallery, nullptr, nullptr, false};
-  return knn_select(o, B, N, D, k, index_base, out_val, out_idx, workspace, workspace_bytes,
-                    static_cast<hipStream_t>(stream), gallery_norm_bound, status, uncertified);
+  const KnnOutputs out{index_base, out_val, out_idx, gallery_norm_bound, status, uncertified};
+  return knn_run({q, gallery, nullptr, nullptr, false}, B, N, D, k, false, &out, workspace, workspace_bytes, stream,
+                 false, VPR_ERR_UNSUPPORTED);
 }
 
-static int knn_topk_any(const KnnOperands& o, int B, int N, int D, int k, int index_base, float* out_val,
-                        int32_t* out_idx, void* workspace, size_t workspace_bytes, void* stream,
-                        float gallery_norm_bound, int32_t* status, int32_t* uncertified) {
-  KnnPlan p;
-  if (B <= 0 || N <= 0 || D <= 0 || k <= 0) return VPR_ERR_INVALID_ARG;
-  if (!knn_plan(B, N, D, k, &p)) return VPR_ERR_UNSUPPORTED;
-  if (workspace_bytes < p.total) return VPR_ERR_WORKSPACE;
-  const int st = knn_scores(o, B, N, D, workspace, workspace_bytes, k, static_cast<hipStream_t>(stream), true);
-  if (st != VPR_OK) return st;
-  return knn_select(o, B, N, D, k, index_base, out_val, out_idx, workspace, workspace_bytes,
-                    static_cast<hipStream_t>(stream), gallery_norm_bound, status, uncertified, true);
+extern "C" int vpr_knn_select(const uint16_t* q, const uint16_t* gallery, int B, int N, int D, int k,
+                              int index_base, float* out_val, int32_t* out_idx, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  return vpr_knn_select_checked(q, gallery, B, N, D, k, index_base, out_val, out_idx, workspace, workspace_bytes,
+                                NORM_BOUND_BF16, nullptr, nullptr, stream);
 }
 
 // The two halves of vpr_knn_topk[_fp8]_checked as separate calls (same kernels, same workspace contents in between:
 // the score stage may leave K-slice slabs that only this select stage knows to add), for callers that put events or
-// other stream work between the HBM-bound score stage and the latency-bound tail.
+// other stream work between the HBM-bound score stage and the latency-bound tail.  Each resolves the call on its own.
 extern "C" int vpr_knn_topk_scores_stage(const void* q, const float* q_scale, const void* gallery,
                                          const float* gallery_scale, int is_fp8, int B, int N, int D, int k,
                                          void* workspace, size_t workspace_bytes, void* stream) {
-  if (B <= 0 || N <= 0 || D <= 0 || k <= 0) return VPR_ERR_INVALID_ARG;
-  const KnnOperands o{q, gallery, q_scale, gallery_scale, is_fp8 != 0};
-  return knn_scores(o, B, N, D, workspace, workspace_bytes, k, static_cast<hipStream_t>(stream), true);
+  return knn_run({q, gallery, q_scale, gallery_scale, is_fp8 != 0}, B, N, D, k, true, nullptr, workspace,
+                 workspace_bytes, stream, true, VPR_ERR_INVALID_ARG);
 }
 
 extern "C" int vpr_knn_topk_select_stage(const void* q, const float* q_scale, const void* gallery,
@@ -1354,36 +1366,25 @@ extern "C" int vpr_knn_topk_select_stage(const void* q, const float* q_scale, co
                                          int index_base, float* out_val, int32_t* out_idx, void* workspace,
                                          size_t workspace_bytes, float gallery_norm_bound, int32_t* status,
                                          int32_t* uncertified, void* stream) {
-  if (B <= 0 || N <= 0 || D <= 0 || k <= 0) return VPR_ERR_INVALID_ARG;
-  const KnnOperands o{q, gallery, q_scale, gallery_scale, is_fp8 != 0};
-  return knn_select(o, B, N, D, k, index_base, out_val, out_idx, workspace, workspace_bytes,
-                    static_cast<hipStream_t>(stream), gallery_norm_bound, status, uncertified, true);
-}
-
-extern "C" int vpr_knn_topk(const uint16_t* q, const uint16_t* gallery, int B, int N, int D, int k,
-                            int index_base, float* out_val, int32_t* out_idx, void* workspace,
-                            size_t workspace_bytes, void* stream) {
-  const KnnOperands o{q, gallery, nullptr, nullptr, false};
-  return knn_topk_any(o, B, N, D, k, index_base, out_val, out_idx, workspace, workspace_bytes, stream,
-                      NORM_BOUND_BF16, nullptr, nullptr);
+  const KnnOutputs out{index_base, out_val, out_idx, gallery_norm_bound, status, uncertified};
+  return knn_run({q, gallery, q_scale, gallery_scale, is_fp8 != 0}, B, N, D, k, false, &out, workspace,
+                 workspace_bytes, stream, true, VPR_ERR_INVALID_ARG);
 }
 
 extern "C" int vpr_knn_topk_checked(const uint16_t* q, const uint16_t* gallery, int B, int N, int D, int k,
                                     int index_base, float* out_val, int32_t* out_idx, void* workspace,
                                     size_t workspace_bytes, float gallery_norm_bound, int32_t* status,
                                     int32_t* uncertified, void* stream) {
-  const KnnOperands o{q, gallery, nullptr, nullptr, false};
-  return knn_topk_any(o, B, N, D, k, index_base, out_val, out_idx, workspace, workspace_bytes, stream,
-                      gallery_norm_bound, status, uncertified);
+  const KnnOutputs out{index_base, out_val, out_idx, gallery_norm_bound, status, uncertified};
+  return knn_run({q, gallery, nullptr, nullptr, false}, B, N, D, k, true, &out, workspace, workspace_bytes, stream,
+                 true, VPR_ERR_INVALID_ARG);
 }
 
-extern "C" int vpr_knn_topk_fp8(const uint8_t* q, const float* q_scale, const uint8_t* gallery,
-                                const float* gallery_scale, int B, int N, int D, int k, int index_base,
-                                float* out_val, int32_t* out_idx, void* workspace, size_t workspace_bytes,
-                                void* stream) {
-  const KnnOperands o{q, gallery, q_scale, gallery_scale, true};
-  return knn_topk_any(o, B, N, D, k, index_base, out_val, out_idx, workspace, workspace_bytes, stream,
-                      NORM_BOUND_FP8, nullptr, nullptr);
+extern "C" int vpr_knn_topk(const uint16_t* q, const uint16_t* gallery, int B, int N, int D, int k,
+                            int index_base, float* out_val, int32_t* out_idx, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  return vpr_knn_topk_checked(q, gallery, B, N, D, k, index_base, out_val, out_idx, workspace, workspace_bytes,
+                              NORM_BOUND_BF16, nullptr, nullptr, stream);
 }
 
 extern "C" int vpr_knn_topk_fp8_checked(const uint8_t* q, const float* q_scale, const uint8_t* gallery,
@@ -1391,35 +1392,36 @@ extern "C" int vpr_knn_topk_fp8_checked(const uint8_t* q, const float* q_scale, 
                                         float* out_val, int32_t* out_idx, void* workspace, size_t workspace_bytes,
                                         float gallery_norm_bound, int32_t* status, int32_t* uncertified,
                                         void* stream) {
-  const KnnOperands o{q, gallery, q_scale, gallery_scale, true};
-  return knn_topk_any(o, B, N, D, k, index_base, out_val, out_idx, workspace, workspace_bytes, stream,
-                      gallery_norm_bound, status, uncertified);
+  const KnnOutputs out{index_base, out_val, out_idx, gallery_norm_bound, status, uncertified};
+  return knn_run({q, gallery, q_scale, gallery_scale, true}, B, N, D, k, true, &out, workspace, workspace_bytes, stream,
+                 true, VPR_ERR_INVALID_ARG);
+}
+
+extern "C" int vpr_knn_topk_fp8(const uint8_t* q, const float* q_scale, const uint8_t* gallery,
+                                const float* gallery_scale, int B, int N, int D, int k, int index_base,
+                                float* out_val, int32_t* out_idx, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+  return vpr_knn_topk_fp8_checked(q, q_scale, gallery, gallery_scale, B, N, D, k, index_base, out_val, out_idx, workspace,
+                                  workspace_bytes, NORM_BOUND_FP8, nullptr, nullptr, stream);
 }
 
 extern "C" int vpr_knn_topk_exhaustive(const void* q, const float* q_scale, const void* gallery,
                                        const float* gallery_scale, int is_fp8, int B, int N, int D, int k,
                                        int index_base, float* out_val, int32_t* out_idx, void* workspace,
                                        size_t workspace_bytes, void* stream) {
-  KnnPlan p;
-  if (B <= 0 || N <= 0 || D <= 0 || k <= 0 || !workspace) return VPR_ERR_INVALID_ARG;
-  if (!knn_plan(B, N, D, k, &p)) return VPR_ERR_UNSUPPORTED;
-  const KnnOperands o{q, gallery, q_scale, gallery_scale, is_fp8 != 0};
-  const int st = knn_check(o, D);
-  if (st != VPR_OK) return st;
-  if (workspace_bytes < p.total) return VPR_ERR_WORKSPACE;
-  const int rb = o.fp8 ? D : D * 2;
-  if (rb > EX_MAXCH * 64 * 16) return VPR_ERR_UNSUPPORTED;
-  float* S = reinterpret_cast<float*>(static_cast<char*>(workspace) + p.off_S);
-  hipStream_t hs = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)((N + 3) / 4));
-  if (o.fp8)
-    VPR_TRY_LAUNCH(launch_kernel(knn_exact_scores_kernel<true>, grid, dim3(256), 0, hs, o.q, o.g, o.q_scale, o.g_scale,
-                                 S, B, N, rb, p.ldS));
-  else
-    VPR_TRY_LAUNCH(launch_kernel(knn_exact_scores_kernel<false>, grid, dim3(256), 0, hs, o.q, o.g, o.q_scale, o.g_scale,
-                                 S, B, N, rb, p.ldS));
   // the scores are exact already: every cut keeps the true largest keys, whatever the bound says
-  return knn_select(o, B, N, D, k, index_base, out_val, out_idx, workspace, workspace_bytes, hs, 1.0f, nullptr, nullptr);
+  const KnnOutputs out{index_base, out_val, out_idx, 1.0f, nullptr, nullptr};
+  KnnCall c;      // one slab: the exact kernel writes a plain score matrix
+  VPR_TRY_LAUNCH(knn_resolve({q, gallery, q_scale, gallery_scale, is_fp8 != 0}, B, N, D, k, workspace, workspace_bytes,
+                             &out, false, VPR_ERR_INVALID_ARG, &c));
+  if (c.row_bytes > EX_MAXCH * 64 * 16) return VPR_ERR_UNSUPPORTED;
+  float* S = reinterpret_cast<float*>(c.ws + c.p.off_S);
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  VPR_TRY_LAUNCH(knn_dispatch_fp8(c.o.fp8, [&](auto fp8) {
+    return launch_kernel(knn_exact_scores_kernel<decltype(fp8)::value>, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, hs,
+                         c.o.q, c.o.g, c.o.q_scale, c.o.g_scale, S, B, N, c.row_bytes, c.p.ldS);
+  }));
+  return knn_select(c, out, hs);
 }
 
 extern "C" int vpr_quantize_fp8_rows(const float* x, long long rows, int D, uint8_t* q, float* scale, void* stream) {

@@ -28,6 +28,10 @@ int launch_gemm_nt_group(const GemmProblem* probs, int count, hipStream_t stream
 int launch_gemm_nt_fp8(const uint8_t* A, int lda, const float* a_scale, const uint8_t* W, int ldw, const float* w_scale,
                        float* C, int ldc, int M, int N, int K, hipStream_t stream);
 int launch_gemm256(const GemmProblem& problem, hipStream_t stream);   // gemm256.hip: 256x256 tiles, K >= 128
+// What launch_gemm_nt[_fp8] (N output columns) / launch_gemm256[_fp8] launch, by the name a kernel trace prints: each sits
+// beside its launch function and takes the same decisions.
+const char* gemm_nt_kernel_name(bool fp8, int N);
+const char* gemm256_kernel_name(bool fp8);
 // gemm256.hip: SALAD score + cluster MLPs with the second layers fused into the layer-1 tile epilogue; S / F receive
 // hidden / 256 partial-sum slabs of [M][m] / [M][l] f32 (slab 0 carries the bias), to be added in slab order.
 // Fuse2Drop: dropout on the hidden layer (vpr_salad_aggregate_train): unit u of token `token` of image image_base + b is kept
