@@ -509,6 +509,42 @@ def test_knn_default_bound_certifies_normalised_descriptors(dev):
     assert int(status.max()) == 0 and int(unc) == 0
 
 
+def _certificate_case(dev, B, N, D, k, seed):
+    """Problem and oracle answer once per shape; run(bound) -> (status list, flagged count) after asserting that the
+    answer is the oracle's whatever the bound made of the certificate."""
+    from vpr_amd import ops
+    q, g = _unit_rows(B, D, seed), _unit_rows(N, D, seed + 1)
+    v_ref, i_ref = oknn.knn_topk(q, g, k)
+    qd, gd = q.to(dev), g.to(dev)
+
+    def run(bound, **kw):
+        status = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        unc = torch.zeros(1, dtype=torch.int32, device=dev)
+        v, i = ops.knn_topk(qd, gd, k, norm_bound=bound, status=status, uncertified=unc, **kw)
+        assert torch.equal(i.cpu(), i_ref) and torch.equal(v.cpu(), v_ref), f"answer differs at bound {bound}"
+        return status.tolist(), int(unc)
+    return run
+
+
+def test_knn_general_path_certificate(dev):
+    """Rows wider than the fused kernel's 24 KB (knn_rescore_kernel + knn_order_kernel): the bound alone decides
+    between status 0 and 2 (kp = 16 < N: the list is full, and this path does not widen); the answer is the oracle's
+    either way.  Fewer rows than kp: nothing was cut, status 0 whatever the bound."""
+    run = _certificate_case(dev, 3, 600, 16384, 5, 81)
+    assert run(1e-9) == ([0, 0, 0], 0)
+    assert run(1e6) == ([2, 2, 2], 3)
+    assert _certificate_case(dev, 3, 12, 16384, 5, 83)(1e6) == ([0, 0, 0], 0)
+
+
+def test_knn_fused_certificate_on_lists_of_a_later_select_level(dev):
+    """37 level-0 chunks x kp 128 > 4096 candidates: a knn_select_kernel level runs, then the fused kernel on lists
+    whose per-chunk cuts it cannot see (level0_lists == 0): certified at once, or widened and flagged."""
+    run = _certificate_case(dev, 2, 300000, 64, 64, 85)
+    assert run(1e-9) == ([0, 0], 0)
+    assert run(1e6) == ([2, 2], 2)
+    assert run(1e6, exact_fallback=True)[0] == [3, 3]
+
+
 
 # ----------------------------------------------------------------- score-store paths
 @pytest.mark.parametrize("B,N,D,fp8", [(64, 20000, 8448, False), (64, 20000, 8448, True), (7, 1003, 256, False),

@@ -151,7 +151,7 @@ EXTENSION_PROTOTYPES = {
 
 
 def library_path() -> str:
-    """The in-tree library; VPR_AMD_LIBRARY points an A/B run at another build of it (scripts/ab_libs.sh)."""
+    """The in-tree library; VPR_AMD_LIBRARY points an A/B run at another build of it."""
     return os.environ.get("VPR_AMD_LIBRARY") or os.path.join(_HERE, "libvpr_amd.so")
 
 

@@ -221,7 +221,7 @@ __global__ __launch_bounds__(256, WGPC) void knn_scores_kernel(
 }
 
 // ---------------------------------------------------------------------------------------------
-// Block-wide iterative top-KP over <= 4096 (value, index) pairs held 16 per thread.
+// 2. Block-wide top-kp selection, shared by every select level, the fused final kernel and the shard merge.
 // Key order: value desc, index asc (packed into one u64 so a max-reduction does both).
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t f32_orderable(float f) {
@@ -232,31 +232,27 @@ __device__ __forceinline__ float f32_from_orderable(uint32_t o) {
   const uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
   return __uint_as_float(u);
 }
-__device__ __forceinline__ unsigned long long make_key(float v, int idx) {
-  // idx >= 0 real entry; idx < 0 padding (sorts last among equal values, and carries -inf).
+__device__ __forceinline__ unsigned long long make_key(float v, int idx) {   // idx >= 0; unique per idx
   return ((unsigned long long)f32_orderable(v) << 32) | (uint32_t)(0x7fffffff - idx);
 }
 __device__ __forceinline__ int key_idx(unsigned long long k) { return 0x7fffffff - (int)(uint32_t)k; }
 __device__ __forceinline__ float key_val(unsigned long long k) { return f32_from_orderable((uint32_t)(k >> 32)); }
 
-constexpr unsigned long long KEY_DEAD = 0ull;   // below every real key (orderable(-inf) > 0)
-constexpr int SEL_CAP = 4096;                   // candidate list capacity (= elements per block)
+constexpr unsigned long long KEY_DEAD = 0ull;   // padding: below every real key (orderable(-inf) > 0), so it sorts last
+constexpr int SEL_CAP = 4096;                   // candidate list capacity of the register-held selects (= keys per block)
 
-struct SelectSmem {
-  unsigned long long tmax[256];
-  unsigned long long cand[SEL_CAP];
-  unsigned long long outk[128];
-  unsigned long long thr;
-  int cnt;
-};
+// The key of an input entry: positions outside the input and padding entries (index < 0) become KEY_DEAD by a select,
+// so callers load from a clamped position and stay branch-free (their keys stay in registers).
+__device__ __forceinline__ unsigned long long candidate_key(float val, int id, bool in_range) {
+  return (in_range && id >= 0) ? make_key(val, id) : KEY_DEAD;
+}
+// One output entry: KEY_DEAD -> (-inf, -1); a real key -> (value, index + index_base).
+__device__ __forceinline__ void store_entry(unsigned long long k, float* __restrict__ out_val,
+                                            int32_t* __restrict__ out_idx, long long o, int index_base = 0) {
+  out_val[o] = k == KEY_DEAD ? -INFINITY : key_val(k);
+  out_idx[o] = k == KEY_DEAD ? -1 : key_idx(k) + index_base;
+}
 
-// Block-wide top-kp of <= 4096 unique keys held 16 per thread, without a serial argmax loop:
-//   a. every thread (or, for kp <= 64, every group of 4 threads) publishes the max of its keys;
-//   b. the kp-th largest published max T (found by rank counting) is a lower bound of the kp-th
-//      largest key overall, so every top-kp key is >= T;
-//   c. keys >= T are appended to an LDS list (typically kp..2kp of them);
-//   d. each listed key counts the listed keys above it = its rank; ranks < kp go to outk[rank].
-// outk[0..kp) is complete (KEY_DEAD-padded) and visible to the whole block on return.
 template <int CTRL>
 __device__ __forceinline__ unsigned long long dpp_u64(unsigned long long v) {
   const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, 0xf, 0xf, true);
@@ -264,53 +260,115 @@ __device__ __forceinline__ unsigned long long dpp_u64(unsigned long long v) {
   return ((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo;
 }
 
-__device__ __forceinline__ void block_select(const unsigned long long (&keys)[16], int kp, SelectSmem& sm) {
-  const int tid = threadIdx.x;
-  unsigned long long best = KEY_DEAD;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) best = keys[i] > best ? keys[i] : best;
-  if (tid == 0) { sm.thr = 1ull; sm.cnt = 0; }
-  if (tid < kp) sm.outk[tid] = KEY_DEAD;
-  if (kp <= 64) {
-    // 64 group maxes (4 adjacent lanes each, DPP quad permutes) are enough to bound kp <= 64
-    // keys, and ranking 64 values is 4x cheaper than ranking 256.
-    unsigned long long o = dpp_u64<0xB1>(best);
-    best = o > best ? o : best;
-    o = dpp_u64<0x4E>(best);
-    best = o > best ? o : best;
-    if ((tid & 3) == 0) sm.tmax[tid >> 2] = best;
-    __syncthreads();
-    if (tid < 64) {
-      const unsigned long long mine = sm.tmax[tid];
-      int rank = 0;
-      for (int s = 0; s < 64; s += 2) {
-        const ulonglong2 t2 = *reinterpret_cast<const ulonglong2*>(&sm.tmax[s]);
-        rank += (t2.x > mine ? 1 : 0) + (t2.y > mine ? 1 : 0);
-      }
-      if (rank == kp - 1 && mine != KEY_DEAD) sm.thr = mine;   // keys are unique: one writer
-    }
-  } else {
-    sm.tmax[tid] = best;
-    __syncthreads();
+// Top-kp of a block's unique keys without a serial argmax loop, in four steps:
+//   a. publish   every group of G threads (G = 1, 2, 4) leaves the max of its keys in tmax;
+//   b. threshold T = the kp-th largest published max (two forms below) is a lower bound of the kp-th largest key
+//                overall, so every top-kp key is >= T;
+//   c. filter    keys >= T are appended to the LDS list cand (typically kp..2kp of them);
+//   d. rank      each listed key counts the listed keys above it = its rank; ranks < kp go to outk[rank].
+// Invariants every step relies on:
+//   - keys are unique (the index is part of the key), so exactly one published max has rank kp - 1: thr has one writer;
+//   - thr == 1 means "no threshold" (fewer than kp live published maxes): 1 is below every real key and above
+//     KEY_DEAD, so `key >= thr` then takes every live key and still drops the padding;
+//   - KEY_DEAD sorts last, so it never outranks a real key and outk[0, kp) ends in the padding it was reset to.
+template <int CAP, int NOUT>
+struct SelectState {
+  unsigned long long tmax[256];    // published maxes
+  unsigned long long cand[CAP];    // keys >= thr, unordered
+  unsigned long long outk[NOUT];   // the answer, rank-ordered, KEY_DEAD-padded
+  unsigned long long thr;
+  int cnt;                         // entries of cand
+};
+
+// Before the first barrier of a selection.  NT = threads of the block.
+template <int NT, int CAP, int NOUT>
+__device__ __forceinline__ void select_reset(SelectState<CAP, NOUT>& sm) {
+  static_assert(NOUT <= NT, "one thread per output slot");
+  if (threadIdx.x == 0) { sm.thr = 1ull; sm.cnt = 0; }
+  if (threadIdx.x < NOUT) sm.outk[threadIdx.x] = KEY_DEAD;
+}
+
+// Step a: the max over each group of G adjacent lanes (DPP quad permutes) goes to tmax[tid / G].
+template <int G, int CAP, int NOUT>
+__device__ __forceinline__ void publish_max(SelectState<CAP, NOUT>& sm, unsigned long long best) {
+  static_assert(G == 1 || G == 2 || G == 4, "a group lives inside one DPP quad");
+  if constexpr (G >= 2) { const unsigned long long o = dpp_u64<0xB1>(best); best = o > best ? o : best; }
+  if constexpr (G == 4) { const unsigned long long o = dpp_u64<0x4E>(best); best = o > best ? o : best; }
+  if ((threadIdx.x & (G - 1)) == 0) sm.tmax[threadIdx.x / G] = best;
+}
+
+// Step b, all-pairs form: thread t < NPUB ranks tmax[t] against all NPUB published maxes.  Returns T to every thread.
+template <int NPUB, int CAP, int NOUT>
+__device__ __forceinline__ unsigned long long threshold_all_pairs(SelectState<CAP, NOUT>& sm, int kp) {
+  __syncthreads();
+  if (threadIdx.x < NPUB) {
+    const unsigned long long mine = sm.tmax[threadIdx.x];
     int rank = 0;
-    for (int s = 0; s < 256; s += 2) {
+    for (int s = 0; s < NPUB; s += 2) {
       const ulonglong2 t2 = *reinterpret_cast<const ulonglong2*>(&sm.tmax[s]);
-      rank += (t2.x > best ? 1 : 0) + (t2.y > best ? 1 : 0);
+      rank += (t2.x > mine ? 1 : 0) + (t2.y > mine ? 1 : 0);
     }
-    if (rank == kp - 1 && best != KEY_DEAD) sm.thr = best;
+    if (rank == kp - 1 && mine != KEY_DEAD) sm.thr = mine;
   }
   __syncthreads();
-  const unsigned long long T = sm.thr;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    if (keys[i] >= T) {
-      const int pos = atomicAdd(&sm.cnt, 1);
-      sm.cand[pos] = keys[i];
-    }
+  return sm.thr;
+}
+
+// Step b, wave-list form for 256 threads that each publish their own max `best`, without the 256 x 256 all-pairs
+// ranking (VALU-bound: 100 us at 1M rows): rank inside the own wave (64 broadcast reads), the top kp of every wave go
+// to a sorted list, and the global rank of a listed key = own rank + binary searches in the other three lists.
+template <int CAP, int NOUT>
+__device__ __forceinline__ unsigned long long threshold_wave_lists(SelectState<CAP, NOUT>& sm,
+                                                                   unsigned long long (&wtop)[4][128],
+                                                                   unsigned long long best, int kp) {
+  const int tid = threadIdx.x, wv = tid >> 6;
+  for (int i = tid; i < 4 * 128; i += 256) wtop[i >> 7][i & 127] = KEY_DEAD;
+  publish_max<1>(sm, best);
+  __syncthreads();
+  int wr = 0;
+  for (int s = 0; s < 64; s += 2) {
+    const ulonglong2 t2 = *reinterpret_cast<const ulonglong2*>(&sm.tmax[wv * 64 + s]);
+    wr += (t2.x > best ? 1 : 0) + (t2.y > best ? 1 : 0);
   }
+  const bool listed = best != KEY_DEAD && wr < kp;
+  if (listed) wtop[wv][wr] = best;
+  __syncthreads();
+  if (listed) {
+    int gr = wr;
+    for (int w2 = 0; w2 < 4; ++w2) {
+      if (w2 == wv) continue;
+      int lo = 0, hi = kp;                      // descending list, KEY_DEAD (= 0) padding at the end
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (wtop[w2][mid] > best) lo = mid + 1; else hi = mid;
+      }
+      gr += lo;
+    }
+    if (gr == kp - 1) sm.thr = best;
+  }
+  __syncthreads();
+  return sm.thr;
+}
+
+// Step c over a thread's NSLOT slots: kept(i) says whether slot i reaches the threshold, key(i) is its key, asked for
+// only then (a caller that holds scores, not keys, builds no key for a score that fails).
+// Length of the list, whatever the data (ties, sorted input, all-equal scores): with m keys behind every published
+// max, kp - 1 published maxes lie above T and their groups add at most m keys each; the group whose max is T adds
+// that one key; every other group's keys are all below T.  So cnt <= m (kp - 1) + 1, and without a threshold
+// (fewer than kp live groups) cnt <= m (kp - 1).  Every caller says why its CAP covers that.
+template <int NSLOT, int CAP, int NOUT, typename P, typename K>
+__device__ __forceinline__ void select_filter(SelectState<CAP, NOUT>& sm, P&& kept, K&& key) {
+#pragma unroll
+  for (int i = 0; i < NSLOT; ++i)
+    if (kept(i)) sm.cand[atomicAdd(&sm.cnt, 1)] = key(i);
+}
+
+// Step d.  outk[0, kp) is complete and visible to the whole block on return.
+template <int NT, int CAP, int NOUT>
+__device__ __forceinline__ void select_rank(SelectState<CAP, NOUT>& sm, int kp) {
   __syncthreads();
   const int c = sm.cnt;
-  for (int ci = tid; ci < c; ci += 256) {
+  for (int ci = threadIdx.x; ci < c; ci += NT) {
     const unsigned long long mine = sm.cand[ci];
     int r = 0;
     for (int cj = 0; cj < c; ++cj) r += sm.cand[cj] > mine ? 1 : 0;
@@ -319,8 +377,30 @@ __device__ __forceinline__ void block_select(const unsigned long long (&keys)[16
   __syncthreads();
 }
 
-// Branch-free load of up to 16 (value, index) pairs per thread: out-of-range positions are
-// clamped for the load and turned into KEY_DEAD by a select (keeps the 16 keys in registers).
+// All four steps for NT threads that hold NK keys each.  256 threads and kp <= 64: 64 quad maxes are enough to bound
+// kp keys, and ranking 64 values is 4x cheaper than ranking 256; otherwise 256 maxes (of threads, or of thread pairs
+// of a 512-thread block).
+template <int NT, int NK, int CAP, int NOUT>
+__device__ __forceinline__ void block_select(const unsigned long long (&keys)[NK], int kp, SelectState<CAP, NOUT>& sm) {
+  static_assert(NT == 256 || NT == 512, "256 published maxes at most");
+  static_assert(NT * NK <= CAP, "cand holds every key of the block, so no threshold can overflow it");
+  unsigned long long best = keys[0];
+#pragma unroll
+  for (int i = 1; i < NK; ++i) best = keys[i] > best ? keys[i] : best;
+  select_reset<NT>(sm);
+  unsigned long long T;
+  if (NT == 256 && kp <= 64) {
+    publish_max<4>(sm, best);
+    T = threshold_all_pairs<64>(sm, kp);
+  } else {
+    publish_max<NT / 256>(sm, best);
+    T = threshold_all_pairs<256>(sm, kp);
+  }
+  select_filter<NK>(sm, [&](int i) { return keys[i] >= T; }, [&](int i) { return keys[i]; });
+  select_rank<NT>(sm, kp);
+}
+
+// Branch-free load of up to 16 (value, index) pairs per thread (clamped position, see candidate_key).
 __device__ __forceinline__ void load_keys(unsigned long long (&keys)[16], const float* __restrict__ v,
                                           const int32_t* __restrict__ ix, int L, int base) {
   if (ix != nullptr) {
@@ -329,16 +409,13 @@ __device__ __forceinline__ void load_keys(unsigned long long (&keys)[16], const 
       const int p = base + i * 256 + (int)threadIdx.x;
       const int pc = p < L ? p : L - 1;
       const int id = ix[pc];
-      const float val = v[pc];
-      keys[i] = (p < L && id >= 0) ? make_key(val, id) : KEY_DEAD;
+      keys[i] = candidate_key(v[pc], id, p < L);
     }
   } else {
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int p = base + i * 256 + (int)threadIdx.x;
-      const int pc = p < L ? p : L - 1;
-      const float val = v[pc];
-      keys[i] = p < L ? make_key(val, p) : KEY_DEAD;
+      keys[i] = candidate_key(v[p < L ? p : L - 1], p, p < L);
     }
   }
 }
@@ -348,43 +425,37 @@ __device__ __forceinline__ void load_keys(unsigned long long (&keys)[16], const 
 __global__ __launch_bounds__(256) void knn_select_kernel(
     const float* __restrict__ in_val, const int32_t* __restrict__ in_idx, int L, long long ld_in,
     float* __restrict__ out_val, int32_t* __restrict__ out_idx, int kp, int nchunk) {
-  __shared__ SelectSmem sm;
+  __shared__ SelectState<SEL_CAP, 128> sm;
   const int c = blockIdx.x, b = blockIdx.y;
   const float* v = in_val + (long long)b * ld_in;
   const int32_t* ix = in_idx ? in_idx + (long long)b * ld_in : nullptr;
   unsigned long long keys[16];
   load_keys(keys, v, ix, L, c * KNN_CHUNK);
-  block_select(keys, kp, sm);
-  if ((int)threadIdx.x < kp) {
-    const unsigned long long k = sm.outk[threadIdx.x];
-    const long long o = ((long long)b * nchunk + c) * kp + threadIdx.x;
-    out_val[o] = k == KEY_DEAD ? -INFINITY : key_val(k);
-    out_idx[o] = k == KEY_DEAD ? -1 : key_idx(k);
-  }
+  block_select<256>(keys, kp, sm);
+  if ((int)threadIdx.x < kp)
+    store_entry(sm.outk[threadIdx.x], out_val, out_idx, ((long long)b * nchunk + c) * kp + threadIdx.x);
 }
+
+// Component e of a float4 by a compile-time-foldable select (keeps the vector in registers).
+__device__ __forceinline__ float f4_at(const float4& v, int e) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
 
 // 2a. level-0 select straight from the score matrix: grid (chunks, B), chunk = `ch` scores (multiple of 1024,
 // <= 8192).  The chunk is read ONCE: every thread requests its (up to) 8 float4 (32 scores, strided by 1024 so a wave
-// reads 1 KiB lines) before the first compare and keeps them in registers for both phases:
+// reads 1 KiB lines) before the first compare and keeps them in registers, as floats, for both passes over them:
 //   max     the thread's best (value, then lower index) of its 32 scores, plain f32 compares in index-ascending
 //           order (strict '>' keeps ties right);
-//   rank    T = the kp-th largest of the 256 published thread maxes bounds the kp-th largest key of the chunk from
-//           below; keys are unique, so at most 32 (kp-1) + 1 keys are >= T whatever the data — ties, sorted input,
-//           all-equal scores: CAP = 1024 for kp <= 32 (k <= 16), 4096 otherwise;
-//   filter  keys >= T (from the registers) appended to an LDS list (typically ~kp of them);
-//   order   each listed key counts the listed keys above it = its rank; ranks < kp are written, rank-ordered.
+//   filter  a key is built only for a score that reaches the threshold (32 u64 keys would double the registers).
+// The threshold is the wave-list form, the other steps are the shared ones.  m = 32 keys per published max, so the
+// list holds at most 32 (kp - 1) + 1 keys: CAP = 1024 for kp <= 32 (k <= 16), 4096 otherwise (kp <= 128).
 // Round 1 read the chunk twice with dependent loads (8 round trips per pass) under 35 KB of LDS (4 workgroups per CU):
 // 15.7 us at 100k rows, 117 us at 1M; this form needs 15 KB (kp <= 32) and one round trip.
+static_assert(32 * (32 - 1) + 1 <= 1024 && 32 * (128 - 1) + 1 <= 4096, "list bound of the streaming select");
 template <int CAP>
 __global__ __launch_bounds__(256) void knn_select_stream_kernel(
     const float* __restrict__ S, int N, long long ldS, int ch,
     float* __restrict__ out_val, int32_t* __restrict__ out_idx, int kp, int nchunk, int nslab, long long slab_stride) {
-  __shared__ unsigned long long tmax[256];
+  __shared__ SelectState<CAP, 128> sm;
   __shared__ unsigned long long wtop[4][128];
-  __shared__ unsigned long long cand[CAP];
-  __shared__ unsigned long long outk[128];
-  __shared__ unsigned long long thr;
-  __shared__ int cnt;
   const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const float* v = S + (long long)b * ldS;
   const int base = c * ch;
@@ -426,69 +497,102 @@ __global__ __launch_bounds__(256) void knn_select_stream_kernel(
     for (int e = 0; e < 4; ++e)
       if (p + e < len && (qq[e] > bv || bi < 0)) { bv = qq[e]; bi = base + p + e; }
   }
-  const unsigned long long best = bi >= 0 ? make_key(bv, bi) : KEY_DEAD;
-  if (tid == 0) { thr = 1ull; cnt = 0; }
-  if (tid < kp) outk[tid] = KEY_DEAD;
-  for (int i = tid; i < 4 * 128; i += 256) wtop[i >> 7][i & 127] = KEY_DEAD;
-  tmax[tid] = best;
-  __syncthreads();
-  // kp-th largest of the 256 thread maxes without the 256 x 256 all-pairs ranking (VALU-bound: 100 us at 1M rows):
-  // rank inside the own wave (64 broadcast reads), the top kp of every wave go to a sorted list, and the global rank
-  // of a listed key = own rank + binary searches in the other three lists.
-  const int wv = tid >> 6;
-  int wr = 0;
-  for (int s = 0; s < 64; s += 2) {
-    const ulonglong2 t2 = *reinterpret_cast<const ulonglong2*>(&tmax[wv * 64 + s]);
-    wr += (t2.x > best ? 1 : 0) + (t2.y > best ? 1 : 0);
-  }
-  const bool listed = best != KEY_DEAD && wr < kp;
-  if (listed) wtop[wv][wr] = best;
-  __syncthreads();
-  if (listed) {
-    int gr = wr;
-    for (int w2 = 0; w2 < 4; ++w2) {
-      if (w2 == wv) continue;
-      int lo = 0, hi = kp;                      // descending list, KEY_DEAD (= 0) padding at the end
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (wtop[w2][mid] > best) lo = mid + 1; else hi = mid;
-      }
-      gr += lo;
-    }
-    if (gr == kp - 1) thr = best;               // unique keys: one writer
-  }
-  __syncthreads();
-  const unsigned long long T = thr;
+  select_reset<256>(sm);
+  const unsigned long long T = threshold_wave_lists(sm, wtop, candidate_key(bv, bi, true), kp);
   // key >= T  <=>  value > Tv, or value == Tv and index <= Ti  (T == 1: no threshold, take all)
   const bool all = T == 1ull;
   const float Tv = all ? -INFINITY : key_val(T);
   const int Ti = all ? 0x7fffffff : key_idx(T);
+  // slot i of the thread = component i & 3 of q[i >> 2], at position pos(i) of the chunk
+  const auto pos = [&](int i) { return tid * 4 + (i >> 2) * 1024 + (i & 3); };
+  select_filter<32>(
+      sm,
+      [&](int i) {
+        const float x = f4_at(q[i >> 2], i & 3);
+        return pos(i) < len && (x > Tv || (x == Tv && base + pos(i) <= Ti) || all);
+      },
+      [&](int i) { return make_key(f4_at(q[i >> 2], i & 3), base + pos(i)); });
+  select_rank<256>(sm, kp);
+  if (tid < kp) store_entry(sm.outk[tid], out_val, out_idx, ((long long)b * nchunk + c) * kp + tid);
+}
+
+// ---------------------------------------------------------------------------------------------
+// 3. Exact rescoring and certification.  One operand dispatch (bf16 / e4m3 16-B chunks), one finish of an exact
+// score, one |q| and one certificate, shared by the split kernels, the fused kernel and the exhaustive fallback.
+// ---------------------------------------------------------------------------------------------
+// acc + <q, g> over one 16-B chunk of each operand, in f64: every product is exact.
+template <bool FP8>
+__device__ __forceinline__ double dot16(const s16x8& qa, const s16x8& ga, double acc) {
+  if constexpr (FP8) {
+    typedef __attribute__((ext_vector_type(4))) int i32x4;
+    const i32x4 qi = __builtin_bit_cast(i32x4, qa), gi = __builtin_bit_cast(i32x4, ga);
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int p = tid * 4 + i * 1024;
-    const float qq[4] = {q[i].x, q[i].y, q[i].z, q[i].w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float x = qq[e];
-      if (p + e < len && (x > Tv || (x == Tv && base + p + e <= Ti) || all))
-        cand[atomicAdd(&cnt, 1)] = make_key(x, base + p + e);
+    for (int w = 0; w < 4; ++w) {
+      acc = fma((double)__builtin_amdgcn_cvt_f32_fp8(qi[w], 0), (double)__builtin_amdgcn_cvt_f32_fp8(gi[w], 0), acc);
+      acc = fma((double)__builtin_amdgcn_cvt_f32_fp8(qi[w], 1), (double)__builtin_amdgcn_cvt_f32_fp8(gi[w], 1), acc);
+      acc = fma((double)__builtin_amdgcn_cvt_f32_fp8(qi[w], 2), (double)__builtin_amdgcn_cvt_f32_fp8(gi[w], 2), acc);
+      acc = fma((double)__builtin_amdgcn_cvt_f32_fp8(qi[w], 3), (double)__builtin_amdgcn_cvt_f32_fp8(gi[w], 3), acc);
     }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      acc = fma((double)bf16_bits_to_f32((uint16_t)qa[j]), (double)bf16_bits_to_f32((uint16_t)ga[j]), acc);
   }
-  __syncthreads();
-  const int cn = cnt;
-  for (int ci = tid; ci < cn; ci += 256) {
-    const unsigned long long mine = cand[ci];
-    int r = 0;
-    for (int cj = 0; cj < cn; ++cj) r += cand[cj] > mine ? 1 : 0;
-    if (r < kp) outk[r] = mine;
+  return acc;
+}
+
+// Sum of squares of one 16-B operand chunk (f32; feeds the error bound of the certification step only).
+template <bool FP8>
+__device__ __forceinline__ float sumsq16(const s16x8& a) {
+  float t = 0.f;
+  if constexpr (FP8) {
+    typedef __attribute__((ext_vector_type(4))) int i32x4;
+    const i32x4 w = __builtin_bit_cast(i32x4, a);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float x = __builtin_amdgcn_cvt_f32_fp8(w[i], 0); t = fmaf(x, x, t);
+      x = __builtin_amdgcn_cvt_f32_fp8(w[i], 1); t = fmaf(x, x, t);
+      x = __builtin_amdgcn_cvt_f32_fp8(w[i], 2); t = fmaf(x, x, t);
+      x = __builtin_amdgcn_cvt_f32_fp8(w[i], 3); t = fmaf(x, x, t);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { const float x = bf16_bits_to_f32((uint16_t)a[j]); t = fmaf(x, x, t); }
   }
-  __syncthreads();
-  if (tid < kp) {
-    const unsigned long long k = outk[tid];
-    const long long o = ((long long)b * nchunk + c) * kp + tid;
-    out_val[o] = k == KEY_DEAD ? -INFINITY : key_val(k);
-    out_idx[o] = k == KEY_DEAD ? -1 : key_idx(k);
-  }
+  return t;
+}
+
+// The f32 scale of row i of an e4m3 operand; 1 for bf16 operands (null scale arrays) and for padding (i < 0).
+template <bool FP8>
+__device__ __forceinline__ float row_scale(const float* __restrict__ scale, long long i) {
+  if constexpr (FP8) return i >= 0 ? scale[i] : 1.f;
+  return 1.f;
+}
+
+// From the f64 sum of products to the score: scales in the order of oracle/knn.py, (tot * q_scale) * g_scale, then ONE
+// rounding to f32.  Padding (id < 0) scores -inf.
+template <bool FP8>
+__device__ __forceinline__ float finish_exact(double tot, float q_scale, float g_scale, int id) {
+  if constexpr (FP8) tot = (tot * (double)q_scale) * (double)g_scale;
+  return id < 0 ? -INFINITY : (float)tot;
+}
+
+// |q| of the quantised query from the sum of squares of its stored elements.
+__device__ __forceinline__ float query_norm(float sumsq, float q_scale) { return sqrtf(sumsq) * fabsf(q_scale); }
+
+// Certification (the exactness contract, made checkable).  The result is the exact top-k iff no row OUTSIDE the
+// rescored set has an exact score >= the k-th best exact score e_k of the set.  Every such row lost an
+// approximate-score comparison: its MFMA score is <= a_min, the smallest approximate score kept (level-0 lists and
+// the top-kp cut both keep the largest keys), and |MFMA score - exact score| <= eps = err_rel * |q| for gallery
+// rows inside the norm bound the caller folded into err_rel (any summation order of D f32 additions of exact
+// products: gamma_D * sum|q_i g_i| <= D 2^-24 |q| |g|).  So  e_k - eps > a_min  certifies the answer, and so does a
+// list that is not full: nothing was cut.
+// Otherwise the set is widened to every level-0 candidate with MFMA score >= e_k - eps (they are rescored exactly
+// too, status 1); if a level-0 chunk list is itself cut above that bar (>= kp rows of one chunk inside the band),
+// or the widened set does not fit, the query is flagged (status 2) and the host re-runs it on exact scores
+// (vpr_knn_exact_scores): ops.knn_topk(..., exact_fallback=True).
+__device__ __forceinline__ bool knn_certified(float e_k, float eps, bool list_full, float a_min) {
+  return !list_full || e_k - eps > a_min;
 }
 
 // 3a. exact rescoring: grid (kp, B), one workgroup per (candidate, query).  cand_idx [B][kp] are
@@ -497,46 +601,6 @@ __global__ __launch_bounds__(256) void knn_select_stream_kernel(
 // butterfly, then the 4 wave sums) -> independent of how the candidate was found.  All of a
 // thread's loads are issued before the first FMA: one trip to HBM per row.
 constexpr int RS_U = 6;   // 16-B chunks per thread per trip
-__device__ __forceinline__ double dot16_bf16(const s16x8& qa, const s16x8& ga, double acc) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j)
-    acc = fma((double)bf16_bits_to_f32((uint16_t)qa[j]), (double)bf16_bits_to_f32((uint16_t)ga[j]), acc);
-  return acc;
-}
-__device__ __forceinline__ double dot16_fp8(const s16x8& qa, const s16x8& ga, double acc) {
-  typedef __attribute__((ext_vector_type(4))) int i32x4;
-  const i32x4 qi = __builtin_bit_cast(i32x4, qa), gi = __builtin_bit_cast(i32x4, ga);
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    acc = fma((double)__builtin_amdgcn_cvt_f32_fp8(qi[w], 0), (double)__builtin_amdgcn_cvt_f32_fp8(gi[w], 0), acc);
-    acc = fma((double)__builtin_amdgcn_cvt_f32_fp8(qi[w], 1), (double)__builtin_amdgcn_cvt_f32_fp8(gi[w], 1), acc);
-    acc = fma((double)__builtin_amdgcn_cvt_f32_fp8(qi[w], 2), (double)__builtin_amdgcn_cvt_f32_fp8(gi[w], 2), acc);
-    acc = fma((double)__builtin_amdgcn_cvt_f32_fp8(qi[w], 3), (double)__builtin_amdgcn_cvt_f32_fp8(gi[w], 3), acc);
-  }
-  return acc;
-}
-
-// Sum of squares of one 16-B operand chunk (f32; feeds the error bound of the certification step only).
-__device__ __forceinline__ float sumsq16_bf16(const s16x8& a) {
-  float t = 0.f;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { const float x = bf16_bits_to_f32((uint16_t)a[j]); t = fmaf(x, x, t); }
-  return t;
-}
-__device__ __forceinline__ float sumsq16_fp8(const s16x8& a) {
-  typedef __attribute__((ext_vector_type(4))) int i32x4;
-  const i32x4 w = __builtin_bit_cast(i32x4, a);
-  float t = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float x = __builtin_amdgcn_cvt_f32_fp8(w[i], 0); t = fmaf(x, x, t);
-    x = __builtin_amdgcn_cvt_f32_fp8(w[i], 1); t = fmaf(x, x, t);
-    x = __builtin_amdgcn_cvt_f32_fp8(w[i], 2); t = fmaf(x, x, t);
-    x = __builtin_amdgcn_cvt_f32_fp8(w[i], 3); t = fmaf(x, x, t);
-  }
-  return t;
-}
-
 template <bool FP8>
 __global__ __launch_bounds__(256) void knn_rescore_kernel(
     const int32_t* __restrict__ cand_idx, const void* __restrict__ Qv, const void* __restrict__ Gv,
@@ -567,8 +631,8 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(
 #pragma unroll
     for (int u = 0; u < RS_U; ++u) {
       if (ch0 + 256 * u < nchunks) {
-        acc = FP8 ? dot16_fp8(qa[u], ga[u], acc) : dot16_bf16(qa[u], ga[u], acc);
-        if (c == 0) qq += FP8 ? sumsq16_fp8(qa[u]) : sumsq16_bf16(qa[u]);
+        acc = dot16<FP8>(qa[u], ga[u], acc);
+        if (c == 0) qq += sumsq16<FP8>(qa[u]);
       }
     }
   }
@@ -577,18 +641,14 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(
   if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = acc; redq[threadIdx.x >> 6] = qq; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    double tot = (red[0] + red[1]) + (red[2] + red[3]);
-    if (FP8 && id >= 0) tot = (tot * (double)q_scale[b]) * (double)g_scale[id];   // same order as oracle/knn.py
-    exact[(long long)b * kp + c] = id < 0 ? -INFINITY : (float)tot;
-    if (c == 0) {
-      const float n2 = (redq[0] + redq[1]) + (redq[2] + redq[3]);
-      qnorm[b] = sqrtf(n2) * (FP8 ? fabsf(q_scale[b]) : 1.0f);
-    }
+    const double tot = (red[0] + red[1]) + (red[2] + red[3]);
+    exact[(long long)b * kp + c] = finish_exact<FP8>(tot, row_scale<FP8>(q_scale, b), row_scale<FP8>(g_scale, id), id);
+    if (c == 0) qnorm[b] = query_norm((redq[0] + redq[1]) + (redq[2] + redq[3]), row_scale<FP8>(q_scale, b));
   }
 }
 
-// 3c. fused final stage: grid (B), 1024 threads.  Takes the level-0 candidates (<= 4096 per
-// query), selects the top-kp by MFMA score, rescoring them exactly (16 waves, every load of a
+// 3c. fused final stage: grid (B), 512 threads.  Takes the candidates of the last select level (<= 4096 per
+// query), selects the top-kp by MFMA score, rescoring them exactly (8 waves, every load of a
 // row issued before its first FMA, the query row staged once in LDS) and writes the ordered
 // top-k — one launch instead of select + rescore + order.  Same arithmetic as the split kernels
 // (same per-lane chunk order, same butterfly), so the results are bit-identical to them.
@@ -597,11 +657,7 @@ constexpr int FF_CPW = 3;         // candidates a wave rescoring together (all t
 constexpr int FF_MAXCH = 9;       // 16-B chunks per lane per row in flight per trip
 constexpr int FF_MAXC = 256;      // rescored candidates per query: kp + what the certification step adds
 struct FinalSmem {
-  unsigned long long tmax[256];
-  unsigned long long cand[SEL_CAP];
-  unsigned long long outk[FF_MAXC];
-  unsigned long long thr;
-  int cnt;
+  SelectState<SEL_CAP, FF_MAXC> sel;
   float exact[FF_MAXC];
   float red[8];
   float ek;         // k-th best exact score of the rescored set
@@ -610,16 +666,6 @@ struct FinalSmem {
   int flag;         // 0 certified, 1 widen, 2 cannot be certified from the lists in hand
 };
 
-// Certification (the exactness contract, made checkable).  The result is the exact top-k iff no row OUTSIDE the
-// rescored set has an exact score >= the k-th best exact score e_k of the set.  Every such row lost an
-// approximate-score comparison: its MFMA score is <= a_min, the smallest approximate score kept (level-0 lists and
-// the top-kp cut both keep the largest keys), and |MFMA score - exact score| <= eps = err_rel * |q| for gallery
-// rows inside the norm bound the caller folded into err_rel (any summation order of D f32 additions of exact
-// products: gamma_D * sum|q_i g_i| <= D 2^-24 |q| |g|).  So  e_k - eps > a_min  certifies the answer.
-// Otherwise the set is widened to every level-0 candidate with MFMA score >= e_k - eps (they are rescored exactly
-// too, status 1); if a level-0 chunk list is itself cut above that bar (>= kp rows of one chunk inside the band),
-// or the widened set does not fit, the query is flagged (status 2) and the host re-runs it on exact scores
-// (vpr_knn_exact_scores): ops.knn_topk(..., exact_fallback=True).
 template <bool FP8>
 __global__ __launch_bounds__(FF_NT) void knn_final_fused_kernel(
     const float* __restrict__ cand_val, const int32_t* __restrict__ cand_idx, int L,
@@ -629,6 +675,7 @@ __global__ __launch_bounds__(FF_NT) void knn_final_fused_kernel(
     float err_rel, int level0_lists, int32_t* __restrict__ status, int32_t* __restrict__ uncertified) {
   extern __shared__ __attribute__((aligned(16))) char dyn[];      // [row_bytes] query row
   __shared__ FinalSmem sm;
+  unsigned long long (&outk)[FF_MAXC] = sm.sel.outk;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
   // stage the query row (16-B chunks); |q|^2 on the way
@@ -638,7 +685,7 @@ __global__ __launch_bounds__(FF_NT) void knn_final_fused_kernel(
   for (int ch = tid; ch < nchunks; ch += FF_NT) {
     const s16x8 c16 = *reinterpret_cast<const s16x8*>(qrow + ch * 16);
     *reinterpret_cast<s16x8*>(dyn + ch * 16) = c16;
-    qq += FP8 ? sumsq16_fp8(c16) : sumsq16_bf16(c16);
+    qq += sumsq16<FP8>(c16);
   }
   qq = wave_sum(qq);
   if (lane == 0) sm.red[wave] = qq;
@@ -652,43 +699,10 @@ __global__ __launch_bounds__(FF_NT) void knn_final_fused_kernel(
     const int p = i * FF_NT + tid;
     const int pc = p < L ? p : L - 1;
     const int id = ix[pc];
-    const float val = v[pc];
-    keys[i] = (p < L && id >= 0) ? make_key(val, id) : KEY_DEAD;
+    keys[i] = candidate_key(v[pc], id, p < L);
   }
-  unsigned long long best = keys[0];
-#pragma unroll
-  for (int i = 1; i < 8; ++i) best = keys[i] > best ? keys[i] : best;
-  if (tid == 0) { sm.thr = 1ull; sm.cnt = 0; sm.extra = 0; sm.flag = 0; sm.nvalid = 0; sm.ek = -INFINITY; }
-  if (tid < FF_MAXC) sm.outk[tid] = KEY_DEAD;
-  {  // 256 group maxes: pairs of threads (quad-perm xor 1)
-    const unsigned long long o = dpp_u64<0xB1>(best);
-    best = o > best ? o : best;
-    if ((tid & 1) == 0) sm.tmax[tid >> 1] = best;
-  }
-  __syncthreads();
-  if (tid < 256) {
-    const unsigned long long mine = sm.tmax[tid];
-    int rank = 0;
-    for (int s2 = 0; s2 < 256; s2 += 2) {
-      const ulonglong2 t2 = *reinterpret_cast<const ulonglong2*>(&sm.tmax[s2]);
-      rank += (t2.x > mine ? 1 : 0) + (t2.y > mine ? 1 : 0);
-    }
-    if (rank == kp - 1 && mine != KEY_DEAD) sm.thr = mine;
-  }
-  __syncthreads();
-  const unsigned long long T = sm.thr;
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-    if (keys[i] >= T) sm.cand[atomicAdd(&sm.cnt, 1)] = keys[i];
-  __syncthreads();
-  const int cn = sm.cnt;
-  for (int ci = tid; ci < cn; ci += FF_NT) {
-    const unsigned long long mine = sm.cand[ci];
-    int r = 0;
-    for (int cj = 0; cj < cn; ++cj) r += sm.cand[cj] > mine ? 1 : 0;
-    if (r < kp) sm.outk[r] = mine;
-  }
-  __syncthreads();
+  if (tid == 0) { sm.extra = 0; sm.flag = 0; sm.nvalid = 0; sm.ek = -INFINITY; }
+  block_select<FF_NT>(keys, kp, sm.sel);
 
   // ---- exact rescoring of outk[c_lo, c_hi): wave w takes candidates c_lo + w + 8*j; FF_CPW of them per trip, with
   // every 16-B chunk of all their rows requested before the first FMA (one HBM round trip per trip) ----
@@ -700,7 +714,7 @@ __global__ __launch_bounds__(FF_NT) void knn_final_fused_kernel(
 #pragma unroll
       for (int j = 0; j < FF_CPW; ++j) {
         const int c = c0 + 8 * j;
-        const unsigned long long key = c < c_hi ? sm.outk[c] : KEY_DEAD;
+        const unsigned long long key = c < c_hi ? outk[c] : KEY_DEAD;
         id[j] = key == KEY_DEAD ? -1 : key_idx(key);
         grow[j] = static_cast<const char*>(Gv) + (long long)(id[j] < 0 ? 0 : id[j]) * row_bytes;
         acc[j] = 0.0;
@@ -720,40 +734,32 @@ __global__ __launch_bounds__(FF_NT) void knn_final_fused_kernel(
           if (ch < nchunks) {
             const s16x8 qa = *reinterpret_cast<const s16x8*>(dyn + ch * 16);
 #pragma unroll
-            for (int j = 0; j < FF_CPW; ++j)
-              acc[j] = FP8 ? dot16_fp8(qa, ga[j][u], acc[j]) : dot16_bf16(qa, ga[j][u], acc[j]);
+            for (int j = 0; j < FF_CPW; ++j) acc[j] = dot16<FP8>(qa, ga[j][u], acc[j]);
           }
         }
       }
 #pragma unroll
       for (int j = 0; j < FF_CPW; ++j) {
         const int c = c0 + 8 * j;
-        double tot = wave_sum_f64(acc[j]);
-        if (FP8 && id[j] >= 0) tot = (tot * (double)q_scale[b]) * (double)g_scale[id[j]];
-        if (lane == 0 && c < c_hi) sm.exact[c] = id[j] < 0 ? -INFINITY : (float)tot;
+        const float e = finish_exact<FP8>(wave_sum_f64(acc[j]), row_scale<FP8>(q_scale, b), row_scale<FP8>(g_scale, id[j]), id[j]);
+        if (lane == 0 && c < c_hi) sm.exact[c] = e;
       }
     }
   };
   // ---- final order of outk[0, tot) by (f32(exact) desc, index asc); leaves e_k and the entry count ----
   auto order = [&](int tot) {
     if (tid < tot) {
-      const unsigned long long ki = sm.outk[tid];
-      int rank;
-      if (ki == KEY_DEAD) {
-        rank = FF_MAXC + tid;                      // padding: behind every real entry
-      } else {
+      const unsigned long long ki = outk[tid];
+      if (ki != KEY_DEAD) {                          // padding stays behind every real entry: never written here
         const unsigned long long mine = make_key(sm.exact[tid], key_idx(ki));
-        rank = 0;
+        int rank = 0;
         for (int j = 0; j < tot; ++j) {
-          const unsigned long long kj = sm.outk[j];
+          const unsigned long long kj = outk[j];
           rank += (kj != KEY_DEAD && make_key(sm.exact[j], key_idx(kj)) > mine) ? 1 : 0;
         }
         atomicAdd(&sm.nvalid, 1);
         if (rank == k - 1) sm.ek = sm.exact[tid];
-      }
-      if (rank < k) {
-        out_val[(long long)b * k + rank] = sm.exact[tid];
-        out_idx[(long long)b * k + rank] = key_idx(ki) + index_base;
+        if (rank < k) store_entry(mine, out_val, out_idx, (long long)b * k + rank, index_base);
       }
     }
   };
@@ -763,27 +769,24 @@ __global__ __launch_bounds__(FF_NT) void knn_final_fused_kernel(
   order(kp);
   __syncthreads();
   const int nvalid = sm.nvalid;
-  if (tid < k && tid >= nvalid) {                  // fewer real rows than k: (-inf, -1) tail
-    out_val[(long long)b * k + tid] = -INFINITY;
-    out_idx[(long long)b * k + tid] = -1;
-  }
+  if (tid < k && tid >= nvalid) store_entry(KEY_DEAD, out_val, out_idx, (long long)b * k + tid);   // fewer real rows than k
   // ---- certification ----
-  const float qnorm = sqrtf(((sm.red[0] + sm.red[1]) + (sm.red[2] + sm.red[3])) + ((sm.red[4] + sm.red[5]) + (sm.red[6] + sm.red[7]))) *
-                      (FP8 ? fabsf(q_scale[b]) : 1.0f);
-  const float eps = err_rel * qnorm;
-  const unsigned long long kmin = sm.outk[kp - 1];               // smallest approximate key kept (KEY_DEAD: list not full)
+  const float eps = err_rel * query_norm(((sm.red[0] + sm.red[1]) + (sm.red[2] + sm.red[3])) + ((sm.red[4] + sm.red[5]) + (sm.red[6] + sm.red[7])),
+                                         row_scale<FP8>(q_scale, b));
+  const unsigned long long kmin = outk[kp - 1];                  // smallest approximate key kept (KEY_DEAD: list not full)
   const float bar = sm.ek - eps;
+  const bool certified = knn_certified(sm.ek, eps, kmin != KEY_DEAD, key_val(kmin));
   __syncthreads();                                               // everybody has read nvalid / ek before they are reused
-  if (kmin == KEY_DEAD || bar > key_val(kmin)) {                 // nothing was cut, or the margin covers the MFMA error
+  if (certified) {
     if (tid == 0 && status) status[b] = 0;
     return;
   }
-  // widen: every level-0 candidate outside the top-kp whose approximate score reaches the bar
+  // widen: every candidate outside the top-kp whose approximate score reaches the bar
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     if (keys[i] != KEY_DEAD && keys[i] < kmin && key_val(keys[i]) >= bar) {
       const int pos = atomicAdd(&sm.extra, 1);
-      if (kp + pos < FF_MAXC) sm.outk[kp + pos] = keys[i];
+      if (kp + pos < FF_MAXC) outk[kp + pos] = keys[i];
     }
   }
   if (level0_lists) {                                            // a chunk list cut above the bar hides rows of the band
@@ -822,32 +825,24 @@ __global__ __launch_bounds__(128) void knn_order_kernel(
   __shared__ unsigned long long key[128];
   __shared__ float ek;
   const int b = blockIdx.x, i = threadIdx.x;
-  int id = -1;
-  unsigned long long mine = KEY_DEAD;
-  if (i < kp) {
-    id = cand_idx[(long long)b * kp + i];
-    if (id >= 0) mine = make_key(exact[(long long)b * kp + i], id);
-  }
+  const unsigned long long mine =
+      i < kp ? candidate_key(exact[(long long)b * kp + i], cand_idx[(long long)b * kp + i], true) : KEY_DEAD;
   key[i] = mine;
   if (i == 0) ek = -INFINITY;
   __syncthreads();
   if (i < kp) {
-    int rank = 0;
-    if (id < 0) {
-      rank = i;     // padding already sits behind every real entry (select output is ordered)
-    } else {
+    int rank = i;     // padding already sits behind every real entry (select output is ordered)
+    if (mine != KEY_DEAD) {
+      rank = 0;
       for (int j = 0; j < kp; ++j) rank += key[j] > mine ? 1 : 0;
       if (rank == k - 1) ek = key_val(mine);
     }
-    if (rank < k) {
-      out_val[(long long)b * k + rank] = id < 0 ? -INFINITY : key_val(mine);
-      out_idx[(long long)b * k + rank] = id < 0 ? -1 : id + index_base;
-    }
+    if (rank < k) store_entry(mine, out_val, out_idx, (long long)b * k + rank, index_base);
   }
   __syncthreads();
   if (i == 0 && (status || uncertified)) {
-    const bool full = cand_idx[(long long)b * kp + kp - 1] >= 0;          // the list is rank-ordered: last entry = a_min
-    const bool ok = !full || ek - err_rel * qnorm[b] > cand_approx[(long long)b * kp + kp - 1];
+    const long long last = (long long)b * kp + kp - 1;           // the list is rank-ordered: last entry = a_min
+    const bool ok = knn_certified(ek, err_rel * qnorm[b], cand_idx[last] >= 0, cand_approx[last]);
     if (status) status[b] = ok ? 0 : 2;
     if (!ok && uncertified) atomicAdd(uncertified, 1);
   }
@@ -873,21 +868,17 @@ __global__ __launch_bounds__(256) void knn_exact_scores_kernel(
     const int ch = lane + 64 * u;
     ga[u] = *reinterpret_cast<const s16x8*>(grow + (ch < nchunks ? ch : 0) * 16);
   }
-  const float gs = FP8 ? g_scale[n] : 1.f;
+  const float gs = row_scale<FP8>(g_scale, n);
   for (int b = 0; b < B; ++b) {
     const char* qrow = static_cast<const char*>(Qv) + (long long)b * row_bytes;
     double acc = 0.0;
 #pragma unroll
     for (int u = 0; u < EX_MAXCH; ++u) {
       const int ch = lane + 64 * u;
-      if (ch < nchunks) {
-        const s16x8 qa = *reinterpret_cast<const s16x8*>(qrow + ch * 16);
-        acc = FP8 ? dot16_fp8(qa, ga[u], acc) : dot16_bf16(qa, ga[u], acc);
-      }
+      if (ch < nchunks) acc = dot16<FP8>(*reinterpret_cast<const s16x8*>(qrow + ch * 16), ga[u], acc);
     }
-    double tot = wave_sum_f64(acc);
-    if (FP8) tot = (tot * (double)q_scale[b]) * (double)gs;
-    if (lane == 0) S[(long long)b * ldS + n] = (float)tot;
+    const float e = finish_exact<FP8>(wave_sum_f64(acc), row_scale<FP8>(q_scale, b), gs, 0);
+    if (lane == 0) S[(long long)b * ldS + n] = e;
   }
 }
 
@@ -895,7 +886,7 @@ __global__ __launch_bounds__(256) void knn_exact_scores_kernel(
 __global__ __launch_bounds__(256) void topk_merge_kernel(
     const float* __restrict__ vals, const int32_t* __restrict__ idxs, int shards, int B, int k,
     float* __restrict__ out_val, int32_t* __restrict__ out_idx) {
-  __shared__ SelectSmem sm;
+  __shared__ SelectState<SEL_CAP, 128> sm;
   const int b = blockIdx.x;
   const int L = shards * k;
   unsigned long long keys[16];
@@ -903,18 +894,12 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(
   for (int i = 0; i < 16; ++i) {
     const int p = i * 256 + (int)threadIdx.x;
     const int pc = p < L ? p : L - 1;
-    const int s = pc / k, j = pc % k;
-    const long long o = ((long long)s * B + b) * k + j;
+    const long long o = ((long long)(pc / k) * B + b) * k + pc % k;
     const int id = idxs[o];
-    const float val = vals[o];
-    keys[i] = (p < L && id >= 0) ? make_key(val, id) : KEY_DEAD;
+    keys[i] = candidate_key(vals[o], id, p < L);
   }
-  block_select(keys, k, sm);
-  if ((int)threadIdx.x < k) {
-    const unsigned long long key = sm.outk[threadIdx.x];
-    out_val[(long long)b * k + threadIdx.x] = key == KEY_DEAD ? -INFINITY : key_val(key);
-    out_idx[(long long)b * k + threadIdx.x] = key == KEY_DEAD ? -1 : key_idx(key);
-  }
+  block_select<256>(keys, k, sm);
+  if ((int)threadIdx.x < k) store_entry(sm.outk[threadIdx.x], out_val, out_idx, (long long)b * k + threadIdx.x);
 }
 
 // ---------------------------------------------------------------------------------------------
