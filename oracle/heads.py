@@ -21,7 +21,7 @@ import torch
 import torch.nn.functional as F
 
 U = 2.0 ** -24
-MAX_SLICES = 64          # no form of the first layer splits K into more slices (pick_slices / VPR_POSE_KS <= 64)
+MAX_SLICES = 64          # no form of the first layer splits K into more slices (pose_f32_plan, pose_split_plan / VPR_POSE_KS <= 64)
 
 
 def _normalize_pair(out: torch.Tensor, off: int) -> torch.Tensor:
@@ -186,7 +186,7 @@ SPLIT_K_EDGE_CASES = ((5, 32, 16, 4, 2, None), (3, 96, 16, 2, 0, None), (65, 224
 
 
 def split_case_slices(D: int, ks) -> int:
-    """Slab count of the split forms at hidden = 16, B <= 130 (pick_slices_split: at least 8 K-steps per slice)."""
+    """Slab count of the split forms at hidden = 16, B <= 130 (pose_split_plan: at least 8 K-steps per slice)."""
     return ks if ks else max(1, min(32, (D // 32) // 8))
 
 

@@ -147,6 +147,45 @@ def test_split_entry_point_writes_every_slab_it_reads(dev, tune):
         assert bool(torch.isnan(ws[-4096:]).all())                     # nothing written past the slabs
 
 
+@pytest.mark.parametrize("variant", [None, 1], ids=["frag", "counters"])
+def test_fused_entry_point_writes_every_slab_it_reads(dev, tune, variant):
+    """The same for vpr_pose_head_fused in both of its forms, on the tile-contiguous slabs: the counter area at the head of
+    the workspace zero, everything after it NaN.  One writer (the first-layer kernel) and two readers (the epilogue launch,
+    the arrival-counter finisher) have to agree on the tile layout; the counters are left zero and nothing is written past
+    the workspace the query asks for."""
+    from vpr_amd import _lib, ops
+    L = _lib.lib()
+    form = "counters" if variant == 1 else "frag"
+    for B, D, hidden, ks in ((65, 96, 48, None), (130, 544, 80, None), (5, 128, 16, 3)):
+        tune("VPR_POSE_VARIANT", variant)
+        tune("VPR_POSE_KS", ks)
+        cpu = oheads.head_case_inputs(B, D, hidden, 4, 5000 + B, 2)
+        x, W1, b1, W2, b2 = _to(dev, cpu)
+        hi, lo = ops._pack_w1_planes(W1, True)
+        need, cnt = L.vpr_pose_head_fused_workspace_bytes(B, D, hidden), L.vpr_pose_head_fused_counter_bytes(B, D, hidden)
+        assert 0 < cnt < need and cnt % 4 == 0 and need % 4 == 0
+        ws = torch.full((need // 4 + 4096,), float("nan"), dtype=torch.float32, device=dev)
+        ws[:cnt // 4].view(torch.int32).zero_()
+        out = torch.full((B, 4), float("nan"), dtype=torch.float32, device=dev)
+        st = L.vpr_pose_head_fused(ops._ptr(x), ops._ptr(hi), ops._ptr(lo), ops._ptr(b1), ops._ptr(W2), ops._ptr(b2), ops._ptr(out),
+                                   B, D, hidden, 4, 2, ops._ptr(ws), ws.numel() * 4, ops._stream())
+        assert st == 0
+        _check(out, cpu, form, 2, oheads.split_case_slices(D, ks), f"direct fused B={B} D={D} hidden={hidden}")
+        assert torch.equal(out, ops.pose_head(x, W1, b1, W2, b2, 2, fused=True))
+        assert bool(torch.isnan(ws[-4096:]).all())                     # nothing written past the workspace
+        assert int(ws[:cnt // 4].view(torch.int32).abs().sum()) == 0   # the counters are zero again
+
+
+@pytest.mark.parametrize("B,D,hidden,ks", [(65, 544, 80, None), (130, 96, 208, None), (5, 128, 16, 3), (2, 1056, 16, 17)])
+def test_fragment_order_form_gives_the_bits_of_the_split_form(dev, tune, B, D, hidden, ks):
+    """"frag" and "split" run the same first-layer routine (slice count, per-wave K partition, MFMA order, four-way sum) and
+    the same epilogue; they differ in where a weight fragment is read and where a finished block is stored, so their outputs
+    are the same bits.  ("split8" and "counters" add in other orders.)"""
+    args = _to(dev, oheads.head_case_inputs(B, D, hidden, 4, 5500 + B, 2))
+    tune("VPR_POSE_KS", ks)
+    assert torch.equal(_run(dev, tune, "frag", args, 2), _run(dev, tune, "split", args, 2))
+
+
 # ------------------------------------------------------------------------------------------------ outputs and the pair
 @pytest.mark.parametrize("n_out", range(1, 9))
 def test_n_out_and_pair_offsets(dev, tune, n_out):

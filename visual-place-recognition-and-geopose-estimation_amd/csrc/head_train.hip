@@ -50,8 +50,6 @@ __global__ __launch_bounds__(256) void head_fwd_partial_kernel(
   const int nsteps = D >> 4;
   const int s_begin = ks * steps_per_slice;
   const int s_end = min(nsteps, s_begin + steps_per_slice);
-  // operand maps of v_mfma_f32_16x16x4_f32: A[row = lane&15][k = lane>>4], B[k = lane>>4][col = lane&15]; a lane loads 4
-  // consecutive k (one float4) and feeds element t to MFMA t — A and B use the same k permutation, so it cancels.
   const int r = lane & 15, kg = lane >> 4;
   const int brow = min(b0 + r, B - 1);
   const long long row = idx ? (long long)idx[brow] : (long long)brow;
@@ -59,43 +57,13 @@ __global__ __launch_bounds__(256) void head_fwd_partial_kernel(
   const float4* wa = reinterpret_cast<const float4*>(W1 + (long long)(h0 + r) * D) + kg;
   const float4* wb = reinterpret_cast<const float4*>(W1 + (long long)(h0 + 16 + r) * D) + kg;
   f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-  constexpr int STRIDE = WIDE ? 1 : 4;                       // k-steps between two steps of one wave
-  const int first = WIDE ? 0 : wave;
-  for (int base = s_begin; base < s_end; base += STRIDE * HT_CH) {     // uniform per workgroup
-    float4 a[HT_CH], w0[HT_CH], w1[HT_CH];
-#pragma unroll
-    for (int i = 0; i < HT_CH; ++i) {
-      const int s = min(base + first + STRIDE * i, s_end - 1);
-      a[i] = xa[s * 4];
-      w0[i] = wa[s * 4];
-      w1[i] = wb[s * 4];
-    }
-#pragma unroll
-    for (int i = 0; i < HT_CH; ++i) {
-      if (base + first + STRIDE * i < s_end) {   // wave-uniform
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].x, w0[i].x, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].x, w1[i].x, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].y, w0[i].y, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].y, w1[i].y, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].z, w0[i].z, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].z, w1[i].z, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].w, w0[i].w, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].w, w1[i].w, acc1, 0, 0, 0);
-      }
-    }
-  }
-  // C/D: col (hidden) = lane&15, row (batch) = 4*(lane>>4) + e
+  const SlabRowMajor slab{part, B, hidden};
   if constexpr (WIDE) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int b = b0 + 4 * kg + e;
-      if (b < B) {
-        float* p = part + ((long long)ks * B + b) * hidden + h0;
-        p[r] = acc0[e];
-        p[16 + r] = acc1[e];
-      }
-    }
+    mfma_f32_slice<HT_CH, 1>(xa, wa, wb, 0, s_begin, s_end, acc0, acc1);
+    mfma_f32_store_rows(slab, ks, b0, h0, lane, acc0, acc1);
   } else {
+    mfma_f32_slice<HT_CH, 4>(xa, wa, wb, wave, s_begin, s_end, acc0, acc1);     // k-steps round robin over the four waves
+    // C/D: col (hidden) = lane&15, row (batch) = 4*(lane>>4) + e
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       red[wave][(4 * kg + e) * HT_HT + r] = acc0[e];
@@ -104,7 +72,7 @@ __global__ __launch_bounds__(256) void head_fwd_partial_kernel(
     __syncthreads();
     for (int t = threadIdx.x; t < HT_BT * HT_HT; t += 256) {
       const int b = b0 + (t >> 5);
-      if (b < B) part[((long long)ks * B + b) * hidden + h0 + (t & 31)] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+      if (b < B) *slab.at(ks, b, h0 + (t & 31)) = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
     }
   }
 }

@@ -32,6 +32,13 @@ __device__ __forceinline__ uint16_t f32_to_bf16_bits(float f) {
   return __builtin_bit_cast(uint16_t, h);
 }
 
+// v = hi + lo to 2^-17 relative: hi = bf16(v), lo = bf16(v - hi), both round-to-nearest-even (the packed W1 planes of the
+// pose head and the x operand it splits in registers).
+__device__ __forceinline__ void split_hi_lo(float v, uint16_t& hi, uint16_t& lo) {
+  hi = f32_to_bf16_bits(v);
+  lo = f32_to_bf16_bits(v - bf16_bits_to_f32(hi));
+}
+
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() compiles to s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier,
 // i.e. it also drains every global load the wave has in flight; a kernel that wants its global loads to keep flying
 // across barriers (the compiler still waits for each loaded register before its first use) uses this one.
@@ -126,6 +133,74 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1
     k1 += 0xBB67AE85u;
   }
   return c;
+}
+
+// ---- split-K slabs of the heads' first layer ---------------------------------------------------------------
+// A slab holds one K-slice's partial sums of x W1^T.  Two layouts; at(slice, b, h) is the address of hidden unit h of batch
+// row b in slab `slice` (the four units of an aligned group of 4 are contiguous in both), slice_stride() the distance in
+// floats between the same element of two consecutive slabs.  Every writer and reader of a slab addresses it through these.
+struct SlabRowMajor {        // part[slice][B][hidden]
+  float* part; int B, hidden;
+  __device__ __forceinline__ float* at(int slice, int b, int h) const { return part + ((long long)slice * B + b) * hidden + h; }
+  __device__ __forceinline__ long long slice_stride() const { return (long long)B * hidden; }
+};
+struct SlabTiles {           // part[slice][mtiles][ntiles][64 rows][64 cols]: a reader of one (batch, hidden) tile sees 16 KB runs
+  float* part; int mtiles, ntiles;
+  __device__ __forceinline__ float* at(int slice, int b, int h) const {
+    return part + (((long long)slice * mtiles + (b >> 6)) * ntiles + (h >> 6)) * 4096 + (b & 63) * 64 + (h & 63);
+  }
+  __device__ __forceinline__ long long slice_stride() const { return (long long)mtiles * ntiles * 4096; }
+};
+
+// ---- exact-f32 MFMA over one K-slice (v_mfma_f32_16x16x4_f32 == an fmaf chain) ------------------------------
+// A wave's 16 rows x 32 columns (acc0: columns 0-15, acc1: 16-31) over the k-steps first, first + STRIDE, ... of
+// [s_begin, s_end), a step being 16 of K.  Operand maps of 16x16x4: A[row = lane&15][k = lane>>4], B[k = lane>>4][col =
+// lane&15]; a lane loads 4 consecutive k (one float4) and feeds element t to MFMA t — A and B use the same k permutation, so
+// it cancels.  xa / wa / wb are the lane's float4 streams of its x row and of its two weight rows, already offset by the
+// lane's k-group (lane>>4); step s is element [4 s].  CH steps (3 x 16 B per lane each) are requested before their MFMAs, so a
+// slice is a few round trips to HBM/L2 instead of one per step; the guard is wave-uniform.
+template <int CH, int STRIDE>
+__device__ __forceinline__ void mfma_f32_slice(const float4* xa, const float4* wa, const float4* wb, int first, int s_begin,
+                                               int s_end, f32x4& acc0, f32x4& acc1) {
+  for (int base = s_begin; base < s_end; base += STRIDE * CH) {     // uniform per workgroup
+    float4 a[CH], w0[CH], w1[CH];
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+      const int s = min(base + first + STRIDE * i, s_end - 1);
+      a[i] = xa[s * 4];
+      w0[i] = wa[s * 4];
+      w1[i] = wb[s * 4];
+    }
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+      if (base + first + STRIDE * i < s_end) {
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].x, w0[i].x, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].x, w1[i].x, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].y, w0[i].y, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].y, w1[i].y, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].z, w0[i].z, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].z, w1[i].z, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].w, w0[i].w, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].w, w1[i].w, acc1, 0, 0, 0);
+      }
+    }
+  }
+}
+
+// The wave's accumulators of mfma_f32_slice to slab `slice`, batch rows b0 .. b0+15 (those below B), hidden units h0 .. h0+31.
+// C/D: col (hidden) = lane&15, row (batch) = 4*(lane>>4) + e.
+__device__ __forceinline__ void mfma_f32_store_rows(const SlabRowMajor& slab, int slice, int b0, int h0, int lane,
+                                                    const f32x4& acc0, const f32x4& acc1) {
+  const int r = lane & 15, kg = lane >> 4;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int b = b0 + 4 * kg + e;
+    if (b < slab.B) {
+      float* p = slab.at(slice, b, h0);
+      p[r] = acc0[e];
+      p[16 + r] = acc1[e];
+    }
+  }
 }
 
 }  // namespace vpr
