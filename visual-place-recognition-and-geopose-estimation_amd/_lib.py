@@ -148,6 +148,14 @@ EXTENSION_PROTOTYPES = {
     "vpr_retrieval_pose": (c_int, [_P, _P, c_int, c_int, _P, c_longlong, c_int, c_double, _P, c_double, _P,
                                    _P, _P, _P, _P, _P]),
 }
+# include/vpr_amd_expand.h, a table of its own beside the one above
+EXPAND_PROTOTYPES = {
+    # q vals idx B D k | rows row_scales n_local index_base | n_use alpha q_weight add_query | partial out_f32 out_bf16 | stream
+    "vpr_query_expand": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, c_int, c_int, c_int, c_double, c_double, c_int,
+                                 _P, _P, _P, _P]),
+    # partials R q B D | out_f32 out_bf16 | stream
+    "vpr_query_expand_finish": (c_int, [_P, c_int, _P, c_int, c_int, _P, _P, _P]),
+}
 
 
 def library_path() -> str:
@@ -166,7 +174,8 @@ def lib() -> ctypes.CDLL:
                 "Build it with `python -c \"import __graft_entry__ as g; g.build()\"` "
                 "or `make -C visual-place-recognition-and-geopose-estimation_amd/csrc`.")
         handle = ctypes.CDLL(path)
-        for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(EXTENSION_PROTOTYPES.items()):
+        for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(EXTENSION_PROTOTYPES.items())
+                                          + list(EXPAND_PROTOTYPES.items())):
             fn = getattr(handle, name)   # AttributeError if a declared symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

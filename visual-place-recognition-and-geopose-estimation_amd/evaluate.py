@@ -366,7 +366,7 @@ def retrieval_metrics(vals: torch.Tensor, idx: torch.Tensor, labels: np.ndarray,
 def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv_path: str, image_dir: str, *, k: int = 10,
                                tau: float = 25.0, mode: str = "top1", batch_size: int = 64, device: str = "cuda", graph: bool = True,
                                image_size: int = 224, rank: int = 0, world: int = 1, group=None, verbose: bool = True,
-                               on_device: bool = False) -> dict:
+                               on_device: bool = False, query_expansion=None) -> dict:
     """Validation split through descriptor -> sharded cosine top-k -> label transfer:
       pose      (lat, lon, angle) of the best match, or the softmax-weighted mean of the k matches (gallery.label_transfer);
       final_loss on lat/lon with the validation scripts' formula (dinov2salad_validation.py:101), MAAE on the angle
@@ -376,7 +376,9 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
     With world > 1 every rank runs this with its shard (load_gallery_shard) and its share of the queries is gathered by
     ShardedGallery.search_local_queries; the metrics are then those of this rank's queries.
     on_device: the metrics come from the k neighbours alone, on the GPU (retrieval_metrics) — for galleries where the host
-    path's [Q, N] arrays do not fit."""
+    path's [Q, N] arrays do not fit.
+    query_expansion: None, or (n_use, alpha) / a dict with n_use and any of alpha, q_weight, rounds: every batch is searched,
+    expanded on the device (ShardedGallery.search_expanded) and searched again; the metrics are those of the last search."""
     from . import gallery as G
     from .retrieval import ShardedGallery
     dev = torch.device(device)
@@ -394,7 +396,7 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
     fwd = GraphedForward(features, module=extractor) if graph and dev.type == "cuda" else features
     for idxs, u8 in _batches(image_dir, names, batch_size, dev):
         _, d16 = fwd(prep(u8))
-        v, i = sg.search_local_queries(d16, kk)
+        v, i = sg.search_local_queries(d16, kk, query_expansion)
         sel = torch.tensor(idxs, device=dev)
         vals[sel], idx[sel] = v, i
     res = {"filenames": names}

@@ -147,6 +147,41 @@ def positives_by_region(query_region: np.ndarray, gallery_region: np.ndarray) ->
     return [np.nonzero(g == r)[0] for r in np.asarray(query_region)]
 
 
+# ------------------------------------------------------------------------- gallery augmentation
+@torch.no_grad()
+def augment_gallery(sharded: ShardedGallery, n_use: int, alpha: float = 3.0, batch: int = 512):
+    """Database-side augmentation (DBA): every gallery row becomes the L2-normalised sum of score^alpha * row over its n_use
+    best matches in the WHOLE gallery — the row itself is the first of them (it finds itself at rank 0), so the query term
+    is off (q_weight = 0) and n_use counts the row.  Returns this rank's new rows in the shard's own format: bf16
+    [n_local, D], or (e4m3 bytes [n_local, D], scales [n_local]) through quantize_fp8_rows.  Run once, offline; search the
+    result like any gallery.
+    Every rank runs ceil(ceil(N / world) / batch) iterations of {gather, search, expand}, so a sharded gallery stays in
+    lockstep; a short (or empty) last batch is padded with copies of the rank's row 0, whose results are dropped — not with
+    zero rows, whose all-tied scores would count as uncertified searches."""
+    rows, scales = sharded.rows, sharded.scales
+    n_local, D = rows.shape
+    if n_local < 1:
+        raise ValueError("augment_gallery: this rank's shard is empty")
+    world = sharded.world if sharded.collective else 1
+    per_rank = -(-sharded.n_total // max(sharded.world, 1))
+    out = torch.empty((n_local, D), dtype=torch.bfloat16, device=rows.device)
+    for it in range(-(-per_rank // batch)):
+        lo, hi = min(it * batch, n_local), min((it + 1) * batch, n_local)
+        sel = torch.zeros(batch, dtype=torch.long, device=rows.device)
+        sel[:hi - lo] = torch.arange(lo, hi, device=rows.device)
+        q = rows[sel]
+        if scales is not None:
+            q = (q.view(torch.float8_e4m3fn).float() * scales[sel, None]).to(torch.bfloat16)
+        q_all = sharded.gather_queries(q.contiguous())
+        v, i = sharded.search(q_all, n_use)
+        e = sharded.expand(q_all, v, i, n_use, alpha, 0.0)
+        first = sharded.rank * batch if world > 1 else 0
+        out[lo:hi] = e[first:first + hi - lo]
+    if scales is None:
+        return out
+    return ops.quantize_fp8_rows(out.float())
+
+
 # ------------------------------------------------------------------- hipGraph-captured retrieval
 class GraphedLocalTopK:
     """Local shard search captured once into a HIP graph and replayed per batch (BASELINE config 5:

@@ -671,6 +671,74 @@ def retrieval_pose(vals: torch.Tensor, idx: torch.Tensor, labels_dev: torch.Tens
     return pose64, pose4, hit_tau, hit_region
 
 
+def _expand_check(what: str, q, vals, idx, n_use: int, alpha: float, q_weight: float) -> None:
+    _need(q, torch.bfloat16, "q", 2)
+    _need(vals, torch.float32, "vals", 2)
+    _need(idx, torch.int32, "idx", 2)
+    if vals.shape != idx.shape:
+        raise RuntimeError(f"{what}: vals and idx shapes differ")
+    if vals.shape[0] != q.shape[0]:
+        raise RuntimeError(f"{what}: q and vals disagree on B")
+    if not 1 <= int(n_use) <= vals.shape[1]:
+        raise RuntimeError(f"{what}: n_use must be in 1..k (k = {vals.shape[1]})")
+    if not alpha >= 0.0 or not q_weight >= 0.0:
+        raise RuntimeError(f"{what}: alpha and q_weight must be >= 0")
+
+
+def query_expand(q: torch.Tensor, vals: torch.Tensor, idx: torch.Tensor, rows: torch.Tensor,
+                 scales: Optional[torch.Tensor] = None, index_base: int = 0, n_use: Optional[int] = None, alpha: float = 3.0,
+                 q_weight: float = 1.0, add_query: bool = True, *, finish: bool = False,
+                 partial: Optional[torch.Tensor] = None):
+    """One shard's contribution to the expanded queries (include/vpr_amd_expand.h): q bf16 [B, D], vals f32 / idx int32 [B, k]
+    (k <= 128) from a search, rows = the shard, bf16 [n_local, D] or uint8 e4m3 bytes with per-row f32 `scales`, owning global
+    rows index_base ...  Returns partial f32 [B, D] = add_query * q_weight * q + sum over the local neighbours j < n_use of
+    vals^alpha * row (n_use None: all k).
+    finish=True (a gallery of one shard): the same call normalises; returns (out_f32 [B, D] unit rows, out_bf16 [B, D]).
+    partial: the f32 [B, D] buffer to write; None: with finish=True a cached scratch buffer of the current stream (pinned
+    while a graph is captured, like every workspace), else a new tensor."""
+    n_use = vals.shape[1] if n_use is None and isinstance(vals, torch.Tensor) and vals.dim() == 2 else n_use
+    _expand_check("query_expand", q, vals, idx, n_use, alpha, q_weight)
+    fp8 = isinstance(rows, torch.Tensor) and rows.dtype == torch.uint8
+    _need(rows, torch.uint8 if fp8 else torch.bfloat16, "rows", 2)
+    if fp8 != (scales is not None):
+        raise RuntimeError("query_expand: uint8 (e4m3) rows come with per-row scales, bf16 rows without")
+    if fp8:
+        _need(scales, torch.float32, "scales", 1)
+        if scales.numel() != rows.shape[0]:
+            raise RuntimeError("query_expand: scales: one per row")
+    B, D = q.shape
+    if rows.shape[1] != D:
+        raise RuntimeError("query_expand: q and rows disagree on D")
+    dev = q.device
+    if partial is None:
+        partial = (workspace("query_expand", B * D * 4, dev)[:B * D * 4].view(torch.float32).view(B, D) if finish
+                   else torch.empty((B, D), dtype=torch.float32, device=dev))
+    else:
+        _need(partial, torch.float32, "partial", 2)
+        if partial.shape != (B, D):
+            raise RuntimeError("query_expand: partial must be [B, D]")
+    out_f32 = torch.empty((B, D), dtype=torch.float32, device=dev) if finish else None
+    out_bf16 = torch.empty((B, D), dtype=torch.bfloat16, device=dev) if finish else None
+    _call("vpr_query_expand", _ptr(q), _ptr(vals), _ptr(idx), B, D, vals.shape[1], _ptr(rows), _ptr(scales), rows.shape[0],
+          int(index_base), int(n_use), float(alpha), float(q_weight), int(bool(add_query)), _ptr(partial), _ptr(out_f32),
+          _ptr(out_bf16), _stream())
+    return (out_f32, out_bf16) if finish else partial
+
+
+def query_expand_finish(partials: torch.Tensor, q: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Shard partials f32 [R, B, D] (R <= 64, summed in shard order) + the searched queries q bf16 [B, D] -> (out_f32 [B, D]
+    unit rows, out_bf16 [B, D] = its bf16 rounding); a query whose sum is zero or not finite comes back as q."""
+    _need(partials, torch.float32, "partials", 3)
+    _need(q, torch.bfloat16, "q", 2)
+    R, B, D = partials.shape
+    if q.shape != (B, D):
+        raise RuntimeError("query_expand_finish: partials [R, B, D] and q [B, D] disagree")
+    out_f32 = torch.empty((B, D), dtype=torch.float32, device=q.device)
+    out_bf16 = torch.empty((B, D), dtype=torch.bfloat16, device=q.device)
+    _call("vpr_query_expand_finish", _ptr(partials), R, _ptr(q), B, D, _ptr(out_f32), _ptr(out_bf16), _stream())
+    return out_f32, out_bf16
+
+
 # ------------------------------------------------------------------------------------------ heads
 _POSE_PLANES = cache(12)
 

@@ -57,6 +57,18 @@ class HipEngine:
     def merge(self, vals, idxs):
         return torch.ops.vpr.topk_merge(vals, idxs)
 
+    def expand_partial(self, q, vals, idx, rows, scales, index_base, n_use, alpha, q_weight, add_query):
+        """This shard's f32 [B, D] share of the expanded queries (vpr_query_expand)."""
+        return torch.ops.vpr.query_expand(q, vals, idx, rows, scales, index_base, n_use, alpha, q_weight, add_query)
+
+    def expand_finish(self, partials, q):
+        """Shard partials [R, B, D] -> the expanded queries, bf16 [B, D] (vpr_query_expand_finish)."""
+        return torch.ops.vpr.query_expand_finish(partials, q)[1]
+
+    def expand_whole(self, q, vals, idx, rows, scales, index_base, n_use, alpha, q_weight):
+        """A gallery of one shard: partial and finish in one call; the partial lives in the stream's cached workspace."""
+        return ops.query_expand(q, vals, idx, rows, scales, index_base, n_use, alpha, q_weight, True, finish=True)[1]
+
 
 def pose_labels(labels, device) -> torch.Tensor:
     """The label table for torch.ops.vpr.retrieval_pose: a [N, 4] float64 tensor on `device` (gallery.device_labels /
@@ -74,6 +86,24 @@ def pose_scaler(scaler):
     if hasattr(scaler, "mean_"):
         return [float(scaler.mean_[0]), float(scaler.mean_[1]), float(scaler.scale_[0]), float(scaler.scale_[1])]
     return [float(x) for x in scaler]
+
+
+def expansion_params(expand) -> Optional[dict]:
+    """None, (n_use, alpha), or a dict with n_use and any of alpha, q_weight, rounds -> the keyword arguments of
+    ShardedGallery.search_expanded after `k` (defaults alpha 3, q_weight 1, rounds 1)."""
+    if expand is None:
+        return None
+    if not isinstance(expand, dict):
+        n_use, alpha = expand
+        expand = {"n_use": n_use, "alpha": alpha}
+    unknown = set(expand) - {"n_use", "alpha", "q_weight", "rounds"}
+    if unknown or "n_use" not in expand:
+        raise ValueError(f"expand: (n_use, alpha) or a dict with n_use and any of alpha, q_weight, rounds; got {expand}")
+    out = {"n_use": int(expand["n_use"]), "alpha": float(expand.get("alpha", 3.0)),
+           "q_weight": float(expand.get("q_weight", 1.0)), "rounds": int(expand.get("rounds", 1))}
+    if out["rounds"] < 1:
+        raise ValueError("expand: rounds must be >= 1")
+    return out
 
 
 def all_gather_topk(v: torch.Tensor, i: torch.Tensor, world: int, group=None):
@@ -152,10 +182,39 @@ class ShardedGallery:
         vs, is_ = all_gather_topk(v, i, self.world, self.group)
         return self.engine.merge(vs, is_)
 
-    def search_local_queries(self, q_local: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Data-parallel form: each rank contributes B_local queries and gets back its own rows."""
+    def expand(self, q_all: torch.Tensor, vals: torch.Tensor, idx: torch.Tensor, n_use: int, alpha: float = 3.0,
+               q_weight: float = 1.0) -> torch.Tensor:
+        """Query expansion (alpha-QE, include/vpr_amd_expand.h): q_all [B, D] bf16 and its merged top-k (vals, idx) [B, k], the
+        same on every rank -> bf16 [B, D], the same on every rank: normalise(q_weight * q + sum_{j < n_use} vals_j^alpha * row_j).
+        Every rank adds up the neighbour rows it owns (rank 0 also the query term); the f32 partials travel in ONE all-gather and
+        are added in rank order — an all-reduce would leave the order of the sum to the collective.  A query with nothing to
+        add (or a non-finite sum) comes back unchanged."""
+        vals, idx = vals.contiguous(), idx.contiguous()
+        if not self.collective:
+            return self.engine.expand_whole(q_all, vals, idx, self.rows, self.scales, self.index_base, n_use, alpha, q_weight)
+        part = self.engine.expand_partial(q_all, vals, idx, self.rows, self.scales, self.index_base, n_use, alpha, q_weight,
+                                          self.rank == 0)
+        B, D = part.shape
+        parts = torch.empty((self.world * B, D), dtype=torch.float32, device=part.device)
+        dist.all_gather_into_tensor(parts, part, group=self.group)
+        return self.engine.expand_finish(parts.view(self.world, B, D), q_all)
+
+    def search_expanded(self, q_all: torch.Tensor, k: int, n_use: int, alpha: float = 3.0, q_weight: float = 1.0,
+                        rounds: int = 1, ws=None, ws2=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """search -> expand -> search, `rounds` times: the (vals, idx) of the last search.  The expanded bf16 queries go through
+        `search` like any others (an fp8 shard quantises them there).  ws / ws2: kNN workspaces of the first and of the later
+        searches (ws2 None: ws again)."""
+        v, i = self.search(q_all, k, ws)
+        for _ in range(rounds):
+            q_all = self.expand(q_all, v, i, n_use, alpha, q_weight)
+            v, i = self.search(q_all, k, ws if ws2 is None else ws2)
+        return v, i
+
+    def search_local_queries(self, q_local: torch.Tensor, k: int, expand=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Data-parallel form: each rank contributes B_local queries and gets back its own rows.
+        expand: None, or the query expansion to search with (expansion_params)."""
         q_all = self.gather_queries(q_local)
-        v, i = self.search(q_all, k)
+        v, i = self.search(q_all, k) if expand is None else self.search_expanded(q_all, k, **expansion_params(expand))
         b = q_local.shape[0]
         return v[self.rank * b:(self.rank + 1) * b], i[self.rank * b:(self.rank + 1) * b]
 
@@ -182,11 +241,14 @@ class GraphedRetrieval:
     Replay: copy the queries into `self.q`, `replay()`, read `self.vals` / `self.idx` (this rank's B_local rows).
     labels (the full [N, 4] label table, gallery.device_labels): the graph also runs torch.ops.vpr.retrieval_pose on this
     rank's merged rows; `self.pose64` ([B_local, 3] f64: lat, lon, angle_deg) and `self.pose4` ([B_local, 4] f32, the fused
-    head's format under `scaler`) are rewritten by every replay like vals / idx.  Without labels both stay None."""
+    head's format under `scaler`) are rewritten by every replay like vals / idx.  Without labels both stay None.
+    expand ((n_use, alpha) or a dict, expansion_params): the graph holds the two-pass form, ShardedGallery.search_expanded —
+    vals / idx and the poses are those of the last search, which runs in a kNN workspace of its own."""
 
     def __init__(self, gallery: ShardedGallery, batch_local: int, k: int, labels=None, mode: str = "top1",
-                 temperature: float = 0.01, scaler=None):
+                 temperature: float = 0.01, scaler=None, expand=None):
         self.g, self.k, self.b = gallery, k, batch_local
+        self.expand = expansion_params(expand)
         self.labels = None if labels is None else pose_labels(labels, gallery.rows.device)
         self.mode, self.temperature, self.scaler = mode, temperature, pose_scaler(scaler)
         self.pose64 = self.pose4 = None
@@ -200,6 +262,7 @@ class GraphedRetrieval:
         self.q = torch.zeros((batch_local, D), dtype=torch.bfloat16, device=dev)
         B = batch_local * (gallery.world if gallery.collective else 1)
         self.ws = ops.knn_workspace(B, rows.shape[0], D, k, dev)
+        self.ws2 = None if self.expand is None else ops.workspace("knn_expanded", self.ws.numel(), dev)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         counted = gallery.uncertified.clone() if gallery.uncertified is not None else None
@@ -231,7 +294,10 @@ class GraphedRetrieval:
     def _run(self):
         g = self.g
         q_all = g.gather_queries(self.q)
-        v, i = g.search(q_all, self.k, self.ws)
+        if self.expand is None:
+            v, i = g.search(q_all, self.k, self.ws)
+        else:
+            v, i = g.search_expanded(q_all, self.k, ws=self.ws, ws2=self.ws2, **self.expand)
         lo = g.rank * self.b if g.collective else 0
         v, i = v[lo:lo + self.b], i[lo:lo + self.b]
         if self.labels is not None:

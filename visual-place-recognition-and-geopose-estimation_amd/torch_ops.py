@@ -8,6 +8,7 @@ that seam, so the HIP hot path is visible to PyTorch's dispatcher like any other
     torch.ops.vpr.salad_aggregate_train                (training mode: Dropout active in the score / cluster MLPs)
     torch.ops.vpr.knn_topk / knn_topk_fp8 / topk_merge
     torch.ops.vpr.retrieval_pose                       (geopose and first-hit ranks from the merged top-k)
+    torch.ops.vpr.query_expand / query_expand_finish   (alpha-QE / DBA: weighted mean of a query and its best rows)
     torch.ops.vpr.pose_head / ln_meanpool_head
     torch.ops.vpr.head_train_epoch                     (head-only fine-tuning pass; mutates parameters and AdamW moments)
     torch.ops.vpr.head_train_epoch_dropout             (the same pass with Dropout(p) after the ReLU, training mode)
@@ -186,6 +187,32 @@ def _(vals, idx, labels_dev, mode="top1", temperature=0.01, q_targets=None, tau=
             vals.new_empty((B,), dtype=torch.int32), vals.new_empty((B,), dtype=torch.int32))
 
 
+@torch.library.custom_op("vpr::query_expand", mutates_args=())
+def query_expand(q: Tensor, vals: Tensor, idx: Tensor, rows: Tensor, scales: Optional[Tensor], index_base: int, n_use: int,
+                 alpha: float = 3.0, q_weight: float = 1.0, add_query: bool = True) -> Tensor:
+    """One shard's partial sum of the expanded queries: q bf16 [B, D], a top-k list [B, k], the shard's rows (bf16, or uint8
+    e4m3 bytes + per-row f32 scales) -> f32 [B, D] = add_query * q_weight * q + sum_j vals_j^alpha * row_j over the n_use
+    best neighbours this shard owns.  vpr_query_expand."""
+    return ops.query_expand(q, vals, idx, rows, scales, index_base, n_use, alpha, q_weight, add_query)
+
+
+@query_expand.register_fake
+def _(q, vals, idx, rows, scales, index_base, n_use, alpha=3.0, q_weight=1.0, add_query=True):
+    return q.new_empty(q.shape, dtype=torch.float32)
+
+
+@torch.library.custom_op("vpr::query_expand_finish", mutates_args=())
+def query_expand_finish(partials: Tensor, q: Tensor) -> Tuple[Tensor, Tensor]:
+    """Shard partials f32 [R, B, D] -> (expanded queries f32 [B, D], unit rows; their bf16 rounding), summed in shard order; a
+    query whose sum is zero or not finite stays q.  vpr_query_expand_finish."""
+    return ops.query_expand_finish(partials, q)
+
+
+@query_expand_finish.register_fake
+def _(partials, q):
+    return q.new_empty(q.shape, dtype=torch.float32), q.new_empty(q.shape, dtype=torch.bfloat16)
+
+
 # ------------------------------------------------------------------------------------------------------------ heads
 @torch.library.custom_op("vpr::pose_head", mutates_args=())
 def pose_head(x: Tensor, W1: Optional[Tensor], b1: Optional[Tensor], W2: Tensor, b2: Tensor, sincos_offset: int) -> Tensor:
@@ -257,4 +284,4 @@ def _(X, Y, order, batch_size, W1, b1, W2, b2, m, v, first_step, lr, beta1, beta
 
 
 OPS = ("head_train_epoch", "head_train_epoch_dropout", "salad_aggregate", "salad_aggregate_split", "salad_aggregate_f32", "salad_aggregate_train", "knn_topk", "knn_topk_fp8", "quantize_fp8_rows",
-       "topk_merge", "pose_head", "ln_meanpool_head", "retrieval_pose")
+       "topk_merge", "pose_head", "ln_meanpool_head", "retrieval_pose", "query_expand", "query_expand_finish")
