@@ -156,6 +156,14 @@ EXPAND_PROTOTYPES = {
     # partials R q B D | out_f32 out_bf16 | stream
     "vpr_query_expand_finish": (c_int, [_P, c_int, _P, c_int, c_int, _P, _P, _P]),
 }
+# include/vpr_amd_project.h, the third table
+PROJECT_STREAM_MAX_ROWS = 128          # VPR_PROJECT_STREAM_MAX_ROWS: the largest `rows` on route 0
+PROJECT_PROTOTYPES = {
+    "vpr_project_workspace_bytes": (c_size_t, [c_int] * 3),                 # rows D d
+    "vpr_project_route": (c_int, [c_int] * 3),                              # rows D d
+    # x x_stride rows D | P c d normalize | out_f32 out_bf16 | workspace workspace_bytes | stream
+    "vpr_project_rows": (c_int, [_P, c_longlong, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+}
 
 
 def library_path() -> str:
@@ -175,7 +183,7 @@ def lib() -> ctypes.CDLL:
                 "or `make -C visual-place-recognition-and-geopose-estimation_amd/csrc`.")
         handle = ctypes.CDLL(path)
         for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(EXTENSION_PROTOTYPES.items())
-                                          + list(EXPAND_PROTOTYPES.items())):
+                                          + list(EXPAND_PROTOTYPES.items()) + list(PROJECT_PROTOTYPES.items())):
             fn = getattr(handle, name)   # AttributeError if a declared symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

@@ -305,10 +305,14 @@ def calculate_angle_validation_scores(model, val_csv_path: str, image_dir: str, 
 # directory conventions as the validation scripts, with the gallery built from the training split.
 @torch.no_grad()
 def build_gallery_from_images(extractor: DinoV2Salad, csv_path: str, image_dir: str, out_dir: str, *, fp8: bool = False,
-                              batch_size: int = 64, device: str = "cuda", image_size: int = 224, graph: bool = True) -> int:
+                              batch_size: int = 64, device: str = "cuda", image_size: int = 224, graph: bool = True,
+                              projection=None, whiten: bool = True) -> int:
     """labels CSV (`filename,timestamp,latitude,longitude,angle,Region_ID`, cleaned_dataset_files/labels_train.csv:1) +
     images -> on-disk gallery (gallery.save_gallery: bf16 rows, or e4m3 rows + per-row scales with fp8=True).
-    Preprocessing = the DINOv2+SALAD validation transform (dinov2salad_validation.py:18-22).  Returns the row count."""
+    Preprocessing = the DINOv2+SALAD validation transform (dinov2salad_validation.py:18-22).  Returns the row count.
+    projection: None, a projection.DescriptorProjection, or an int d = fit PCA (whiten: with whitening) on this gallery's own
+    descriptors (projection.fit_projection) — the rows are projected to d columns on the device (gallery.project_gallery)
+    and the projection is saved with the gallery, where calculate_retrieval_scores finds it."""
     from . import gallery as G, ops
     dev = torch.device(device)
     extractor = extractor.to(dev).to(torch.bfloat16).eval()
@@ -320,7 +324,14 @@ def build_gallery_from_images(extractor: DinoV2Salad, csv_path: str, image_dir: 
     for idxs, u8 in _batches(image_dir, names, batch_size, dev):
         desc[torch.tensor(idxs, device=dev)] = fwd(prep(u8))
     labels = df[list(G.LABEL_COLUMNS)].to_numpy(dtype=np.float64)
-    if fp8:
+    if projection is not None:
+        from .projection import fit_projection
+        d16 = desc.to(torch.bfloat16)
+        if isinstance(projection, int):
+            projection = fit_projection(d16, projection, whiten=whiten)
+        rows, scales = G.project_gallery(d16, projection, fp8=fp8)
+        G.save_gallery(out_dir, rows, labels, scales=scales, filenames=names, projection=projection)
+    elif fp8:
         rows, scales = ops.quantize_fp8_rows(desc)
         G.save_gallery(out_dir, rows, labels, scales=scales, filenames=names)
     else:
@@ -378,14 +389,16 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
     on_device: the metrics come from the k neighbours alone, on the GPU (retrieval_metrics) — for galleries where the host
     path's [Q, N] arrays do not fit.
     query_expansion: None, or (n_use, alpha) / a dict with n_use and any of alpha, q_weight, rounds: every batch is searched,
-    expanded on the device (ShardedGallery.search_expanded) and searched again; the metrics are those of the last search."""
+    expanded on the device (ShardedGallery.search_expanded) and searched again; the metrics are those of the last search.
+    A gallery saved with a projection (projection.npz) has every query batch projected on the device before its search."""
     from . import gallery as G
     from .retrieval import ShardedGallery
     dev = torch.device(device)
     extractor = extractor.to(dev).to(torch.bfloat16).eval()
     shard = G.load_gallery_shard(gallery_dir, dev, rank, world)
     # offline evaluation: unconditionally exact neighbours (queries the device certificate flags are re-run on f64 scores)
-    sg = ShardedGallery(shard.rows, shard.n_total, rank, world, group=group, scales=shard.scales, exact_fallback=True)
+    sg = ShardedGallery(shard.rows, shard.n_total, rank, world, group=group, scales=shard.scales, exact_fallback=True,
+                        projection=shard.projection)
     df = _existing_rows(val_csv_path, image_dir)
     names = df["filename"].tolist()
     prep = ResizeNormalize(image_size, "bilinear", HALF_MEAN, HALF_STD, torch.bfloat16)

@@ -8,6 +8,8 @@ On-disk format (a directory; every array is a plain .npy so shards can be memory
   scales.npy           [N] float32            (fp8 only: value = scale * fp8)
   labels.npy           [N, 4] float64         latitude, longitude, angle (deg), Region_ID
   filenames.txt        one per row (optional)
+  projection.npz       (optional) the projection.DescriptorProjection the rows went through; "d" is then the stored,
+                       projected width.  A directory without it loads as ever.
 Rank r of R loads rows [N*r/R, N*(r+1)/R) only.
 """
 from __future__ import annotations
@@ -21,9 +23,11 @@ import numpy as np
 import torch
 
 from . import ops
+from .projection import DescriptorProjection
 from .retrieval import ShardedGallery, shard_bounds
 
 LABEL_COLUMNS = ("latitude", "longitude", "angle", "Region_ID")
+PROJECTION_FILE = "projection.npz"
 
 
 @dataclass
@@ -35,12 +39,16 @@ class GalleryShard:
     index_base: int
     dtype: str
     labels_dev: Optional[torch.Tensor] = None   # [N, 4] float64 on the GPU: the same table for ops.retrieval_pose (device_labels)
+    projection: Optional["DescriptorProjection"] = None   # what the rows went through (projection.npz), or None
 
 
 def save_gallery(path: str, descriptors: torch.Tensor, labels: np.ndarray, scales: Optional[torch.Tensor] = None,
-                 filenames: Optional[Sequence[str]] = None) -> None:
-    """descriptors: [N,D] torch.bfloat16 (bf16 gallery) or torch.uint8 (+ scales: fp8 gallery)."""
+                 filenames: Optional[Sequence[str]] = None, projection: Optional[DescriptorProjection] = None) -> None:
+    """descriptors: [N,D] torch.bfloat16 (bf16 gallery) or torch.uint8 (+ scales: fp8 gallery).
+    projection: the DescriptorProjection the rows went through (project_gallery); written as projection.npz."""
     os.makedirs(path, exist_ok=True)
+    if projection is not None and projection.d != descriptors.shape[1]:
+        raise ValueError(f"projection maps to {projection.d} columns, the rows have {descriptors.shape[1]}")
     d = descriptors.detach().cpu().contiguous()
     if d.dtype == torch.bfloat16:
         arr, dtype = d.view(torch.uint16).numpy(), "bf16"
@@ -62,6 +70,11 @@ def save_gallery(path: str, descriptors: torch.Tensor, labels: np.ndarray, scale
     with open(os.path.join(path, "meta.json"), "w") as f:
         json.dump({"version": 1, "n": int(arr.shape[0]), "d": int(arr.shape[1]), "dtype": dtype,
                    "label_columns": list(LABEL_COLUMNS)}, f)
+    proj_path = os.path.join(path, PROJECTION_FILE)
+    if projection is not None:
+        projection.save(proj_path)
+    elif os.path.exists(proj_path):            # a directory written over: the old rows' projection does not describe the new ones
+        os.remove(proj_path)
 
 
 def device_labels(labels: np.ndarray, device: torch.device) -> torch.Tensor:
@@ -94,7 +107,9 @@ def load_gallery_shard(path: str, device: torch.device, rank: int = 0, world: in
         scales = torch.from_numpy(np.array(sc[lo:hi])).to(device)
     labels = np.load(os.path.join(path, "labels.npy"))
     labels_dev = _device_labels(labels, device) if device_labels else None
-    return GalleryShard(rows, scales, labels, meta["n"], lo, meta["dtype"], labels_dev)
+    proj_path = os.path.join(path, PROJECTION_FILE)
+    projection = DescriptorProjection.load(proj_path) if os.path.exists(proj_path) else None
+    return GalleryShard(rows, scales, labels, meta["n"], lo, meta["dtype"], labels_dev, projection)
 
 
 def labels_from_csv(csv_path: str) -> Tuple[np.ndarray, List[str]]:
@@ -145,6 +160,26 @@ def positives_by_distance(query_latlon: np.ndarray, gallery_latlon: np.ndarray, 
 def positives_by_region(query_region: np.ndarray, gallery_region: np.ndarray) -> List[np.ndarray]:
     g = np.asarray(gallery_region)
     return [np.nonzero(g == r)[0] for r in np.asarray(query_region)]
+
+
+# --------------------------------------------------------------------------- gallery projection
+@torch.no_grad()
+def project_gallery(rows_bf16: torch.Tensor, projection: DescriptorProjection, fp8: bool = False):
+    """Gallery rows bf16 [N, D] on the GPU through `projection` (include/vpr_amd_project.h) -> (rows, scales): unit rows
+    bf16 [N, d] and None, or with fp8 the e4m3 bytes and per-row scales that ops.quantize_fp8_rows makes of the f32 output
+    (d % 128 == 0: the e4m3 search's K-step)."""
+    if fp8 and projection.d % 128 != 0:
+        raise ValueError(f"project_gallery: an e4m3 gallery needs d % 128 == 0, got d = {projection.d}")
+    if not fp8:
+        return projection.apply(rows_bf16), None
+    P, c = projection.operands(rows_bf16.device)
+    N = rows_bf16.shape[0]
+    q = torch.empty((N, projection.d), dtype=torch.uint8, device=rows_bf16.device)
+    sc = torch.empty((N,), dtype=torch.float32, device=rows_bf16.device)
+    for lo in range(0, N, ops.PROJECT_CHUNK_ROWS):                 # the f32 rows exist one chunk at a time
+        f32, _ = ops.project_rows(rows_bf16[lo:lo + ops.PROJECT_CHUNK_ROWS], P, c, True, want_f32=True, want_bf16=False)
+        q[lo:lo + ops.PROJECT_CHUNK_ROWS], sc[lo:lo + ops.PROJECT_CHUNK_ROWS] = ops.quantize_fp8_rows(f32)
+    return q, sc
 
 
 # ------------------------------------------------------------------------- gallery augmentation
@@ -222,4 +257,5 @@ class GraphedLocalTopK:
 
 def sharded_gallery_from(shard: GalleryShard, rank: int = 0, world: int = 1, group=None) -> ShardedGallery:
     """A loaded shard (bf16 rows, or e4m3 bytes + per-row scales) as the distributed search object."""
-    return ShardedGallery(shard.rows, shard.n_total, rank, world, group=group, scales=shard.scales)
+    return ShardedGallery(shard.rows, shard.n_total, rank, world, group=group, scales=shard.scales,
+                          projection=shard.projection)

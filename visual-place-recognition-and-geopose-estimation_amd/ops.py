@@ -739,6 +739,71 @@ def query_expand_finish(partials: torch.Tensor, q: torch.Tensor) -> Tuple[torch.
     return out_f32, out_bf16
 
 
+PROJECT_CHUNK_ROWS = 65536       # rows per vpr_project_rows call: bounds the workspace for million-row inputs
+
+
+def project_rows(x: torch.Tensor, P: torch.Tensor, c: torch.Tensor, normalize: bool = True, want_f32: bool = False,
+                 want_bf16: bool = True, out=None):
+    """Descriptor projection (include/vpr_amd_project.h): x bf16 [rows, D] (unit column stride; a row stride >= D that is a
+    multiple of 8 is taken as it is), P bf16 [d, D], c f32 [d] -> z = x P^T + c, L2-normalised per row when `normalize`
+    (a row whose norm is 0 or not finite becomes +0).  Returns (out_f32 [rows, d] or None, out_bf16 [rows, d] or None); the
+    bf16 output is the RNE rounding of the f32 one.
+    out: None, or a pair (out_f32, out_bf16) of contiguous [rows, d] tensors (either None) to write instead of new ones.
+    The workspace is a cached buffer of the current stream (pinned while a graph is captured, like every workspace);
+    inputs taller than PROJECT_CHUNK_ROWS go through several calls."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("x: expected a GPU tensor (the HIP path has no CPU fallback)")
+    if x.dtype != torch.bfloat16:
+        raise RuntimeError(f"x: expected dtype {torch.bfloat16}, got {x.dtype}")
+    if x.dim() != 2:
+        raise RuntimeError(f"x: expected 2 dims, got {x.dim()}")
+    _need(P, torch.bfloat16, "P", 2)
+    _need(c, torch.float32, "c", 1)
+    rows, D = x.shape
+    d = P.shape[0]
+    if P.shape[1] != D:
+        raise RuntimeError("project_rows: x and P disagree on D")
+    if c.shape[0] != d:
+        raise RuntimeError("project_rows: P and c disagree on d")
+    if P.device != x.device or c.device != x.device:
+        raise RuntimeError("project_rows: x, P and c must live on one device")
+    if rows > 1 and (x.stride(1) != 1 or x.stride(0) < D or x.stride(0) % 8):
+        raise RuntimeError("x: expected unit column stride and a row stride >= D that is a multiple of 8")
+    if rows <= 1 and not x.is_contiguous():
+        raise RuntimeError("x: expected a contiguous tensor")
+    x_stride = x.stride(0) if rows > 1 else D
+    dev = x.device
+    if out is not None:
+        out_f32, out_bf16 = out
+        for t, dt, name in ((out_f32, torch.float32, "out_f32"), (out_bf16, torch.bfloat16, "out_bf16")):
+            if t is not None:
+                _need(t, dt, name, 2)
+                if t.shape != (rows, d):
+                    raise RuntimeError(f"project_rows: {name} must be [rows, d]")
+    else:
+        out_f32 = torch.empty((rows, d), dtype=torch.float32, device=dev) if want_f32 else None
+        out_bf16 = torch.empty((rows, d), dtype=torch.bfloat16, device=dev) if want_bf16 else None
+    if out_f32 is None and out_bf16 is None:
+        raise RuntimeError("project_rows: at least one of the f32 and bf16 outputs is needed")
+    L = _lib.lib()
+    for lo in range(0, rows, PROJECT_CHUNK_ROWS):
+        n = min(PROJECT_CHUNK_ROWS, rows - lo)
+        nbytes = L.vpr_project_workspace_bytes(n, D, d)
+        ws = workspace("project_rows", nbytes, dev)
+        _call("vpr_project_rows", ctypes.c_void_p(x.data_ptr() + 2 * lo * x_stride), x_stride, n, D, _ptr(P), _ptr(c), d,
+              int(bool(normalize)), _ptr(None if out_f32 is None else out_f32[lo:lo + n]),
+              _ptr(None if out_bf16 is None else out_bf16[lo:lo + n]), _ptr(ws), ws.numel(), _stream())
+    return out_f32, out_bf16
+
+
+def project_route(rows: int, D: int, d: int) -> int:
+    """vpr_project_route: 0 = split-K streaming, 1 = tiled; raises for shapes vpr_project_rows refuses."""
+    r = _lib.lib().vpr_project_route(int(rows), int(D), int(d))
+    if r < 0:
+        _lib.check(r, "vpr_project_route")
+    return r
+
+
 # ------------------------------------------------------------------------------------------ heads
 _POSE_PLANES = cache(12)
 

@@ -86,7 +86,7 @@ class VPRGeoPosePipeline:
             if self.labels is not None:
                 rpose = gr.pose4.clone()
         else:
-            q_all = g.gather_queries(desc16)
+            q_all = g.gather_queries(g.project_queries(desc16))      # a projected gallery: d-wide rows travel
             # knn_events: same kernels, run as the two stages of the call with HIP events around the score stage
             v, i = g.search(q_all, self.k, score_events=self.knn_events)
             if g.collective:

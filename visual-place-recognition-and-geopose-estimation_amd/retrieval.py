@@ -121,7 +121,8 @@ def all_gather_topk(v: torch.Tensor, i: torch.Tensor, world: int, group=None):
 class ShardedGallery:
     def __init__(self, local_rows: torch.Tensor, n_total: int, rank: int = 0, world: int = 1,
                  engine=None, group: Optional[dist.ProcessGroup] = None, scales: Optional[torch.Tensor] = None,
-                 norm_bound: Optional[float] = None, force_collectives: bool = False, exact_fallback: bool = False):
+                 norm_bound: Optional[float] = None, force_collectives: bool = False, exact_fallback: bool = False,
+                 projection=None):
         """local_rows: [n_local, D] bf16, or uint8 e4m3 bytes with per-row f32 `scales` (value = scale * fp8).
         norm_bound: upper bound of the (dequantised) row norms for the exactness certificate; None = L2-normalised
         descriptors (what SALAD emits); `measure_norm_bound()` computes it from the rows.
@@ -129,7 +130,11 @@ class ShardedGallery:
         single GPU: bench.py --force-dist).
         exact_fallback: every local search reads its certificate back (one host sync per search) and re-runs the
         queries it could not certify on exact f64 scores — unconditionally exact answers, for offline evaluation; the
-        serving path leaves it off and watches `uncertified_queries()` instead (not capturable in a HIP graph)."""
+        serving path leaves it off and watches `uncertified_queries()` instead (not capturable in a HIP graph).
+        projection (projection.DescriptorProjection whose width d is the rows'): the rows are projected descriptors.  search,
+        search_expanded and search_local_queries then take queries of the projection's input width and project them first
+        (include/vpr_amd_project.h; in search_local_queries before the all-gather, so d-wide rows travel); queries of width d
+        are taken as already projected; `expand` works in the projected space."""
         lo, hi = shard_bounds(n_total, rank, world)
         if local_rows.shape[0] != hi - lo:
             raise ValueError(f"rank {rank}: shard has {local_rows.shape[0]} rows, expected {hi - lo}")
@@ -137,6 +142,9 @@ class ShardedGallery:
             raise ValueError("fp8 shards (uint8 rows) come with per-row scales, bf16 shards without")
         if scales is not None and scales.numel() != hi - lo:
             raise ValueError("scales: one per local row")
+        if projection is not None and projection.d != local_rows.shape[1]:
+            raise ValueError(f"projection maps to {projection.d} columns, the rows have {local_rows.shape[1]}")
+        self.projection = projection
         self.scales = scales
         self.rows, self.n_total, self.rank, self.world = local_rows, n_total, rank, world
         self.index_base = lo
@@ -158,6 +166,21 @@ class ShardedGallery:
         self.norm_bound = best * 1.001
         return self.norm_bound
 
+    @property
+    def query_width(self) -> int:
+        """Width of the queries a caller hands in: the projection's input width, or the rows' own."""
+        return self.rows.shape[1] if self.projection is None else self.projection.d_in
+
+    def project_queries(self, q: torch.Tensor) -> torch.Tensor:
+        """Queries as the rows are: [B, D_in] bf16 through the gallery's projection, [B, d] as they are; without a projection
+        every query passes unchanged (the search kernels check its width)."""
+        if self.projection is None or q.shape[1] == self.rows.shape[1]:
+            return q
+        if q.shape[1] != self.projection.d_in:
+            raise ValueError(f"queries are {q.shape[1]} wide; this gallery takes {self.projection.d_in} (projected here) or "
+                             f"{self.rows.shape[1]} (already projected)")
+        return self.projection.apply(q)
+
     def gather_queries(self, q_local: torch.Tensor) -> torch.Tensor:
         if not self.collective:
             return q_local
@@ -176,7 +199,7 @@ class ShardedGallery:
     def search(self, q_all: torch.Tensor, k: int, ws=None, score_events=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """q_all [B, D]: the same on every rank.  Returns merged (vals [B,k], idx [B,k]) on every rank.
         score_events (HipEngine only): list collecting (start, end) timing events around the local score stage."""
-        v, i = self._local(q_all, k, ws, score_events)
+        v, i = self._local(self.project_queries(q_all), k, ws, score_events)
         if not self.collective:
             return v, i
         vs, is_ = all_gather_topk(v, i, self.world, self.group)
@@ -204,6 +227,7 @@ class ShardedGallery:
         """search -> expand -> search, `rounds` times: the (vals, idx) of the last search.  The expanded bf16 queries go through
         `search` like any others (an fp8 shard quantises them there).  ws / ws2: kNN workspaces of the first and of the later
         searches (ws2 None: ws again)."""
+        q_all = self.project_queries(q_all)
         v, i = self.search(q_all, k, ws)
         for _ in range(rounds):
             q_all = self.expand(q_all, v, i, n_use, alpha, q_weight)
@@ -213,7 +237,7 @@ class ShardedGallery:
     def search_local_queries(self, q_local: torch.Tensor, k: int, expand=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Data-parallel form: each rank contributes B_local queries and gets back its own rows.
         expand: None, or the query expansion to search with (expansion_params)."""
-        q_all = self.gather_queries(q_local)
+        q_all = self.gather_queries(self.project_queries(q_local))
         v, i = self.search(q_all, k) if expand is None else self.search_expanded(q_all, k, **expansion_params(expand))
         b = q_local.shape[0]
         return v[self.rank * b:(self.rank + 1) * b], i[self.rank * b:(self.rank + 1) * b]
@@ -243,7 +267,9 @@ class GraphedRetrieval:
     rank's merged rows; `self.pose64` ([B_local, 3] f64: lat, lon, angle_deg) and `self.pose4` ([B_local, 4] f32, the fused
     head's format under `scaler`) are rewritten by every replay like vals / idx.  Without labels both stay None.
     expand ((n_use, alpha) or a dict, expansion_params): the graph holds the two-pass form, ShardedGallery.search_expanded —
-    vals / idx and the poses are those of the last search, which runs in a kNN workspace of its own."""
+    vals / idx and the poses are those of the last search, which runs in a kNN workspace of its own.
+    A gallery with a projection: `self.q` has the projection's input width and the projection is captured inside the graph,
+    ahead of the gather."""
 
     def __init__(self, gallery: ShardedGallery, batch_local: int, k: int, labels=None, mode: str = "top1",
                  temperature: float = 0.01, scaler=None, expand=None):
@@ -259,7 +285,7 @@ class GraphedRetrieval:
                                f"this process group is '{dist.get_backend(gallery.group)}' — use the eager search")
         rows = gallery.rows
         dev, D = rows.device, rows.shape[1]
-        self.q = torch.zeros((batch_local, D), dtype=torch.bfloat16, device=dev)
+        self.q = torch.zeros((batch_local, gallery.query_width), dtype=torch.bfloat16, device=dev)
         B = batch_local * (gallery.world if gallery.collective else 1)
         self.ws = ops.knn_workspace(B, rows.shape[0], D, k, dev)
         self.ws2 = None if self.expand is None else ops.workspace("knn_expanded", self.ws.numel(), dev)
@@ -293,7 +319,7 @@ class GraphedRetrieval:
 
     def _run(self):
         g = self.g
-        q_all = g.gather_queries(self.q)
+        q_all = g.gather_queries(g.project_queries(self.q))
         if self.expand is None:
             v, i = g.search(q_all, self.k, self.ws)
         else:

@@ -9,6 +9,7 @@ that seam, so the HIP hot path is visible to PyTorch's dispatcher like any other
     torch.ops.vpr.knn_topk / knn_topk_fp8 / topk_merge
     torch.ops.vpr.retrieval_pose                       (geopose and first-hit ranks from the merged top-k)
     torch.ops.vpr.query_expand / query_expand_finish   (alpha-QE / DBA: weighted mean of a query and its best rows)
+    torch.ops.vpr.project_rows                         (PCA / whitening projection of descriptors + L2 re-normalisation)
     torch.ops.vpr.pose_head / ln_meanpool_head
     torch.ops.vpr.head_train_epoch                     (head-only fine-tuning pass; mutates parameters and AdamW moments)
     torch.ops.vpr.head_train_epoch_dropout             (the same pass with Dropout(p) after the ReLU, training mode)
@@ -213,6 +214,19 @@ def _(partials, q):
     return q.new_empty(q.shape, dtype=torch.float32), q.new_empty(q.shape, dtype=torch.bfloat16)
 
 
+@torch.library.custom_op("vpr::project_rows", mutates_args=())
+def project_rows(x: Tensor, P: Tensor, c: Tensor, normalize: bool = True) -> Tuple[Tensor, Tensor]:
+    """Descriptor projection: x bf16 [rows, D], P bf16 [d, D], c f32 [d] -> (f32 [rows, d], its bf16 rounding) =
+    x P^T + c, L2-normalised per row when `normalize` (a row of norm 0 or not finite becomes +0).  vpr_project_rows."""
+    return ops.project_rows(x, P, c, normalize, want_f32=True, want_bf16=True)
+
+
+@project_rows.register_fake
+def _(x, P, c, normalize=True):
+    shape = (x.shape[0], P.shape[0])
+    return x.new_empty(shape, dtype=torch.float32), x.new_empty(shape, dtype=torch.bfloat16)
+
+
 # ------------------------------------------------------------------------------------------------------------ heads
 @torch.library.custom_op("vpr::pose_head", mutates_args=())
 def pose_head(x: Tensor, W1: Optional[Tensor], b1: Optional[Tensor], W2: Tensor, b2: Tensor, sincos_offset: int) -> Tensor:
@@ -284,4 +298,4 @@ def _(X, Y, order, batch_size, W1, b1, W2, b2, m, v, first_step, lr, beta1, beta
 
 
 OPS = ("head_train_epoch", "head_train_epoch_dropout", "salad_aggregate", "salad_aggregate_split", "salad_aggregate_f32", "salad_aggregate_train", "knn_topk", "knn_topk_fp8", "quantize_fp8_rows",
-       "topk_merge", "pose_head", "ln_meanpool_head", "retrieval_pose", "query_expand", "query_expand_finish")
+       "topk_merge", "pose_head", "ln_meanpool_head", "retrieval_pose", "query_expand", "query_expand_finish", "project_rows")
