@@ -164,6 +164,18 @@ PROJECT_PROTOTYPES = {
     # x x_stride rows D | P c d normalize | out_f32 out_bf16 | workspace workspace_bytes | stream
     "vpr_project_rows": (c_int, [_P, c_longlong, c_int, c_int, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
 }
+# include/vpr_amd_rerank.h, the fourth table
+RERANK_MAX_KC, RERANK_MAX_D = 128, 16384      # VPR_RERANK_MAX_KC, VPR_RERANK_MAX_D
+RERANK_PROTOTYPES = {
+    "vpr_rerank_workspace_bytes": (c_size_t, [c_int] * 2),                  # B kc
+    # q q_is_f32 | idx B D kc | rows rows_are_f32 n_local index_base | k_out vals_out idx_out | workspace workspace_bytes | stream
+    "vpr_rerank_rows": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+}
+
+
+def rerank_roundings(D: int, rows_are_f32: bool) -> int:
+    """VPR_RERANK_ROUNDINGS: L of the fine score, the roundings on the longest path from a product to the result."""
+    return (D + 255) // 256 + 2 + 6 if rows_are_f32 else (D + 511) // 512 + 3 + 6
 
 
 def library_path() -> str:
@@ -183,7 +195,8 @@ def lib() -> ctypes.CDLL:
                 "or `make -C visual-place-recognition-and-geopose-estimation_amd/csrc`.")
         handle = ctypes.CDLL(path)
         for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(EXTENSION_PROTOTYPES.items())
-                                          + list(EXPAND_PROTOTYPES.items()) + list(PROJECT_PROTOTYPES.items())):
+                                          + list(EXPAND_PROTOTYPES.items()) + list(PROJECT_PROTOTYPES.items())
+                                          + list(RERANK_PROTOTYPES.items())):
             fn = getattr(handle, name)   # AttributeError if a declared symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

@@ -224,34 +224,8 @@ __global__ __launch_bounds__(256, WGPC) void knn_scores_kernel(
 // 2. Block-wide top-kp selection, shared by every select level, the fused final kernel and the shard merge.
 // Key order: value desc, index asc (packed into one u64 so a max-reduction does both).
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t f32_orderable(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float f32_from_orderable(uint32_t o) {
-  const uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-  return __uint_as_float(u);
-}
-__device__ __forceinline__ unsigned long long make_key(float v, int idx) {   // idx >= 0; unique per idx
-  return ((unsigned long long)f32_orderable(v) << 32) | (uint32_t)(0x7fffffff - idx);
-}
-__device__ __forceinline__ int key_idx(unsigned long long k) { return 0x7fffffff - (int)(uint32_t)k; }
-__device__ __forceinline__ float key_val(unsigned long long k) { return f32_from_orderable((uint32_t)(k >> 32)); }
-
-constexpr unsigned long long KEY_DEAD = 0ull;   // padding: below every real key (orderable(-inf) > 0), so it sorts last
+// (the packed key itself — f32_orderable .. store_entry, KEY_DEAD — lives in vpr_common.h: rerank.hip orders by it too)
 constexpr int SEL_CAP = 4096;                   // candidate list capacity of the register-held selects (= keys per block)
-
-// The key of an input entry: positions outside the input and padding entries (index < 0) become KEY_DEAD by a select,
-// so callers load from a clamped position and stay branch-free (their keys stay in registers).
-__device__ __forceinline__ unsigned long long candidate_key(float val, int id, bool in_range) {
-  return (in_range && id >= 0) ? make_key(val, id) : KEY_DEAD;
-}
-// One output entry: KEY_DEAD -> (-inf, -1); a real key -> (value, index + index_base).
-__device__ __forceinline__ void store_entry(unsigned long long k, float* __restrict__ out_val,
-                                            int32_t* __restrict__ out_idx, long long o, int index_base = 0) {
-  out_val[o] = k == KEY_DEAD ? -INFINITY : key_val(k);
-  out_idx[o] = k == KEY_DEAD ? -1 : key_idx(k) + index_base;
-}
 
 template <int CTRL>
 __device__ __forceinline__ unsigned long long dpp_u64(unsigned long long v) {

@@ -306,13 +306,15 @@ def calculate_angle_validation_scores(model, val_csv_path: str, image_dir: str, 
 @torch.no_grad()
 def build_gallery_from_images(extractor: DinoV2Salad, csv_path: str, image_dir: str, out_dir: str, *, fp8: bool = False,
                               batch_size: int = 64, device: str = "cuda", image_size: int = 224, graph: bool = True,
-                              projection=None, whiten: bool = True) -> int:
+                              projection=None, whiten: bool = True, keep_fine: bool = False) -> int:
     """labels CSV (`filename,timestamp,latitude,longitude,angle,Region_ID`, cleaned_dataset_files/labels_train.csv:1) +
     images -> on-disk gallery (gallery.save_gallery: bf16 rows, or e4m3 rows + per-row scales with fp8=True).
     Preprocessing = the DINOv2+SALAD validation transform (dinov2salad_validation.py:18-22).  Returns the row count.
     projection: None, a projection.DescriptorProjection, or an int d = fit PCA (whiten: with whitening) on this gallery's own
     descriptors (projection.fit_projection) — the rows are projected to d columns on the device (gallery.project_gallery)
-    and the projection is saved with the gallery, where calculate_retrieval_scores finds it."""
+    and the projection is saved with the gallery, where calculate_retrieval_scores finds it.
+    keep_fine: an e4m3 or projected gallery also keeps the bf16 full descriptors (fine_descriptors.npy), the second tier of
+    calculate_retrieval_scores(rerank=); a plain bf16 gallery's rows are those descriptors already, and nothing is added."""
     from . import gallery as G, ops
     dev = torch.device(device)
     extractor = extractor.to(dev).to(torch.bfloat16).eval()
@@ -324,16 +326,17 @@ def build_gallery_from_images(extractor: DinoV2Salad, csv_path: str, image_dir: 
     for idxs, u8 in _batches(image_dir, names, batch_size, dev):
         desc[torch.tensor(idxs, device=dev)] = fwd(prep(u8))
     labels = df[list(G.LABEL_COLUMNS)].to_numpy(dtype=np.float64)
+    fine = desc.to(torch.bfloat16) if keep_fine and (fp8 or projection is not None) else None
     if projection is not None:
         from .projection import fit_projection
         d16 = desc.to(torch.bfloat16)
         if isinstance(projection, int):
             projection = fit_projection(d16, projection, whiten=whiten)
         rows, scales = G.project_gallery(d16, projection, fp8=fp8)
-        G.save_gallery(out_dir, rows, labels, scales=scales, filenames=names, projection=projection)
+        G.save_gallery(out_dir, rows, labels, scales=scales, filenames=names, projection=projection, fine=fine)
     elif fp8:
         rows, scales = ops.quantize_fp8_rows(desc)
-        G.save_gallery(out_dir, rows, labels, scales=scales, filenames=names)
+        G.save_gallery(out_dir, rows, labels, scales=scales, filenames=names, fine=fine)
     else:
         G.save_gallery(out_dir, desc.to(torch.bfloat16), labels, filenames=names)
     return len(names)
@@ -377,7 +380,7 @@ def retrieval_metrics(vals: torch.Tensor, idx: torch.Tensor, labels: np.ndarray,
 def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv_path: str, image_dir: str, *, k: int = 10,
                                tau: float = 25.0, mode: str = "top1", batch_size: int = 64, device: str = "cuda", graph: bool = True,
                                image_size: int = 224, rank: int = 0, world: int = 1, group=None, verbose: bool = True,
-                               on_device: bool = False, query_expansion=None) -> dict:
+                               on_device: bool = False, query_expansion=None, rerank: Optional[int] = None) -> dict:
     """Validation split through descriptor -> sharded cosine top-k -> label transfer:
       pose      (lat, lon, angle) of the best match, or the softmax-weighted mean of the k matches (gallery.label_transfer);
       final_loss on lat/lon with the validation scripts' formula (dinov2salad_validation.py:101), MAAE on the angle
@@ -390,15 +393,24 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
     path's [Q, N] arrays do not fit.
     query_expansion: None, or (n_use, alpha) / a dict with n_use and any of alpha, q_weight, rounds: every batch is searched,
     expanded on the device (ShardedGallery.search_expanded) and searched again; the metrics are those of the last search.
-    A gallery saved with a projection (projection.npz) has every query batch projected on the device before its search."""
+    A gallery saved with a projection (projection.npz) has every query batch projected on the device before its search.
+    rerank (kc): two-tier retrieval — every (last) search yields kc coarse candidates, re-ranked to k on the gallery's fine
+    descriptors (fine_descriptors.npy, build_gallery_from_images(keep_fine=True); a plain bf16 gallery is its own fine tier)
+    with the batch's bf16 descriptors as fine queries (ShardedGallery.search_reranked); topk_scores are then fine scores."""
     from . import gallery as G
     from .retrieval import ShardedGallery
     dev = torch.device(device)
     extractor = extractor.to(dev).to(torch.bfloat16).eval()
-    shard = G.load_gallery_shard(gallery_dir, dev, rank, world)
+    has_fine = os.path.exists(os.path.join(gallery_dir, G.FINE_FILE))
+    shard = G.load_gallery_shard(gallery_dir, dev, rank, world, load_fine=rerank is not None and has_fine)
+    fine = shard.fine
+    if rerank is not None and fine is None:
+        if shard.dtype != "bf16" or shard.projection is not None:
+            raise ValueError(f"rerank: {gallery_dir} has no {G.FINE_FILE} (build_gallery_from_images(keep_fine=True))")
+        fine = shard.rows
     # offline evaluation: unconditionally exact neighbours (queries the device certificate flags are re-run on f64 scores)
     sg = ShardedGallery(shard.rows, shard.n_total, rank, world, group=group, scales=shard.scales, exact_fallback=True,
-                        projection=shard.projection)
+                        projection=shard.projection, fine_rows=fine)
     df = _existing_rows(val_csv_path, image_dir)
     names = df["filename"].tolist()
     prep = ResizeNormalize(image_size, "bilinear", HALF_MEAN, HALF_STD, torch.bfloat16)
@@ -409,7 +421,8 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
     fwd = GraphedForward(features, module=extractor) if graph and dev.type == "cuda" else features
     for idxs, u8 in _batches(image_dir, names, batch_size, dev):
         _, d16 = fwd(prep(u8))
-        v, i = sg.search_local_queries(d16, kk, query_expansion)
+        v, i = (sg.search_local_queries(d16, kk, query_expansion) if rerank is None
+                else sg.search_local_queries(d16, kk, query_expansion, rerank=int(rerank)))
         sel = torch.tensor(idxs, device=dev)
         vals[sel], idx[sel] = v, i
     res = {"filenames": names}

@@ -739,7 +739,54 @@ def query_expand_finish(partials: torch.Tensor, q: torch.Tensor) -> Tuple[torch.
     return out_f32, out_bf16
 
 
-PROJECT_CHUNK_ROWS = 65536       # rows per vpr_project_rows call: bounds the workspace for million-row inputs
+def _rerank_check(what: str, q, idx, rows, k) -> int:
+    for t, name in ((q, "q"), (rows, "rows")):                  # bf16, or f32 taken as it is
+        _need(t, torch.float32 if isinstance(t, torch.Tensor) and t.dtype == torch.float32 else torch.bfloat16, name, 2)
+    _need(idx, torch.int32, "idx", 2)
+    if idx.shape[0] != q.shape[0]:
+        raise RuntimeError(f"{what}: q and idx disagree on B")
+    if rows.shape[1] != q.shape[1]:
+        raise RuntimeError(f"{what}: q and rows disagree on D")
+    if idx.device != q.device or rows.device != q.device:
+        raise RuntimeError(f"{what}: q, idx and rows must live on one device")
+    kc = idx.shape[1]
+    if not 1 <= kc <= _lib.RERANK_MAX_KC:
+        raise RuntimeError(f"{what}: idx must hold 1..{_lib.RERANK_MAX_KC} candidates per query, got {kc}")
+    k = kc if k is None else int(k)
+    if not 1 <= k <= kc:
+        raise RuntimeError(f"{what}: k must be in 1..kc (kc = {kc})")
+    return k
+
+
+def rerank_rows(q: torch.Tensor, idx: torch.Tensor, rows: torch.Tensor, index_base: int = 0, k: Optional[int] = None,
+                ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Two-tier retrieval (include/vpr_amd_rerank.h): q [B, D] bf16 or f32, idx int32 [B, kc] (kc <= 128) the candidates of a
+    coarse search as global rows, rows = this shard's FINE rows [n_local, D] bf16 or f32, owning global rows index_base ...
+    Returns (vals f32 [B, k], idx int32 [B, k]): the k best (None: all kc) of the candidates this shard owns by the f32 dot
+    product with their fine row, (score desc, index asc); everything else — the -1 padding, rows of other shards — is never
+    dereferenced and comes back as (-inf, -1) at the tail.  The output is a list vpr_topk_merge / retrieval_pose take.
+    ws: a byte buffer of vpr_rerank_workspace_bytes(B, kc); None: the current stream's cached one (pinned while a graph is
+    captured, like every workspace)."""
+    k = _rerank_check("rerank_rows", q, idx, rows, k)
+    B, D = q.shape
+    kc = idx.shape[1]
+    dev = q.device
+    need = _lib.lib().vpr_rerank_workspace_bytes(B, kc)
+    if ws is None:
+        ws = workspace("rerank_rows", need, dev)
+    else:
+        _need(ws, torch.uint8, "ws", 1)
+    vals = torch.empty((B, k), dtype=torch.float32, device=dev)
+    out = torch.empty((B, k), dtype=torch.int32, device=dev)
+    if B == 0:
+        return vals, out
+    _call("vpr_rerank_rows", _ptr(q), int(q.dtype == torch.float32), _ptr(idx), B, D, kc, _ptr(rows),
+          int(rows.dtype == torch.float32), rows.shape[0], int(index_base), k, _ptr(vals), _ptr(out), _ptr(ws), ws.numel(),
+          _stream())
+    return vals, out
+
+
+PROJECT_CHUNK_ROWS = 65536      # rows per vpr_project_rows call: bounds the workspace for million-row inputs
 
 
 def project_rows(x: torch.Tensor, P: torch.Tensor, c: torch.Tensor, normalize: bool = True, want_f32: bool = False,

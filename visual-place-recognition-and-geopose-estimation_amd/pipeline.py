@@ -28,7 +28,7 @@ class StepOutput:
 class VPRGeoPosePipeline:
     def __init__(self, extractor: DinoV2Salad, head: FusedGeoPoseHead, gallery: ShardedGallery, k: int = 10,
                  overlap_head: Optional[bool] = None, graph_retrieval: bool = False, labels=None,
-                 retrieval_mode: str = "top1", temperature: float = 0.01, scaler=None):
+                 retrieval_mode: str = "top1", temperature: float = 0.01, scaler=None, rerank: Optional[int] = None):
         """graph_retrieval: the retrieval leg of every step — {query all-gather, local shard search, packed top-k
         all-gather, merge} — is ONE HIP-graph replay (retrieval.GraphedRetrieval, captured at the first step of a given
         batch size; every rank must step in lockstep, as with the eager collectives).  BASELINE config 5's "hipGraph-
@@ -37,7 +37,11 @@ class VPRGeoPosePipeline:
         every step also transfers the neighbours' labels to a pose on the device (torch.ops.vpr.retrieval_pose, inside the
         graph when graph_retrieval) — StepOutput.retrieval_pose, in the head's 4-wide format under `scaler` (four numbers
         or a postproc.LatLonScaler; None = no standardisation).  retrieval_mode "top1" | "weighted" with `temperature`, as
-        gallery.label_transfer.  Without labels the step is unchanged and the field stays None."""
+        gallery.label_transfer.  Without labels the step is unchanged and the field stays None.
+        rerank (kc): two-tier retrieval — the gallery's coarse search for kc candidates, re-ranked to k on its fine_rows
+        (ShardedGallery.search_reranked).  The fine query is the step's bf16 descriptor on the eager and on the graph path
+        alike, so the two stay bit-identical; topk_scores are then fine scores."""
+        self.rerank = None if rerank is None else int(rerank)
         self.labels = None if labels is None else pose_labels(labels, gallery.rows.device)
         self.retrieval_mode, self.temperature, self.scaler = retrieval_mode, temperature, pose_scaler(scaler)
         self.extractor, self.head, self.gallery, self.k = extractor, head, gallery, k
@@ -74,7 +78,7 @@ class VPRGeoPosePipeline:
             gr = self._graphed.get(key)
             if gr is None:
                 gr = self._graphed[key] = GraphedRetrieval(g, desc16.shape[0], self.k, self.labels, self.retrieval_mode,
-                                                           self.temperature, self.scaler)
+                                                           self.temperature, self.scaler, rerank=self.rerank)
             if self.knn_events is not None:                # a graph has no seam for events: the whole replay is timed
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
@@ -86,9 +90,14 @@ class VPRGeoPosePipeline:
             if self.labels is not None:
                 rpose = gr.pose4.clone()
         else:
-            q_all = g.gather_queries(g.project_queries(desc16))      # a projected gallery: d-wide rows travel
+            q_proj = g.project_queries(desc16)
+            q_all = g.gather_queries(q_proj)                         # a projected gallery: d-wide rows travel
             # knn_events: same kernels, run as the two stages of the call with HIP events around the score stage
-            v, i = g.search(q_all, self.k, score_events=self.knn_events)
+            if self.rerank is None:
+                v, i = g.search(q_all, self.k, score_events=self.knn_events)
+            else:
+                v, i = g.search_reranked(q_all, self.k, self.rerank, g.gather_fine_queries(desc16, q_proj, q_all),
+                                         score_events=self.knn_events)
             if g.collective:
                 b = desc.shape[0]
                 v, i = v[g.rank * b:(g.rank + 1) * b], i[g.rank * b:(g.rank + 1) * b]

@@ -69,6 +69,12 @@ class HipEngine:
         """A gallery of one shard: partial and finish in one call; the partial lives in the stream's cached workspace."""
         return ops.query_expand(q, vals, idx, rows, scales, index_base, n_use, alpha, q_weight, True, finish=True)[1]
 
+    def rerank(self, q, idx, rows, index_base, k, ws=None):
+        """The k best of the candidates idx [B, kc] this shard owns, by fine score (vpr_rerank_rows): (vals, idx) [B, k]."""
+        if ws is None:
+            return torch.ops.vpr.rerank_rows(q, idx, rows, index_base, k)
+        return ops.rerank_rows(q, idx, rows, index_base, k, ws)
+
 
 def pose_labels(labels, device) -> torch.Tensor:
     """The label table for torch.ops.vpr.retrieval_pose: a [N, 4] float64 tensor on `device` (gallery.device_labels /
@@ -122,7 +128,7 @@ class ShardedGallery:
     def __init__(self, local_rows: torch.Tensor, n_total: int, rank: int = 0, world: int = 1,
                  engine=None, group: Optional[dist.ProcessGroup] = None, scales: Optional[torch.Tensor] = None,
                  norm_bound: Optional[float] = None, force_collectives: bool = False, exact_fallback: bool = False,
-                 projection=None):
+                 projection=None, fine_rows: Optional[torch.Tensor] = None):
         """local_rows: [n_local, D] bf16, or uint8 e4m3 bytes with per-row f32 `scales` (value = scale * fp8).
         norm_bound: upper bound of the (dequantised) row norms for the exactness certificate; None = L2-normalised
         descriptors (what SALAD emits); `measure_norm_bound()` computes it from the rows.
@@ -134,7 +140,9 @@ class ShardedGallery:
         projection (projection.DescriptorProjection whose width d is the rows'): the rows are projected descriptors.  search,
         search_expanded and search_local_queries then take queries of the projection's input width and project them first
         (include/vpr_amd_project.h; in search_local_queries before the all-gather, so d-wide rows travel); queries of width d
-        are taken as already projected; `expand` works in the projected space."""
+        are taken as already projected; `expand` works in the projected space.
+        fine_rows ([n_local, D_fine] bf16 or f32, this shard's rows of the full-precision descriptors the local rows were made
+        from): the second tier of search_reranked (include/vpr_amd_rerank.h); nothing else reads them."""
         lo, hi = shard_bounds(n_total, rank, world)
         if local_rows.shape[0] != hi - lo:
             raise ValueError(f"rank {rank}: shard has {local_rows.shape[0]} rows, expected {hi - lo}")
@@ -144,6 +152,12 @@ class ShardedGallery:
             raise ValueError("scales: one per local row")
         if projection is not None and projection.d != local_rows.shape[1]:
             raise ValueError(f"projection maps to {projection.d} columns, the rows have {local_rows.shape[1]}")
+        if fine_rows is not None:
+            if fine_rows.dim() != 2 or fine_rows.shape[0] != hi - lo:
+                raise ValueError(f"rank {rank}: fine_rows must be [{hi - lo}, D_fine], one per local row; got {tuple(fine_rows.shape)}")
+            if fine_rows.dtype not in (torch.bfloat16, torch.float32):
+                raise ValueError(f"fine_rows: bf16 or f32, got {fine_rows.dtype}")
+        self.fine_rows = fine_rows
         self.projection = projection
         self.scales = scales
         self.rows, self.n_total, self.rank, self.world = local_rows, n_total, rank, world
@@ -205,6 +219,35 @@ class ShardedGallery:
         vs, is_ = all_gather_topk(v, i, self.world, self.group)
         return self.engine.merge(vs, is_)
 
+    def search_reranked(self, q_all: torch.Tensor, k: int, kc: int, q_fine: Optional[torch.Tensor] = None,
+                        ws=None, score_events=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Two-tier search (include/vpr_amd_rerank.h): the coarse local search of this shard for kc candidates (k <= kc <= 64,
+        through the projection if there is one), those candidates re-ranked to k by their f32 dot product with the shard's
+        `fine_rows`, then the packed all-gather and merge of `search` — as many collectives as a plain search.
+        q_fine [B, D_fine] bf16 or f32: the queries of the fine tier; None: q_all, which must then be D_fine wide (with a
+        projection the caller's D_in-wide queries are the fine queries).  ws, score_events: of the coarse search, as in `search`.
+        Sharded meaning: the answer is the k best by fine score among the UNION of the shards' coarse top-kc — each shard
+        re-ranks its own kc candidates, so up to world * kc rows are considered, a superset of the global coarse top-kc.  With
+        one shard that is the coarse top-kc itself.  Values are fine scores; a candidate whose fine score is NaN comes last
+        among the live ones, as -inf."""
+        if self.fine_rows is None:
+            raise ValueError("search_reranked: this gallery has no fine_rows")
+        if not 1 <= kc <= 64:
+            raise ValueError(f"search_reranked: one coarse search yields at most 64 candidates; kc = {kc}")
+        if not 1 <= k <= kc:
+            raise ValueError(f"search_reranked: k must be in 1..kc (k = {k}, kc = {kc})")
+        q_fine = q_all if q_fine is None else q_fine
+        if q_fine.shape[1] != self.fine_rows.shape[1]:
+            raise ValueError(f"search_reranked: the fine queries are {q_fine.shape[1]} wide, the fine rows {self.fine_rows.shape[1]}")
+        if q_fine.shape[0] != q_all.shape[0]:
+            raise ValueError("search_reranked: q_all and q_fine disagree on B")
+        _, i = self._local(self.project_queries(q_all), kc, ws, score_events)
+        v, i = self.engine.rerank(q_fine, i.contiguous(), self.fine_rows, self.index_base, k)
+        if not self.collective:
+            return v, i
+        vs, is_ = all_gather_topk(v, i, self.world, self.group)
+        return self.engine.merge(vs, is_)
+
     def expand(self, q_all: torch.Tensor, vals: torch.Tensor, idx: torch.Tensor, n_use: int, alpha: float = 3.0,
                q_weight: float = 1.0) -> torch.Tensor:
         """Query expansion (alpha-QE, include/vpr_amd_expand.h): q_all [B, D] bf16 and its merged top-k (vals, idx) [B, k], the
@@ -223,22 +266,43 @@ class ShardedGallery:
         return self.engine.expand_finish(parts.view(self.world, B, D), q_all)
 
     def search_expanded(self, q_all: torch.Tensor, k: int, n_use: int, alpha: float = 3.0, q_weight: float = 1.0,
-                        rounds: int = 1, ws=None, ws2=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                        rounds: int = 1, ws=None, ws2=None, rerank: Optional[int] = None,
+                        q_fine: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """search -> expand -> search, `rounds` times: the (vals, idx) of the last search.  The expanded bf16 queries go through
         `search` like any others (an fp8 shard quantises them there).  ws / ws2: kNN workspaces of the first and of the later
-        searches (ws2 None: ws again)."""
+        searches (ws2 None: ws again).
+        rerank = kc: the LAST search is search_reranked(expanded queries, k, kc); its fine queries are q_fine, or (None) the
+        caller's q_all as handed in — the original queries, not the expanded ones."""
+        if rerank is not None and q_fine is None:
+            q_fine = q_all
         q_all = self.project_queries(q_all)
         v, i = self.search(q_all, k, ws)
-        for _ in range(rounds):
+        for r in range(rounds):
             q_all = self.expand(q_all, v, i, n_use, alpha, q_weight)
+            if rerank is not None and r == rounds - 1:
+                return self.search_reranked(q_all, k, rerank, q_fine, ws if ws2 is None else ws2)
             v, i = self.search(q_all, k, ws if ws2 is None else ws2)
         return v, i
 
-    def search_local_queries(self, q_local: torch.Tensor, k: int, expand=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def gather_fine_queries(self, q_local: torch.Tensor, q_proj: torch.Tensor, q_all: torch.Tensor) -> torch.Tensor:
+        """The fine tier's queries of the global batch: q_all itself unless a projection made the travelling rows narrower
+        than the caller's (q_proj is not q_local) — then the caller's own rows are gathered as well."""
+        return q_all if q_proj is q_local else self.gather_queries(q_local)
+
+    def search_local_queries(self, q_local: torch.Tensor, k: int, expand=None,
+                             rerank: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Data-parallel form: each rank contributes B_local queries and gets back its own rows.
-        expand: None, or the query expansion to search with (expansion_params)."""
-        q_all = self.gather_queries(self.project_queries(q_local))
-        v, i = self.search(q_all, k) if expand is None else self.search_expanded(q_all, k, **expansion_params(expand))
+        expand: None, or the query expansion to search with (expansion_params).
+        rerank = kc: the two-tier form (search_reranked; with `expand`, of its last search).  The fine queries are q_local's
+        rows: when a projection made the travelling rows d wide, the D_in-wide ones are gathered as well."""
+        q_proj = self.project_queries(q_local)
+        q_all = self.gather_queries(q_proj)
+        if rerank is not None:
+            q_fine = self.gather_fine_queries(q_local, q_proj, q_all)
+            v, i = (self.search_reranked(q_all, k, rerank, q_fine) if expand is None
+                    else self.search_expanded(q_all, k, rerank=rerank, q_fine=q_fine, **expansion_params(expand)))
+        else:
+            v, i = self.search(q_all, k) if expand is None else self.search_expanded(q_all, k, **expansion_params(expand))
         b = q_local.shape[0]
         return v[self.rank * b:(self.rank + 1) * b], i[self.rank * b:(self.rank + 1) * b]
 
@@ -269,11 +333,14 @@ class GraphedRetrieval:
     expand ((n_use, alpha) or a dict, expansion_params): the graph holds the two-pass form, ShardedGallery.search_expanded —
     vals / idx and the poses are those of the last search, which runs in a kNN workspace of its own.
     A gallery with a projection: `self.q` has the projection's input width and the projection is captured inside the graph,
-    ahead of the gather."""
+    ahead of the gather.
+    rerank (kc): the graph holds the two-tier form, ShardedGallery.search_reranked (with `expand`, of its last search): the fine
+    queries are `self.q`, vals are fine scores, and the poses come from the re-ranked rows."""
 
     def __init__(self, gallery: ShardedGallery, batch_local: int, k: int, labels=None, mode: str = "top1",
-                 temperature: float = 0.01, scaler=None, expand=None):
+                 temperature: float = 0.01, scaler=None, expand=None, rerank: Optional[int] = None):
         self.g, self.k, self.b = gallery, k, batch_local
+        self.rerank = None if rerank is None else int(rerank)
         self.expand = expansion_params(expand)
         self.labels = None if labels is None else pose_labels(labels, gallery.rows.device)
         self.mode, self.temperature, self.scaler = mode, temperature, pose_scaler(scaler)
@@ -287,7 +354,7 @@ class GraphedRetrieval:
         dev, D = rows.device, rows.shape[1]
         self.q = torch.zeros((batch_local, gallery.query_width), dtype=torch.bfloat16, device=dev)
         B = batch_local * (gallery.world if gallery.collective else 1)
-        self.ws = ops.knn_workspace(B, rows.shape[0], D, k, dev)
+        self.ws = ops.knn_workspace(B, rows.shape[0], D, k if self.rerank is None else max(k, self.rerank), dev)
         self.ws2 = None if self.expand is None else ops.workspace("knn_expanded", self.ws.numel(), dev)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -319,11 +386,13 @@ class GraphedRetrieval:
 
     def _run(self):
         g = self.g
-        q_all = g.gather_queries(g.project_queries(self.q))
+        q_proj = g.project_queries(self.q)
+        q_all = g.gather_queries(q_proj)
+        q_fine = None if self.rerank is None else g.gather_fine_queries(self.q, q_proj, q_all)
         if self.expand is None:
-            v, i = g.search(q_all, self.k, self.ws)
+            v, i = g.search(q_all, self.k, self.ws) if self.rerank is None else g.search_reranked(q_all, self.k, self.rerank, q_fine, self.ws)
         else:
-            v, i = g.search_expanded(q_all, self.k, ws=self.ws, ws2=self.ws2, **self.expand)
+            v, i = g.search_expanded(q_all, self.k, ws=self.ws, ws2=self.ws2, rerank=self.rerank, q_fine=q_fine, **self.expand)
         lo = g.rank * self.b if g.collective else 0
         v, i = v[lo:lo + self.b], i[lo:lo + self.b]
         if self.labels is not None:

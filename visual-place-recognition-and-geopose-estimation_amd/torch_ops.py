@@ -10,6 +10,7 @@ that seam, so the HIP hot path is visible to PyTorch's dispatcher like any other
     torch.ops.vpr.retrieval_pose                       (geopose and first-hit ranks from the merged top-k)
     torch.ops.vpr.query_expand / query_expand_finish   (alpha-QE / DBA: weighted mean of a query and its best rows)
     torch.ops.vpr.project_rows                         (PCA / whitening projection of descriptors + L2 re-normalisation)
+    torch.ops.vpr.rerank_rows                          (two-tier retrieval: coarse candidates re-ranked on full-precision rows)
     torch.ops.vpr.pose_head / ln_meanpool_head
     torch.ops.vpr.head_train_epoch                     (head-only fine-tuning pass; mutates parameters and AdamW moments)
     torch.ops.vpr.head_train_epoch_dropout             (the same pass with Dropout(p) after the ReLU, training mode)
@@ -227,6 +228,20 @@ def _(x, P, c, normalize=True):
     return x.new_empty(shape, dtype=torch.float32), x.new_empty(shape, dtype=torch.bfloat16)
 
 
+@torch.library.custom_op("vpr::rerank_rows", mutates_args=())
+def rerank_rows(q: Tensor, idx: Tensor, rows: Tensor, index_base: int = 0, k: Optional[int] = None) -> Tuple[Tensor, Tensor]:
+    """Two-tier retrieval: q [B, D] (bf16 | f32), candidates idx int32 [B, kc] (global rows), this shard's fine rows
+    [n_local, D] (bf16 | f32) -> (scores f32 [B, k], indices int32 [B, k]): the k best (None: kc) of the candidates the shard
+    owns by their f32 dot product with the fine row, (score desc, index asc); the rest is (-inf, -1).  vpr_rerank_rows."""
+    return ops.rerank_rows(q, idx, rows, index_base, k)
+
+
+@rerank_rows.register_fake
+def _(q, idx, rows, index_base=0, k=None):
+    B, k = idx.shape[0], idx.shape[1] if k is None else k
+    return q.new_empty((B, k), dtype=torch.float32), q.new_empty((B, k), dtype=torch.int32)
+
+
 # ------------------------------------------------------------------------------------------------------------ heads
 @torch.library.custom_op("vpr::pose_head", mutates_args=())
 def pose_head(x: Tensor, W1: Optional[Tensor], b1: Optional[Tensor], W2: Tensor, b2: Tensor, sincos_offset: int) -> Tensor:
@@ -298,4 +313,5 @@ def _(X, Y, order, batch_size, W1, b1, W2, b2, m, v, first_step, lr, beta1, beta
 
 
 OPS = ("head_train_epoch", "head_train_epoch_dropout", "salad_aggregate", "salad_aggregate_split", "salad_aggregate_f32", "salad_aggregate_train", "knn_topk", "knn_topk_fp8", "quantize_fp8_rows",
-       "topk_merge", "pose_head", "ln_meanpool_head", "retrieval_pose", "query_expand", "query_expand_finish", "project_rows")
+       "topk_merge", "pose_head", "ln_meanpool_head", "retrieval_pose", "query_expand", "query_expand_finish", "project_rows",
+       "rerank_rows")
