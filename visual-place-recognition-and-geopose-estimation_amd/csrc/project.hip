@@ -132,13 +132,8 @@ __global__ __launch_bounds__(PJ_FIN_THREADS) void project_finish_kernel(
   float inv = 1.f;
   bool zero = false;
   if (normalize) {                              // uniform over the grid
-    t = wave_sum(t);
-    if (lane == 0) s_part[wave] = t;
-    __syncthreads();
-    float n2 = 0.f;
-#pragma unroll
-    for (int w = 0; w < PJ_FIN_THREADS / WAVE; ++w) n2 += s_part[w];
-    zero = !(n2 > 0.f) || isinf(n2);            // 0, NaN or Inf: the row becomes +0
+    const float n2 = block_sum_in_wave_order<PJ_FIN_THREADS / WAVE>(wave_sum(t), s_part, lane, wave);
+    zero = norm_unusable(n2);                   // the row becomes +0
     inv = 1.0f / sqrtf(n2);
   }
 #pragma unroll
@@ -148,17 +143,10 @@ __global__ __launch_bounds__(PJ_FIN_THREADS) void project_finish_kernel(
       f32x4 o = normalize ? z[i] * inv : z[i];
       if (zero) o = f32x4{0.f, 0.f, 0.f, 0.f};
       if (out_f32) *reinterpret_cast<f32x4*>(out_f32 + b * d + col) = o;
-      if (out_bf16) {
-        uint2 h;
-        h.x = (uint32_t)f32_to_bf16_bits(o[0]) | ((uint32_t)f32_to_bf16_bits(o[1]) << 16);
-        h.y = (uint32_t)f32_to_bf16_bits(o[2]) | ((uint32_t)f32_to_bf16_bits(o[3]) << 16);
-        *reinterpret_cast<uint2*>(out_bf16 + b * d + col) = h;
-      }
+      if (out_bf16) *reinterpret_cast<uint2*>(out_bf16 + b * d + col) = pack_bf16x4(o);
     }
   }
 }
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // the part of the status that the three shape arguments decide
 static int pj_shape_status(int rows, int D, int d) {

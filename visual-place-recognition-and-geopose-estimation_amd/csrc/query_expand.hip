@@ -23,8 +23,6 @@ constexpr int XQ_NJ = 16;            // row chunks a thread has in flight
 constexpr int XF_THREADS = 1024;
 constexpr int XF_MAX_R = 64;
 
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-
 __device__ __forceinline__ i32x4 load_row_chunk(const char* p) {
 #if VPR_EXPAND_NT
   return __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(p));
@@ -44,8 +42,8 @@ __device__ __forceinline__ void add_chunk(float* acc, i32x4 v, float c) {
       acc[4 * w + 2] = fmaf(c, __builtin_amdgcn_cvt_f32_fp8(v[w], 2), acc[4 * w + 2]);
       acc[4 * w + 3] = fmaf(c, __builtin_amdgcn_cvt_f32_fp8(v[w], 3), acc[4 * w + 3]);
     } else {
-      acc[2 * w + 0] = fmaf(c, __uint_as_float((uint32_t)v[w] << 16), acc[2 * w + 0]);
-      acc[2 * w + 1] = fmaf(c, __uint_as_float((uint32_t)v[w] & 0xffff0000u), acc[2 * w + 1]);
+      acc[2 * w + 0] = fmaf(c, bf16_lo(v[w]), acc[2 * w + 0]);
+      acc[2 * w + 1] = fmaf(c, bf16_hi(v[w]), acc[2 * w + 1]);
     }
   }
 }
@@ -68,8 +66,8 @@ __global__ __launch_bounds__(XQ_THREADS) void query_expand_kernel(
   long long off = 0;
   float coef = 0.f;
   if (tid < n_use) {
-    const long long r = (long long)idx[b * k + tid] - index_base;
-    if (r >= 0 && r < n_local) {
+    long long r;
+    if (shard_row(idx[b * k + tid], n_local, index_base, r)) {
       const float v = vals[b * k + tid];
       if (v > 0.f) {
         coef = alpha == 0.0 ? 1.f : (float)pow((double)v, alpha);
@@ -145,36 +143,23 @@ __global__ __launch_bounds__(XF_THREADS) void query_expand_finish_kernel(
     const f32x4 s = shard_sum(p + d, shard_stride, R);
     t = fmaf(s[0], s[0], t); t = fmaf(s[1], s[1], t); t = fmaf(s[2], s[2], t); t = fmaf(s[3], s[3], t);
   }
-  t = wave_sum(t);
-  if (lane == 0) s_part[wave] = t;
-  __syncthreads();
-  float n2 = 0.f;
-#pragma unroll
-  for (int w = 0; w < XF_THREADS / WAVE; ++w) n2 += s_part[w];
+  const float n2 = block_sum_in_wave_order<XF_THREADS / WAVE>(wave_sum(t), s_part, lane, wave);
 
-  const bool keep_q = !(n2 > 0.f) || isinf(n2);         // 0, NaN or Inf: the query stays what it was
+  const bool keep_q = norm_unusable(n2);                // the query stays what it was
   const float inv = 1.0f / sqrtf(n2);
   for (int d = tid * 4; d < D; d += XF_THREADS * 4) {
     f32x4 o;
     if (keep_q) {
       const uint2 qv = *reinterpret_cast<const uint2*>(q + b * D + d);
-      o = f32x4{__uint_as_float(qv.x << 16), __uint_as_float(qv.x & 0xffff0000u),
-                __uint_as_float(qv.y << 16), __uint_as_float(qv.y & 0xffff0000u)};
+      o = f32x4{bf16_lo(qv.x), bf16_hi(qv.x), bf16_lo(qv.y), bf16_hi(qv.y)};
       if (out_bf16) *reinterpret_cast<uint2*>(out_bf16 + b * D + d) = qv;
     } else {
       o = shard_sum(p + d, shard_stride, R) * inv;
-      if (out_bf16) {
-        uint2 h;
-        h.x = (uint32_t)f32_to_bf16_bits(o[0]) | ((uint32_t)f32_to_bf16_bits(o[1]) << 16);
-        h.y = (uint32_t)f32_to_bf16_bits(o[2]) | ((uint32_t)f32_to_bf16_bits(o[3]) << 16);
-        *reinterpret_cast<uint2*>(out_bf16 + b * D + d) = h;
-      }
+      if (out_bf16) *reinterpret_cast<uint2*>(out_bf16 + b * D + d) = pack_bf16x4(o);
     }
     if (out_f32) *reinterpret_cast<f32x4*>(out_f32 + b * D + d) = o;
   }
 }
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 static int finish_status(const float* partials, int R, const uint16_t* q, int B, int D, float* out_f32, uint16_t* out_bf16) {
   if (!partials || !q || (!out_f32 && !out_bf16) || B < 0 || D < 0 || R < 1) return VPR_ERR_INVALID_ARG;

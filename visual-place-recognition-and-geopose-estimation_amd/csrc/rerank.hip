@@ -20,13 +20,6 @@ constexpr int RR_MAX_KC = VPR_RERANK_MAX_KC;      // = the order kernel's workgr
 constexpr int RR_MAX_D = VPR_RERANK_MAX_D;        // 4 * D bytes of LDS <= 64 KB
 constexpr unsigned long long RR_KEY_NAN_HI = 1ull << 32;   // above KEY_DEAD, below orderable(-inf) = 0x007fffff
 
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-
-__device__ __forceinline__ bool rerank_live(int id, int n_local, int index_base, long long* r) {
-  *r = (long long)id - index_base;
-  return *r >= 0 && *r < n_local;
-}
-
 // a[e] = fmaf(q[e], row[e], a[e]) over the E elements of one 16-byte row chunk; q is the chunk's E staged f32 values
 template <bool ROWS_F32>
 __device__ __forceinline__ void dot_chunk(float* a, i32x4 v, const float* __restrict__ qs) {
@@ -39,8 +32,8 @@ __device__ __forceinline__ void dot_chunk(float* a, i32x4 v, const float* __rest
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
       const float qe = w < 2 ? q0[2 * w] : q1[2 * w - 4], qo = w < 2 ? q0[2 * w + 1] : q1[2 * w - 3];
-      a[2 * w + 0] = fmaf(qe, __uint_as_float((uint32_t)v[w] << 16), a[2 * w + 0]);
-      a[2 * w + 1] = fmaf(qo, __uint_as_float((uint32_t)v[w] & 0xffff0000u), a[2 * w + 1]);
+      a[2 * w + 0] = fmaf(qe, bf16_lo(v[w]), a[2 * w + 0]);
+      a[2 * w + 1] = fmaf(qo, bf16_hi(v[w]), a[2 * w + 1]);
     }
   }
 }
@@ -56,7 +49,7 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_score_kernel(
   const int j = blockIdx.y * RR_WAVES + wave;
 
   long long r = 0;
-  const bool live = j < kc && rerank_live(idx[b * kc + (j < kc ? j : 0)], n_local, index_base, &r);   // wave-uniform
+  const bool live = j < kc && shard_row(idx[b * kc + (j < kc ? j : 0)], n_local, index_base, r);   // wave-uniform
   if (!__syncthreads_or(live)) return;                                // nothing of this group is local: no staging
 
   if constexpr (Q_F32) {
@@ -69,9 +62,7 @@ __global__ __launch_bounds__(RR_THREADS) void rerank_score_kernel(
       const i32x4 v = *reinterpret_cast<const i32x4*>(qrow + d);
 #pragma unroll
       for (int w = 0; w < 4; w += 2)
-        *reinterpret_cast<f32x4*>(s_q + d + 2 * w) =
-            f32x4{__uint_as_float((uint32_t)v[w] << 16), __uint_as_float((uint32_t)v[w] & 0xffff0000u),
-                  __uint_as_float((uint32_t)v[w + 1] << 16), __uint_as_float((uint32_t)v[w + 1] & 0xffff0000u)};
+        *reinterpret_cast<f32x4*>(s_q + d + 2 * w) = f32x4{bf16_lo(v[w]), bf16_hi(v[w]), bf16_lo(v[w + 1]), bf16_hi(v[w + 1])};
     }
   }
   __syncthreads();
@@ -115,7 +106,7 @@ __global__ __launch_bounds__(RR_MAX_KC) void rerank_order_kernel(
   if (j < kc) {
     const int cand = idx[b * kc + j];
     long long r;
-    if (rerank_live(cand, n_local, index_base, &r)) {                 // only a live candidate's score was written
+    if (shard_row(cand, n_local, index_base, r)) {                    // only a live candidate's score was written
       const float s = scores[b * kc + j];
       id = cand;
       if (isnan(s)) key = RR_KEY_NAN_HI | (uint32_t)(0x7fffffff - cand);
@@ -135,9 +126,6 @@ __global__ __launch_bounds__(RR_MAX_KC) void rerank_order_kernel(
     idx_out[b * k_out + rank] = id;
   }
 }
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
 }  // namespace vpr
 

@@ -234,4 +234,39 @@ __device__ __forceinline__ void mfma_f32_store_rows(const SlabRowMajor& slab, in
   }
 }
 
+// ---- 16-byte row chunks (query_expand.hip, rerank.hip, project.hip) ----------------------------------------------
+typedef __attribute__((ext_vector_type(4))) int i32x4;       // one chunk as loaded: 8 bf16, 16 e4m3 or 4 f32
+
+// The two bf16 of a 32-bit word: element 2w in the low half, 2w + 1 in the high half.
+__device__ __forceinline__ float bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf16_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+// Four f32 -> four bf16 (round-to-nearest-even) in two words, element 0 lowest.
+__device__ __forceinline__ uint2 pack_bf16x4(f32x4 v) {
+  uint2 h;
+  h.x = (uint32_t)f32_to_bf16_bits(v[0]) | ((uint32_t)f32_to_bf16_bits(v[1]) << 16);
+  h.y = (uint32_t)f32_to_bf16_bits(v[2]) | ((uint32_t)f32_to_bf16_bits(v[3]) << 16);
+  return h;
+}
+
+// Global row `id` of a gallery sharded by rows: true iff this shard (rows index_base .. index_base + n_local - 1) owns it,
+// r = its local row.  Padding entries (id < 0) and other shards' rows are not owned.
+__device__ __forceinline__ bool shard_row(int id, int n_local, int index_base, long long& r) {
+  r = (long long)id - index_base;
+  return r >= 0 && r < n_local;
+}
+
+// The sums of a workgroup's NWAVES waves (wave_total = wave_sum(...) of the caller's value) added in ascending wave order
+// through s_part[NWAVES] (LDS): the same on every thread.  One barrier; s_part must not be re-used before the next one.
+template <int NWAVES>
+__device__ __forceinline__ float block_sum_in_wave_order(float wave_total, float* s_part, int lane, int wave) {
+  if (lane == 0) s_part[wave] = wave_total;
+  __syncthreads();
+  float s = 0.f;
+#pragma unroll
+  for (int w = 0; w < NWAVES; ++w) s += s_part[w];
+  return s;
+}
+// A squared norm nothing can be divided by: 0, NaN or Inf.
+__device__ __forceinline__ bool norm_unusable(float n2) { return !(n2 > 0.f) || isinf(n2); }
+
 }  // namespace vpr

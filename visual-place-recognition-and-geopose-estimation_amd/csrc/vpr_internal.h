@@ -106,5 +106,8 @@ int device_cu_count();      // capi.hip: multiProcessorCount of the current devi
 #define VPR_TRY_LAUNCH(expr) do { const int vpr_st_ = (expr); if (vpr_st_ != VPR_OK) return vpr_st_; } while (0)
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// Argument checks of pointers read as 16-byte chunks / as 4-byte elements; a null pointer passes both.
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
 }  // namespace vpr

@@ -419,10 +419,10 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
     idx = torch.empty((len(names), kk), dtype=torch.int32, device=dev)
     features = lambda x: extractor.features(x, want_bf16=True)
     fwd = GraphedForward(features, module=extractor) if graph and dev.type == "cuda" else features
+    two_tier = {} if rerank is None else {"rerank": int(rerank)}     # named only when asked for
     for idxs, u8 in _batches(image_dir, names, batch_size, dev):
         _, d16 = fwd(prep(u8))
-        v, i = (sg.search_local_queries(d16, kk, query_expansion) if rerank is None
-                else sg.search_local_queries(d16, kk, query_expansion, rerank=int(rerank)))
+        v, i = sg.search_local_queries(d16, kk, query_expansion, **two_tier)
         sel = torch.tensor(idxs, device=dev)
         vals[sel], idx[sel] = v, i
     res = {"filenames": names}

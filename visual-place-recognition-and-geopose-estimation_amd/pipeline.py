@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 
 from .modules import DinoV2Salad, FusedGeoPoseHead
-from .retrieval import GraphedRetrieval, ShardedGallery, pose_labels, pose_scaler
+from .retrieval import GraphedRetrieval, ShardedGallery, pose_labels, pose_scaler, transfer_pose
 
 
 @dataclass
@@ -90,20 +90,10 @@ class VPRGeoPosePipeline:
             if self.labels is not None:
                 rpose = gr.pose4.clone()
         else:
-            q_proj = g.project_queries(desc16)
-            q_all = g.gather_queries(q_proj)                         # a projected gallery: d-wide rows travel
             # knn_events: same kernels, run as the two stages of the call with HIP events around the score stage
-            if self.rerank is None:
-                v, i = g.search(q_all, self.k, score_events=self.knn_events)
-            else:
-                v, i = g.search_reranked(q_all, self.k, self.rerank, g.gather_fine_queries(desc16, q_proj, q_all),
-                                         score_events=self.knn_events)
-            if g.collective:
-                b = desc.shape[0]
-                v, i = v[g.rank * b:(g.rank + 1) * b], i[g.rank * b:(g.rank + 1) * b]
+            v, i = g.search_local_queries(desc16, self.k, rerank=self.rerank, score_events=self.knn_events)
             if self.labels is not None:
-                _, rpose, _, _ = torch.ops.vpr.retrieval_pose(v.contiguous(), i.contiguous(), self.labels, self.retrieval_mode,
-                                                              self.temperature, None, 0.0, self.scaler)
+                _, rpose = transfer_pose(v, i, self.labels, self.retrieval_mode, self.temperature, self.scaler)
         if self.overlap_head:
             main.wait_stream(side)
             pose.record_stream(main)

@@ -94,6 +94,13 @@ def pose_scaler(scaler):
     return [float(x) for x in scaler]
 
 
+def transfer_pose(v, i, labels, mode, temperature, scaler):
+    """Merged top-k rows (v, i) -> (pose64 [B, 3] f64: lat, lon, angle_deg; pose4 [B, 4] f32, the fused head's format under
+    `scaler`) from the neighbours' labels: torch.ops.vpr.retrieval_pose without truth, so without its recall outputs."""
+    pose64, pose4, _, _ = torch.ops.vpr.retrieval_pose(v.contiguous(), i.contiguous(), labels, mode, temperature, None, 0.0, scaler)
+    return pose64, pose4
+
+
 def expansion_params(expand) -> Optional[dict]:
     """None, (n_use, alpha), or a dict with n_use and any of alpha, q_weight, rounds -> the keyword arguments of
     ShardedGallery.search_expanded after `k` (defaults alpha 3, q_weight 1, rounds 1)."""
@@ -210,14 +217,17 @@ class ShardedGallery:
             return self.engine.local_topk(q_all, self.rows, k, self.index_base, self.scales)
         return self.engine.local_topk(q_all, self.rows, k, self.index_base)
 
-    def search(self, q_all: torch.Tensor, k: int, ws=None, score_events=None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """q_all [B, D]: the same on every rank.  Returns merged (vals [B,k], idx [B,k]) on every rank.
-        score_events (HipEngine only): list collecting (start, end) timing events around the local score stage."""
-        v, i = self._local(self.project_queries(q_all), k, ws, score_events)
+    def _merged(self, v: torch.Tensor, i: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """This shard's (vals, idx) [B, k] -> the gallery's, the same on every rank: one packed all-gather and the merge."""
         if not self.collective:
             return v, i
         vs, is_ = all_gather_topk(v, i, self.world, self.group)
         return self.engine.merge(vs, is_)
+
+    def search(self, q_all: torch.Tensor, k: int, ws=None, score_events=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """q_all [B, D]: the same on every rank.  Returns merged (vals [B,k], idx [B,k]) on every rank.
+        score_events (HipEngine only): list collecting (start, end) timing events around the local score stage."""
+        return self._merged(*self._local(self.project_queries(q_all), k, ws, score_events))
 
     def search_reranked(self, q_all: torch.Tensor, k: int, kc: int, q_fine: Optional[torch.Tensor] = None,
                         ws=None, score_events=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -242,11 +252,7 @@ class ShardedGallery:
         if q_fine.shape[0] != q_all.shape[0]:
             raise ValueError("search_reranked: q_all and q_fine disagree on B")
         _, i = self._local(self.project_queries(q_all), kc, ws, score_events)
-        v, i = self.engine.rerank(q_fine, i.contiguous(), self.fine_rows, self.index_base, k)
-        if not self.collective:
-            return v, i
-        vs, is_ = all_gather_topk(v, i, self.world, self.group)
-        return self.engine.merge(vs, is_)
+        return self._merged(*self.engine.rerank(q_fine, i.contiguous(), self.fine_rows, self.index_base, k))
 
     def expand(self, q_all: torch.Tensor, vals: torch.Tensor, idx: torch.Tensor, n_use: int, alpha: float = 3.0,
                q_weight: float = 1.0) -> torch.Tensor:
@@ -284,25 +290,35 @@ class ShardedGallery:
             v, i = self.search(q_all, k, ws if ws2 is None else ws2)
         return v, i
 
-    def gather_fine_queries(self, q_local: torch.Tensor, q_proj: torch.Tensor, q_all: torch.Tensor) -> torch.Tensor:
-        """The fine tier's queries of the global batch: q_all itself unless a projection made the travelling rows narrower
-        than the caller's (q_proj is not q_local) — then the caller's own rows are gathered as well."""
-        return q_all if q_proj is q_local else self.gather_queries(q_local)
+    def search_gathered(self, q_all: torch.Tensor, k: int, expand=None, rerank: Optional[int] = None,
+                        q_fine: Optional[torch.Tensor] = None, ws=None, ws2=None,
+                        score_events=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The search that (expand, rerank) name, over queries that are the same on every rank: `search`, `search_reranked`
+        (rerank = kc) or `search_expanded` (expand: anything expansion_params takes; with rerank, of its last search).
+        q_fine, ws, ws2, score_events: as those take them; an expanded search has no seam for score_events."""
+        expand = expansion_params(expand)
+        if expand is not None:
+            if score_events is not None:
+                raise ValueError("search_gathered: score_events cannot be collected around an expanded search")
+            return self.search_expanded(q_all, k, ws=ws, ws2=ws2, rerank=rerank, q_fine=q_fine, **expand)
+        if rerank is not None:
+            return self.search_reranked(q_all, k, rerank, q_fine, ws, score_events)
+        return self.search(q_all, k, ws, score_events)
 
-    def search_local_queries(self, q_local: torch.Tensor, k: int, expand=None,
-                             rerank: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Data-parallel form: each rank contributes B_local queries and gets back its own rows.
+    def search_local_queries(self, q_local: torch.Tensor, k: int, expand=None, rerank: Optional[int] = None, *,
+                             ws=None, ws2=None, score_events=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Data-parallel form: each rank contributes B_local queries and gets back its own rows — project, gather, search
+        (search_gathered), keep this rank's rows.  The eager callers and GraphedRetrieval all go through here.
         expand: None, or the query expansion to search with (expansion_params).
         rerank = kc: the two-tier form (search_reranked; with `expand`, of its last search).  The fine queries are q_local's
-        rows: when a projection made the travelling rows d wide, the D_in-wide ones are gathered as well."""
+        rows: when a projection made the travelling rows d wide, the D_in-wide ones are gathered as well.
+        ws, ws2, score_events: handed to search_gathered."""
         q_proj = self.project_queries(q_local)
         q_all = self.gather_queries(q_proj)
+        q_fine = None
         if rerank is not None:
-            q_fine = self.gather_fine_queries(q_local, q_proj, q_all)
-            v, i = (self.search_reranked(q_all, k, rerank, q_fine) if expand is None
-                    else self.search_expanded(q_all, k, rerank=rerank, q_fine=q_fine, **expansion_params(expand)))
-        else:
-            v, i = self.search(q_all, k) if expand is None else self.search_expanded(q_all, k, **expansion_params(expand))
+            q_fine = q_all if q_proj is q_local else self.gather_queries(q_local)
+        v, i = self.search_gathered(q_all, k, expand, rerank, q_fine, ws, ws2, score_events)
         b = q_local.shape[0]
         return v[self.rank * b:(self.rank + 1) * b], i[self.rank * b:(self.rank + 1) * b]
 
@@ -339,7 +355,7 @@ class GraphedRetrieval:
 
     def __init__(self, gallery: ShardedGallery, batch_local: int, k: int, labels=None, mode: str = "top1",
                  temperature: float = 0.01, scaler=None, expand=None, rerank: Optional[int] = None):
-        self.g, self.k, self.b = gallery, k, batch_local
+        self.g, self.k = gallery, k
         self.rerank = None if rerank is None else int(rerank)
         self.expand = expansion_params(expand)
         self.labels = None if labels is None else pose_labels(labels, gallery.rows.device)
@@ -385,19 +401,9 @@ class GraphedRetrieval:
             pass
 
     def _run(self):
-        g = self.g
-        q_proj = g.project_queries(self.q)
-        q_all = g.gather_queries(q_proj)
-        q_fine = None if self.rerank is None else g.gather_fine_queries(self.q, q_proj, q_all)
-        if self.expand is None:
-            v, i = g.search(q_all, self.k, self.ws) if self.rerank is None else g.search_reranked(q_all, self.k, self.rerank, q_fine, self.ws)
-        else:
-            v, i = g.search_expanded(q_all, self.k, ws=self.ws, ws2=self.ws2, rerank=self.rerank, q_fine=q_fine, **self.expand)
-        lo = g.rank * self.b if g.collective else 0
-        v, i = v[lo:lo + self.b], i[lo:lo + self.b]
+        v, i = self.g.search_local_queries(self.q, self.k, self.expand, self.rerank, ws=self.ws, ws2=self.ws2)
         if self.labels is not None:
-            self.pose64, self.pose4, _, _ = torch.ops.vpr.retrieval_pose(v, i, self.labels, self.mode, self.temperature,
-                                                                         None, 0.0, self.scaler)
+            self.pose64, self.pose4 = transfer_pose(v, i, self.labels, self.mode, self.temperature, self.scaler)
         return v, i
 
     def __call__(self, q_local: torch.Tensor):
