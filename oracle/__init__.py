@@ -15,6 +15,9 @@ Pinning status:
     SuperGlue port (transformers ...superglue.modeling_superglue.log_sinkhorn_iterations, the routine SALAD's solver
     descends from): tests/test_oracle_selfchecks.py.  The SALAD-specific wiring (marginals, dustbin row, MLP layout,
     normalisation order) remains unpinned.
+  * salad_stages.py         — the same MLPs stage by stage (hidden activations, partial-sum slabs, token features), inputs
+    on which f32 arithmetic is exact in any order, and the per-element error bound of an f32-accumulating kernel; every
+    property the GPU tests rely on is asserted on the oracle alone in tests/test_oracle_selfchecks.py.
   * knn.py                  — PARITY UNPINNED by the reference: it has no retrieval code at all
     (SURVEY.md fact 3).  Brute-force definition of the stage's contract.
 """

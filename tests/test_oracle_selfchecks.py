@@ -574,3 +574,110 @@ def test_adamw_bound_rejects_mistakes(mistake):
     good, bad = _adam_ratio(oft.adamw_f32(p, m, v, g, c), p, m, v, g, c), _adam_ratio(got, p, m, v, g, c)
     print(f"\n[AdamW {mistake}] err / bound (p, m, v): right {good}, mistaken {bad}")
     assert max(good) <= 1.0 and bad[0] > 1.0
+
+
+# ------------------------------------------------------------------------- SALAD stage oracle (oracle/salad_stages.py)
+def _bf16_exact(x):
+    return torch.equal(x.float().to(torch.bfloat16).float(), x.float())
+
+
+@pytest.mark.parametrize("C", [64, 128, 192, 1536])
+def test_exact_salad_inputs_are_exact_in_any_f32_order(C):
+    """What tests/test_salad_stages_gpu.py relies on when it asks a kernel for the f64 bits: on the inputs of exact_inputs,
+    f32 arithmetic is exact under a permuted K order and a two-slab split of layer 2 (every partial sum is a multiple of
+    the grid below 2^24 grid steps), about half the hidden units are active, and the one rounding that IS there — hidden
+    values to bf16 — changes at least 1 % of them, exact ties (to even, both ways) among them."""
+    from oracle import salad_stages as ost
+    B = 2
+    tokens, w = ost.exact_inputs(C, B, seed=C)
+    for k, v in w.items():                                    # the grids, and that bf16 / f32 hold them
+        q = {"w1": 64, "b1": 8, "w2": 8, "b2": 64}[k[:2]]
+        assert torch.equal((v.double() * q).round(), v.double() * q) and v.double().abs().max() <= {"w1": .25, "b1": 2, "w2": .25, "b2": 1}[k[:2]]
+        assert v.dtype == (torch.bfloat16 if k.startswith("w") else torch.float32)
+    assert tokens.dtype == torch.bfloat16 and torch.equal(tokens.double().round(), tokens.double()) and tokens.double().abs().max() == 3
+    o = ost.salad_stage_outputs(tokens, w)
+    z, zt = ost.pre_activations(tokens, w)
+    W = {k: v.double() for k, v in w.items()}
+    x, cls = tokens[:, 1:].double().reshape(-1, C), tokens[:, 0].double()
+    hidden = 512
+    # magnitudes: sum of absolute terms below 2^24 grid steps in both layers, at dropout scale 2 as well
+    mag1 = max((x.abs() @ W["w1_sc"].abs().T + W["b1_sc"].abs()).max(), (cls.abs() @ W["w1_t"].abs().T + W["b1_t"].abs()).max()).item()
+    mag2 = max((o["H"][:, :hidden] @ W["w2_s"].abs().T + W["b2_s"].abs()).max(), (o["H"][:, hidden:] @ W["w2_c"].abs().T + W["b2_c"].abs()).max(),
+               (o["Ht"] @ W["w2_t"].abs().T + W["b2_t"].abs()).max()).item()
+    print(f"\n[exact SALAD inputs C={C}] sum|x||w1|+|b1| <= {mag1:.1f} (limit {ost.EXACT_LIMIT_1:.0f}), "
+          f"sum|h||w2|+|b2| <= {mag2:.1f} (limit {ost.EXACT_LIMIT_2:.0f})")
+    assert mag1 < ost.EXACT_LIMIT_1 == 2.0 ** 18 and 2 * mag2 < ost.EXACT_LIMIT_2 == 2.0 ** 15
+    for v, q in ((z, ost.Q1), (zt, ost.Q1), (o["H"], ost.Q1), (o["S"], ost.Q2), (o["F"], ost.Q2), (o["g"], ost.Q2)):
+        assert torch.equal((v / q).round(), v / q)
+    # layer 1 in f32 under a random permutation of K, and in two halves added afterwards
+    g = torch.Generator().manual_seed(C)
+    perm = torch.randperm(C, generator=g)
+    xf, w1f = x.float(), w["w1_sc"].float()
+    z32 = xf[:, perm] @ w1f[:, perm].T + w["b1_sc"]
+    half = (xf[:, perm[:C // 2]] @ w1f[:, perm[:C // 2]].T + w["b1_sc"]) + xf[:, perm[C // 2:]] @ w1f[:, perm[C // 2:]].T
+    assert torch.equal(z32.double(), z) and torch.equal(half.double(), z)
+    # layer 2 in f32: the two slabs, each over permuted hidden columns, slab 0 with the bias, added in f32
+    Hf = o["H"].float()
+    assert torch.equal(Hf.double(), o["H"]) and _bf16_exact(Hf)
+    for key, cols, w2, b2 in (("S", slice(0, hidden), w["w2_s"], w["b2_s"]), ("F", slice(hidden, 2 * hidden), w["w2_c"], w["b2_c"])):
+        h, w2f = Hf[:, cols], w2.float()
+        p0, p1 = torch.randperm(256, generator=g), 256 + torch.randperm(256, generator=g)
+        s0, s1 = h[:, p0] @ w2f[:, p0].T + b2, h[:, p1] @ w2f[:, p1].T
+        assert torch.equal(s0.double(), o[key][0]) and torch.equal(s1.double(), o[key][1])
+        assert torch.equal((s0 + s1).double(), o[key].sum(0))
+    s_ref, f_ref, g_ref = osalad.salad_mlps(tokens, w)            # the stage oracle is the MLP oracle, split
+    assert torch.equal(s_ref.reshape(-1, 64), o["S"].sum(0)) and torch.equal(f_ref.reshape(-1, 128), o["F"].sum(0)) and torch.equal(g_ref, o["g"])
+    s32, f32_, g32 = ost.salad_mlps_f32(tokens, w)
+    assert torch.equal(s32.double(), o["S"].sum(0)) and torch.equal(f32_.double(), o["F"].sum(0)) and torch.equal(g32.double(), o["g"])
+    # the one rounding: share of active units, of hidden values the rounding changes, ties both ways resolved to even
+    for name, zz in (("score/cluster", z), ("token", zt)):
+        h = torch.relu(zz)
+        hq = osalad.bf16_round(h)
+        active, changed = (zz > 0).double().mean().item(), (h != hq).double().mean().item()
+        other = 2 * h - hq                                       # a tie: the value on the other side is a bf16 number too
+        tie = (h != hq) & (osalad.bf16_round(other) == other)
+        up, down = (tie & (hq > h)).sum().item(), (tie & (hq < h)).sum().item()
+        print(f"  {name}: active {active:.3f}, changed by bf16 {changed:.4f}, ties up / down {up} / {down}")
+        assert active >= 0.30 and changed >= 0.01 and up > 0 and down > 0
+        even = (hq[tie].float().view(torch.int32) >> 16) & 1
+        assert int(even.sum()) == 0
+    # dropout at p = 0.5 doubles the kept values exactly (a power of two commutes with the rounding)
+    keep = torch.rand(z.shape, generator=g) < 0.5
+    assert torch.equal(ost.hidden_from(z, keep, 2.0), 2 * ost.hidden_from(z) * keep)
+    # and the mistakes the GPU test must catch do change the exact scores
+    for kind in ost.MUTATIONS:
+        assert not torch.equal(ost.mutated_scores(tokens, w, kind), o["S"].sum(0)), kind
+        assert torch.equal(ost.mutated_scores(tokens, w, kind).float().double(), ost.mutated_scores(tokens, w, kind)), kind
+
+
+@pytest.mark.parametrize("C,std", [(128, 0.02), (128, 0.08), (768, 0.02)])
+def test_salad_stage_error_bound_holds_plain_f32_and_rejects_mistakes(C, std):
+    """stage_error_bounds: no element of a plain f32 implementation (torch on the CPU, another summation order than any
+    kernel's) exceeds it, f32 with the K axis reversed neither; a dropped bias, exchanged rows and a zeroed W2 column do.
+    Hidden values left unrounded exceed it at C = 128 only (the bound lets a hidden value move where z sits within eps_z of
+    a rounding boundary, and eps_z grows with C): what catches them at every width is the RMS comparison of the GPU test,
+    rms(err) <= 4 rms(plain f32 err), restated here on the oracle."""
+    from oracle import salad_stages as ost
+    B = 1
+    tokens, w = ost.gaussian_inputs(C, B, seed=7, std=std)
+    o = ost.salad_stage_outputs(tokens, w)
+    ref = dict(S=o["S"].sum(0), F=o["F"].sum(0), g=o["g"])
+    bS, bF, bg = ost.stage_error_bounds(tokens, w)
+    assert bS.shape == ref["S"].shape and bF.shape == ref["F"].shape and bg.shape == ref["g"].shape
+    flip = lambda v: v.flip(-1)
+    for got in (ost.salad_mlps_f32(tokens, w),
+                ost.salad_mlps_f32(flip(tokens), {k: flip(v) if k.startswith("w1") else v for k, v in w.items()})):
+        ratios = [((a.double() - r).abs() / b).max().item() for a, r, b in zip(got, ref.values(), (bS, bF, bg))]
+        print(f"\n[SALAD stage bound C={C} std={std}] max bound S {bS.max():.2e} F {bF.max():.2e} g {bg.max():.2e}; "
+              f"f32 err / bound {[f'{r:.3f}' for r in ratios]}; S std {ref['S'].std():.3f}")
+        assert max(ratios) <= 1.0
+    assert bS.max().item() < 0.1 * ref["S"].std().item()          # loose, yet far below the signal
+    for kind in ost.MUTATIONS:
+        worst = ((ost.mutated_scores(tokens, w, kind) - ref["S"]).abs() / bS).max().item()
+        print(f"  {kind}: err / bound {worst:.2f}")
+        if kind != "skip_bf16_round":
+            assert worst > 1.0, kind
+        else:
+            e_mut, e_f32 = (ost.mutated_scores(tokens, w, kind) - ref["S"]).pow(2).mean().sqrt().item(), (got[0].double() - ref["S"]).pow(2).mean().sqrt().item()
+            print(f"  {kind}: rms err {e_mut:.2e} against plain f32 {e_f32:.2e}")
+            assert (worst > 1.0) == (C == 128) and e_mut > 4 * 4 * e_f32

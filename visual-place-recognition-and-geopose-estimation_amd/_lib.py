@@ -172,6 +172,13 @@ RERANK_PROTOTYPES = {
     "vpr_rerank_rows": (c_int, [_P, c_int, _P, c_int, c_int, c_int, _P, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
 }
 
+# include/vpr_amd_salad_stages.h, the fifth table
+_PP = POINTER(c_void_p)
+SALAD_STAGES_PROTOTYPES = {
+    # workspace workspace_bytes | B n C m l t hidden | S F g H (out pointers) | slabs slab_rows
+    "vpr_salad_stage_outputs": (c_int, [_P, c_size_t] + [c_int] * 7 + [_PP, _PP, _PP, _PP, POINTER(c_int), POINTER(c_longlong)]),
+}
+
 
 def rerank_roundings(D: int, rows_are_f32: bool) -> int:
     """VPR_RERANK_ROUNDINGS: L of the fine score, the roundings on the longest path from a product to the result."""
@@ -196,7 +203,7 @@ def lib() -> ctypes.CDLL:
         handle = ctypes.CDLL(path)
         for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(EXTENSION_PROTOTYPES.items())
                                           + list(EXPAND_PROTOTYPES.items()) + list(PROJECT_PROTOTYPES.items())
-                                          + list(RERANK_PROTOTYPES.items())):
+                                          + list(RERANK_PROTOTYPES.items()) + list(SALAD_STAGES_PROTOTYPES.items())):
             fn = getattr(handle, name)   # AttributeError if a declared symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

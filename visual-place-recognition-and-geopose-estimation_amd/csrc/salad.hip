@@ -18,6 +18,7 @@
 #include <math.h>
 #include "vpr_common.h"
 #include "vpr_internal.h"
+#include "../../include/vpr_amd_salad_stages.h"
 
 namespace vpr {
 
@@ -598,6 +599,23 @@ extern "C" int vpr_salad_stage_aggregate(int B, int n, int C, float dustbin, int
   SaladArgs a;
   VPR_TRY_LAUNCH(salad_args(&a, B, n, C, m, l, t, hidden, nullptr, workspace, workspace_bytes, false));
   return salad_stage_aggregate(a, dustbin, sinkhorn_iters, out_f32, out_bf16, static_cast<hipStream_t>(stream));
+}
+
+// include/vpr_amd_salad_stages.h: where stages T and M leave g, S, F (and, unfused, H) — the plan and the slab rule the
+// stages themselves use, nothing else; no launch, no device access.
+extern "C" int vpr_salad_stage_outputs(void* workspace, size_t workspace_bytes, int B, int n, int C, int m, int l, int t,
+                                       int hidden, float** S, float** F, float** g, uint16_t** H, int* slabs,
+                                       long long* slab_rows) {
+  if (!S || !F || !g || !slabs || !slab_rows) return VPR_ERR_INVALID_ARG;
+  SaladArgs a;
+  VPR_TRY_LAUNCH(salad_args(&a, B, n, C, m, l, t, hidden, nullptr, workspace, workspace_bytes, false));
+  *S = reinterpret_cast<float*>(a.ws + a.p.off_S);
+  *F = reinterpret_cast<float*>(a.ws + a.p.off_F);
+  *g = reinterpret_cast<float*>(a.ws + a.p.off_g);
+  if (H) *H = reinterpret_cast<uint16_t*>(a.ws + a.p.off_H);
+  *slabs = salad_slabs(n, C, m, l, hidden);
+  *slab_rows = (long long)B * n;
+  return VPR_OK;
 }
 
 // patch row r of image b at patch + b*patch_img_stride + r*C; cls token of image b at cls + b*cls_stride

@@ -321,6 +321,35 @@ def salad_aggregate_train(tokens, w: SaladWeights, dropout_p: float, seed: int, 
     return out, out16
 
 
+class SaladStageViews(NamedTuple):
+    S: torch.Tensor                  # [slabs, B*n, m] f32: partial-sum slabs of the cluster scores (slab 0 carries b2_s)
+    F: torch.Tensor                  # [slabs, B*n, l] f32: the same for the cluster features
+    g: torch.Tensor                  # [B, t] f32: token features
+    H: Optional[torch.Tensor]        # [B*n, 2*hidden] bf16 hidden activations — unfused route (slabs == 1) only, else None
+
+
+def salad_stage_views(ws: torch.Tensor, B: int, n: int, w: SaladWeights) -> SaladStageViews:
+    """Views of what stages T and M left in the SALAD workspace `ws` (ops.workspace("salad", ...) of the stream that ran
+    them) for a batch of B images x n patch tokens (tests).  The layout comes from vpr_salad_stage_outputs
+    (include/vpr_amd_salad_stages.h), which asks the library's own plan: nothing about it is restated here.  The route
+    (slabs) is the one the A/B switches select NOW, so ask before changing them."""
+    C, hidden, m, l, t = w.validate()
+    S, F, g, H = (ctypes.c_void_p(0) for _ in range(4))
+    slabs, rows = ctypes.c_int(0), ctypes.c_longlong(0)
+    _call("vpr_salad_stage_outputs", _ptr(ws), ws.numel(), B, n, C, m, l, t, hidden, ctypes.byref(S), ctypes.byref(F),
+          ctypes.byref(g), ctypes.byref(H), ctypes.byref(slabs), ctypes.byref(rows))
+
+    def view(p: ctypes.c_void_p, dtype: torch.dtype, *shape: int) -> torch.Tensor:
+        off, count = p.value - ws.data_ptr(), 1
+        for s in shape:
+            count *= s
+        return ws[off: off + count * dtype.itemsize].view(dtype).view(*shape)
+
+    ns, r = slabs.value, rows.value
+    return SaladStageViews(view(S, torch.float32, ns, r, m), view(F, torch.float32, ns, r, l), view(g, torch.float32, B, t),
+                           view(H, torch.bfloat16, r, 2 * hidden) if ns == 1 else None)
+
+
 @dataclass
 class SaladWeightsF32(SaladWeights):
     """The same ten tensors, all f32 (vpr_salad_weights_f32): operands of the f32-accurate aggregation."""
