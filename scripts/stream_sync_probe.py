@@ -9,7 +9,7 @@ hip.hipExtMallocWithFlags.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_
 hip.hipStreamWriteValue32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint]
 hip.hipStreamWaitValue32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint, ctypes.c_uint32]
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from vpr_amd.backbone import _RawEvents
+from vpr_amd._streams import _RawEvents
 dev = torch.device("cuda:0")
 a = torch.randn(8192, 1024, device=dev, dtype=torch.bfloat16)
 w = torch.randn(1024, 1024, device=dev, dtype=torch.bfloat16)

@@ -5,7 +5,7 @@ import weakref
 
 import torch
 
-from vpr_amd import _lib, ops
+from vpr_amd import _lib, _streams, ops
 from vpr_amd._cache import Cache, tensor_key
 from vpr_amd.backbone import DinoV2
 
@@ -163,8 +163,17 @@ def test_drop_stream_caches_reaches_every_stream_keyed_cache(monkeypatch):
     for c, key in ((ops._WORKSPACES, (0, stream, "test")), (ops._ZERO_ROWS, (0, stream, 4, 8))):
         c.get(key, _buf)
         assert key in c
+    # the one list holds every registry keyed by a stream: _streams' helper streams and fork / join objects included
+    assert [id(c) for c in ops._STREAM_KEYED] == [id(c) for c in (ops._WORKSPACES, ops._ZERO_ROWS, _streams._SIDES, _streams._SYNCS)]
+    for c in ops._STREAM_KEYED:
+        c.get((0, stream, "any"), _buf)
+        c.get((0, stream + 1, "any"), _buf)
     ops.drop_stream_caches(stream)
     assert (0, stream, "test") not in ops._WORKSPACES and (0, stream, 4, 8) not in ops._ZERO_ROWS
+    for c in ops._STREAM_KEYED:
+        assert (0, stream, "any") not in c and (0, stream + 1, "any") in c
+    ops.drop_stream_caches(stream + 1)
+    assert all(len([k for k in c._entries if k[1] in (stream, stream + 1)]) == 0 for c in ops._STREAM_KEYED)
 
 
 def test_cumulative_bias_follows_an_in_place_change_of_fc2_bias():

@@ -51,9 +51,11 @@ class Cache:
                 del self._entries[k]
 
     def drop(self, predicate: Callable[[Hashable], bool]) -> None:
-        """Forget every entry, pinned or not, whose key satisfies `predicate`."""
+        """Forget every entry, pinned or not, whose key satisfies `predicate`, and close() the values that have one (_streams)."""
         for k in [k for k in self._entries if predicate(k)]:
-            del self._entries[k]
+            close = getattr(self._entries.pop(k)[0], "close", None)
+            if close is not None:
+                close()
         self._outgrown = [(k, v) for k, v in self._outgrown if not predicate(k)]
 
     def __contains__(self, key: Hashable) -> bool:

@@ -10,12 +10,14 @@ layout vpr_salad_aggregate consumes directly (no permute to [B,C,16,16]).
 """
 from __future__ import annotations
 
+import os
 from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _streams
 from ._cache import tensor_key
 
 def gemm_autotune(enable: bool = True, tuning: bool = True, max_ms_per_gemm: int = 30) -> None:
@@ -24,7 +26,6 @@ def gemm_autotune(enable: bool = True, tuning: bool = True, max_ms_per_gemm: int
     in memory (PyTorch also dumps them to a scratch file in the temp dir at exit); call
     gemm_autotune(True, tuning=False) afterwards so the timed region only replays the choices.
     Plumbing around the library GEMMs, not a kernel."""
-    import os
     import tempfile
     import torch.cuda.tunable as tun
     tun.enable(enable)
@@ -48,122 +49,6 @@ def _ln(norm: nn.LayerNorm, x: torch.Tensor) -> torch.Tensor:
         from . import ops
         return ops.layernorm_bf16(x, norm.weight, norm.bias, norm.eps)
     return norm(x)
-
-
-class _StreamSignals:
-    """Fork / join between two HIP streams through stream memory operations (hipStreamWriteValue32 on the producer stream,
-    hipStreamWaitValue32 on the consumer stream, one 32-bit word of signal memory per direction, values from a counter that
-    only grows) instead of hipEventRecord + hipStreamWaitEvent.  Round-3 experiment, OFF by default: an event operation costs
-    the launch stream ~7 us of queue time whether or not anything has to be waited for (scripts/step_gaps.py: 14 us per block
-    of the ViT), and in a two-GEMM probe the memory operations are cheaper (scripts/stream_sync_probe.py: 21 -> 13.5 us per
-    fork + join pair) — but in the real step they are slower: 11.7-11.9 vs 11.31 ms per step (bench.py --side-sync signals, two
-    runs each, one box).  A wait is only ever enqueued AFTER its write has been enqueued, so no stream can be left waiting
-    for a value that never comes."""
-
-    def __init__(self, device: torch.device):
-        import ctypes
-        import os
-        hip = ctypes.CDLL(os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"))     # the runtime torch itself uses
-        hip.hipExtMallocWithFlags.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t, ctypes.c_uint]
-        hip.hipStreamWriteValue32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint]
-        hip.hipStreamWaitValue32.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint, ctypes.c_uint32]
-        hip.hipFree.argtypes = [ctypes.c_void_p]
-        self._hip, self._words, self.count = hip, [], 0
-        with torch.cuda.device(device):
-            for _ in range(2):
-                p = ctypes.c_void_p()
-                if hip.hipExtMallocWithFlags(ctypes.byref(p), 8, 0x2) != 0:          # hipMallocSignalMemory
-                    raise RuntimeError("hipExtMallocWithFlags(hipMallocSignalMemory) failed")
-                self._words.append(p)
-
-    def signal(self, word: int, stream: torch.cuda.Stream, value: int) -> None:
-        if self._hip.hipStreamWriteValue32(stream.cuda_stream, self._words[word], value & 0xFFFFFFFF, 0) != 0:
-            raise RuntimeError("hipStreamWriteValue32 failed")
-
-    def wait(self, word: int, stream: torch.cuda.Stream, value: int) -> None:
-        # hipStreamWaitValueEq: the words only ever hold the value of the latest signal, and a wait for value v is enqueued
-        # before the signal for v + 1 can be (program order of the loop), so equality is exact even across the 2^32 wrap
-        if self._hip.hipStreamWaitValue32(stream.cuda_stream, self._words[word], value & 0xFFFFFFFF, 0x1, 0xFFFFFFFF) != 0:
-            raise RuntimeError("hipStreamWaitValue32 failed")
-
-    # the three-call protocol _blocks_side_chain uses (same as _TorchEvents / _RawEvents)
-    def fork(self, main: torch.cuda.Stream, side: torch.cuda.Stream) -> None:
-        self.count += 1
-        self.signal(0, main, self.count)
-        self.wait(0, side, self.count)
-
-    def mark(self, side: torch.cuda.Stream) -> int:
-        self.signal(1, side, self.count)
-        return self.count
-
-    def join(self, main: torch.cuda.Stream, tick: int) -> None:
-        self.wait(1, main, tick)
-
-
-class _TorchEvents:
-    """Fork / join by torch.cuda.Event (hipEventDisableTiming; the record carries a system-scope release)."""
-
-    def fork(self, main: torch.cuda.Stream, side: torch.cuda.Stream) -> None:
-        e = torch.cuda.Event()
-        e.record(main)
-        side.wait_event(e)
-
-    def mark(self, side: torch.cuda.Stream) -> "torch.cuda.Event":
-        e = torch.cuda.Event()
-        e.record(side)
-        return e
-
-    def join(self, main: torch.cuda.Stream, e: "torch.cuda.Event") -> None:
-        main.wait_event(e)
-
-
-class _RawEvents:
-    """Fork / join by HIP events created with hipEventDisableTiming | hipEventDisableSystemFence (torch.cuda.Event cannot pass
-    the second flag): the record then carries no system-scope cache writeback / invalidate — both streams are queues of
-    the same device, device scope is all the hand-over needs.  A ring of events: a wait refers to the record that was
-    latest when the wait was enqueued, so re-recording an event later never disturbs a wait already in a queue."""
-    RING = 128
-
-    def __init__(self, device: torch.device, flags: int = 0x2 | 0x20000000):
-        import ctypes
-        import os
-        hip = ctypes.CDLL(os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"))
-        hip.hipEventCreateWithFlags.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint]
-        hip.hipEventRecord.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        hip.hipStreamWaitEvent.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint]
-        hip.hipEventDestroy.argtypes = [ctypes.c_void_p]
-        self._hip, self._ring, self._next = hip, [], 0
-        with torch.cuda.device(device):
-            for _ in range(self.RING):
-                e = ctypes.c_void_p()
-                st = hip.hipEventCreateWithFlags(ctypes.byref(e), flags)
-                if st != 0:
-                    raise RuntimeError(f"hipEventCreateWithFlags(0x{flags:x}) failed: hipError {st}")
-                self._ring.append(e)
-
-    def __del__(self):
-        for e in getattr(self, "_ring", []):
-            self._hip.hipEventDestroy(e)
-
-    def _record(self, stream: torch.cuda.Stream):
-        e = self._ring[self._next]
-        self._next = (self._next + 1) % self.RING
-        if self._hip.hipEventRecord(e, stream.cuda_stream) != 0:
-            raise RuntimeError("hipEventRecord failed")
-        return e
-
-    def _wait(self, stream: torch.cuda.Stream, e) -> None:
-        if self._hip.hipStreamWaitEvent(stream.cuda_stream, e, 0) != 0:
-            raise RuntimeError("hipStreamWaitEvent failed")
-
-    def fork(self, main: torch.cuda.Stream, side: torch.cuda.Stream) -> None:
-        self._wait(side, self._record(main))
-
-    def mark(self, side: torch.cuda.Stream):
-        return self._record(side)
-
-    def join(self, main: torch.cuda.Stream, e) -> None:
-        self._wait(main, e)
 
 
 class SplitTokens(NamedTuple):
@@ -347,9 +232,8 @@ class DinoV2(nn.Module):
         return c
 
     cls_side_chain = True
-    side_sync = "events"        # fork / join of the cls side chain: "events" (torch.cuda.Event), "light" (HIP events without the system-scope
-                                # fence, _RawEvents), "signals" (stream memory operations, _StreamSignals: measured SLOWER in the step,
-                                # 11.7-11.9 vs 11.31 ms, although the two-GEMM probe favours them).  bench.py --side-sync
+    side_sync = "events"        # fork / join of the cls side chain (_streams): "events" (torch.cuda.Event), "light" (HIP events without the
+                                # system-scope fence), "signals" (stream memory operations: measured SLOWER in the step).  bench.py --side-sync
 
     def _blocks_side_chain(self, x: torch.Tensor, h: torch.Tensor, cum: torch.Tensor, B: int, n: int, C: int) -> "SplitTokens":
         """The 24 blocks with the cls rows on their own stream.  Between two attentions the B cls rows need six
@@ -366,25 +250,13 @@ class DinoV2(nn.Module):
         dev, bf = x.device, torch.bfloat16
         blocks = self.blocks
         main = torch.cuda.current_stream(dev)
-        sides = self.__dict__.setdefault("_sides", {})      # one side stream per (device, main stream)
-        skey = (str(dev), main.cuda_stream)
-        side = sides.get(skey)
-        if side is None:
-            # high priority: the cls-row workgroups take the first CU slots a retiring GEMM workgroup frees (the
-            # library GEMMs fill every CU, so at equal priority the small kernels sit in the queue: 40-95 us each)
-            import os
-            prio = int(os.environ.get("VPR_SIDE_PRIORITY", "-1"))
-            side = sides[skey] = torch.cuda.Stream(device=dev, priority=prio)
+        # high priority: the cls-row workgroups take the first CU slots a retiring GEMM workgroup frees (the
+        # library GEMMs fill every CU, so at equal priority the small kernels sit in the queue: 40-95 us each)
+        side = _streams.side_stream(dev, main.cuda_stream, "cls", int(os.environ.get("VPR_SIDE_PRIORITY", "-1")))
         mode = self.side_sync if not torch.cuda.is_current_stream_capturing() else "events"     # capture: plain event nodes
         if mode not in ("events", "light", "signals"):
             raise RuntimeError(f"DinoV2.side_sync: unknown mode {mode!r}")
-        if mode == "events":
-            sync = _TorchEvents()
-        else:
-            syncs = self.__dict__.setdefault("_syncs", {})
-            sync = syncs.get(skey + (mode,))
-            if sync is None:
-                sync = syncs[skey + (mode,)] = _StreamSignals(dev) if mode == "signals" else _RawEvents(dev)
+        sync = _streams.fork_join(dev, main.cuda_stream, mode)      # "events": a fresh object; else kept per main stream
         C3, C4 = blocks[0].qkv.weight.shape[0], blocks[0].fc1.weight.shape[0]
         xp, xc = x[:Mp], x[Mp:]
         hp = h[:Mp]
@@ -411,7 +283,7 @@ class DinoV2(nn.Module):
                 else:
                     cls_out = hc2
                     if self.cls_tail_hook is not None:     # e.g. SALAD's token MLP: needs the cls rows only, rides on this stream
-                        self.cls_tail_hook(cls_out, main.cuda_stream)
+                        self.cls_tail_hook(cls_out, main.cuda_stream, n)
                         hooked = True
                 joined = sync.mark(side)
             xp.addmm_(att[:Mp], blk.proj.weight.t())
@@ -425,8 +297,8 @@ class DinoV2(nn.Module):
             qkv = qkv_next                 # (att stayed referenced up to here)
         return SplitTokens(hp.view(B, n, C), cls_out, hooked)
 
-    # optional callable(cls_rows [B, C] bf16, raw handle of the main stream): run on the cls-row side stream right after the
-    # final LayerNorm of the cls rows, before that stream is joined (modules.DinoV2Salad installs SALAD's token MLP here)
+    # optional callable(cls_rows [B, C] bf16, raw handle of the main stream, patch tokens per image n): run on the cls-row side
+    # stream right after the final LayerNorm of the cls rows, before that stream is joined (modules.DinoV2Salad installs SALAD's token MLP here)
     cls_tail_hook = None
 
     def _forward_hip_split(self, img: torch.Tensor) -> "SplitTokens":

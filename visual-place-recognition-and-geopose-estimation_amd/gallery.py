@@ -24,7 +24,7 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import ops
+from . import _streams, ops
 from .projection import DescriptorProjection
 from .retrieval import ShardedGallery, shard_bounds
 
@@ -255,14 +255,12 @@ class GraphedLocalTopK:
         self.q = torch.zeros((batch, D), dtype=shard.rows.dtype, device=dev)
         self.q_scale = torch.ones((batch,), dtype=torch.float32, device=dev) if self.fp8 else None
         self.ws = ops.knn_workspace(batch, shard.rows.shape[0], D, k, dev)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):          # warm-up outside capture (module load, allocator)
-            self._run()
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.vals, self.idx = self._run()
+        self._captured = _streams.Captured(self._run, dev, 1)
+        self.vals, self.idx = self._captured.out
+
+    def close(self) -> None:
+        """Destroy the graph and forget what the package keyed by its private stream (also runs when it is collected)."""
+        self._captured.close()
 
     def _run(self):
         s = self.shard
@@ -274,7 +272,7 @@ class GraphedLocalTopK:
         self.q.copy_(q)
         if self.fp8:
             self.q_scale.copy_(q_scale)
-        self.graph.replay()
+        self._captured.graph.replay()
         return self.vals, self.idx
 
 

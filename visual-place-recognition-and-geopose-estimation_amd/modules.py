@@ -79,12 +79,12 @@ class SaladAggregator(nn.Module):
             dustbin=float(self.dust_bin.detach().cpu()))
         return self._packed_f32
 
-    def token_stage(self, cls_rows: torch.Tensor, owner_raw_stream: int) -> None:
-        """The token MLP of these cls rows on the current stream, into the workspace of `owner_raw_stream`
-        (backbone.DinoV2.cls_tail_hook: the backbone's cls-row stream has the cls tokens ~0.3 ms before the main stream has
-        the patch tokens, so the stage costs the step nothing)."""
+    def token_stage(self, cls_rows: torch.Tensor, owner_raw_stream: int, n: int) -> None:
+        """The token MLP of these cls rows (images of n patch tokens) on the current stream, into the workspace of
+        `owner_raw_stream` (backbone.DinoV2.cls_tail_hook: the backbone's cls-row stream has the cls tokens ~0.3 ms before
+        the main stream has the patch tokens, so the stage costs the step nothing)."""
         w = self._packed or self.pack()
-        ops.salad_stage_token(cls_rows, w, 256, owner_raw_stream)
+        ops.salad_stage_token(cls_rows, w, n, owner_raw_stream)
 
     @torch.no_grad()
     def forward(self, tokens, want_bf16: bool = False):

@@ -51,11 +51,7 @@ def capturing() -> bool:
 
 def cache(capacity: Optional[int] = None) -> Cache:
     """A _cache.Cache that asks this module's capturing() (looked up per call: a test can substitute it)."""
-    return Cache(_capturing, capacity)
-
-
-def _capturing() -> bool:
-    return capturing()
+    return Cache(lambda: capturing(), capacity)
 
 
 def _call(name: str, *args) -> None:
@@ -69,7 +65,7 @@ def _call(name: str, *args) -> None:
 # flight) never share scratch memory, and drop_stream_caches() forgets a stream that is gone.
 _WORKSPACES = cache()
 _ZERO_ROWS = cache(8)
-_STREAM_KEYED = (_WORKSPACES, _ZERO_ROWS)
+_STREAM_KEYED = [_WORKSPACES, _ZERO_ROWS]       # the one list: _streams adds its helper-stream and fork / join registries
 
 
 def _alloc_bytes(nbytes: int, device: torch.device, zero: bool) -> torch.Tensor:
@@ -100,8 +96,8 @@ def zero_rows_bf16(M: int, C: int, device: torch.device) -> torch.Tensor:
 
 
 def drop_stream_caches(raw_stream: int) -> None:
-    """Forget every stream-keyed entry (workspaces, raw-token buffers) of this stream handle, pinned ones included
-    (graphed.GraphedForward.close(): its private stream is gone, and so are the graphs that addressed the buffers)."""
+    """Forget every entry keyed by this stream handle (workspaces, raw-token buffers, its helper streams and fork / join objects:
+    _streams), pinned ones included (_streams.Captured.close(): the private stream is gone, with the graphs that addressed them)."""
     for c in _STREAM_KEYED:
         c.drop(lambda k: k[1] == raw_stream)
 
@@ -226,17 +222,6 @@ def salad_aggregate(tokens: torch.Tensor, w: SaladWeights, sinkhorn_iters: int =
     return out, out16
 
 
-_SALAD_SIDE: dict = {}
-
-
-def _salad_side_stream(device: torch.device, main_raw: int) -> torch.cuda.Stream:
-    key = (device.index if device.index is not None else torch.cuda.current_device(), main_raw)
-    s = _SALAD_SIDE.get(key)
-    if s is None:
-        s = _SALAD_SIDE[key] = torch.cuda.Stream(device=device)
-    return s
-
-
 def salad_stage_token(cls: torch.Tensor, w: SaladWeights, n: int, owner_raw_stream: int) -> None:
     """Stage T of the aggregation on its own (vpr_salad_stage_token): token MLP of the B cls rows on the CURRENT stream,
     result left in the SALAD workspace that belongs to stream `owner_raw_stream` (the stream that will run
@@ -280,10 +265,10 @@ def salad_aggregate_split(patch: torch.Tensor, cls: torch.Tensor, w: SaladWeight
         _call("vpr_salad_aggregate_split", _ptr(patch), _ptr(cls), B, n, C, ctypes.byref(cw), float(w.dustbin), m, l, t,
               hidden, int(sinkhorn_iters), _ptr(out), _ptr(out16), _ptr(ws), ws.numel(), _stream())
         return out, out16
-    dev_idx = patch.device.index if patch.device.index is not None else torch.cuda.current_device()
-    main_raw = ctypes.c_void_p(_raw_stream(dev_idx))
     main = torch.cuda.current_stream(patch.device)
-    side = _salad_side_stream(patch.device, main_raw.value)
+    main_raw = ctypes.c_void_p(main.cuda_stream)
+    from . import _streams
+    side = _streams.side_stream(patch.device, main_raw.value, "salad")
     side.wait_stream(main)                                   # cls (and the workspace's previous consumer) are ready
     _call("vpr_salad_stage_token", _ptr(cls), C, B, n, C, ctypes.byref(cw), m, l, t, hidden, _ptr(ws), ws.numel(),
           ctypes.c_void_p(side.cuda_stream))

@@ -12,6 +12,7 @@ from typing import Optional
 
 import torch
 
+from . import _streams
 from .modules import DinoV2Salad, FusedGeoPoseHead
 from .retrieval import GraphedRetrieval, ShardedGallery, pose_labels, pose_scaler, transfer_pose
 
@@ -52,14 +53,6 @@ class VPRGeoPosePipeline:
         # The pose head needs only the descriptor; the retrieval leg (two collectives with launch-latency gaps between
         # them when the gallery is sharded) runs beside it: head on a side stream, joined at the end of the step.
         self.overlap_head = gallery.collective if overlap_head is None else overlap_head
-        self._side = {}
-
-    def _side_stream(self, dev, main):
-        key = (str(dev), main.cuda_stream)
-        s = self._side.get(key)
-        if s is None:
-            s = self._side[key] = torch.cuda.Stream(device=dev)
-        return s
 
     @torch.no_grad()
     def step(self, images: torch.Tensor) -> StepOutput:
@@ -68,7 +61,7 @@ class VPRGeoPosePipeline:
         pose = rpose = None
         if self.overlap_head:
             main = torch.cuda.current_stream(desc.device)
-            side = self._side_stream(desc.device, main)
+            side = _streams.side_stream(desc.device, main.cuda_stream, "head")
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 pose = self.head(desc)

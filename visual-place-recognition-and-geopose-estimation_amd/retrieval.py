@@ -17,7 +17,7 @@ from typing import Optional, Tuple
 import torch
 import torch.distributed as dist
 
-from . import ops
+from . import _streams, ops
 from . import torch_ops  # noqa: F401  registers torch.ops.vpr.*
 
 
@@ -372,33 +372,15 @@ class GraphedRetrieval:
         B = batch_local * (gallery.world if gallery.collective else 1)
         self.ws = ops.knn_workspace(B, rows.shape[0], D, k if self.rerank is None else max(k, self.rerank), dev)
         self.ws2 = None if self.expand is None else ops.workspace("knn_expanded", self.ws.numel(), dev)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
         counted = gallery.uncertified.clone() if gallery.uncertified is not None else None
-        with torch.cuda.stream(side):            # warm-up outside capture: module load, allocator, communicator set-up
-            for _ in range(2):
-                self._run()
-            if counted is not None:              # the warm-up's all-zero queries (every score ties) are not searches
-                gallery.uncertified.copy_(counted)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        self.graph = torch.cuda.CUDAGraph()
-        self._stream = side
-        with torch.cuda.graph(self.graph, stream=side):      # the warm-up's stream: stream-keyed workspaces are re-used, not re-allocated
-            self.vals, self.idx = self._run()
+        self._captured = _streams.Captured(self._run, dev)      # the warm-up also sets the communicator up
+        if counted is not None:                  # the warm-up's all-zero queries (every score ties) are not searches; the
+            gallery.uncertified.copy_(counted)   # device is idle since the warm-up and the capture ran nothing
+        self.vals, self.idx = self._captured.out
 
     def close(self) -> None:
-        """Destroy the graph and drop the stream-keyed workspaces its private stream left in the package caches."""
-        self.graph = None
-        if self._stream is not None:
-            ops.drop_stream_caches(self._stream.cuda_stream)
-            self._stream = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:                     # noqa: BLE001
-            pass
+        """Destroy the graph and forget what the package keyed by its private stream (_streams.Captured.close)."""
+        self._captured.close()
 
     def _run(self):
         v, i = self.g.search_local_queries(self.q, self.k, self.expand, self.rerank, ws=self.ws, ws2=self.ws2)
@@ -408,5 +390,5 @@ class GraphedRetrieval:
 
     def __call__(self, q_local: torch.Tensor):
         self.q.copy_(q_local)
-        self.graph.replay()
+        self._captured.graph.replay()
         return self.vals, self.idx
