@@ -179,6 +179,18 @@ SALAD_STAGES_PROTOTYPES = {
     "vpr_salad_stage_outputs": (c_int, [_P, c_size_t] + [c_int] * 7 + [_PP, _PP, _PP, _PP, POINTER(c_int), POINTER(c_longlong)]),
 }
 
+# include/vpr_amd_salad_anyres.h, the sixth table: the aggregation for a run-time patch-token count
+SALAD_MAX_N = 576                             # VPR_SALAD_MAX_N
+SALAD_ANYRES_PROTOTYPES = {
+    # scores feats tokfeat | B n m l t | dustbin iters | out_f32 out_bf16 | stream
+    "vpr_salad_sinkhorn_aggregate_n": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P, _P, _P]),
+    # patch patch_img_stride cls cls_stride | B n C | weights dustbin | m l t hidden iters | out_f32 out_bf16 | workspace bytes | stream
+    "vpr_salad_aggregate_n": (c_int, [_P, c_longlong, _P, c_longlong, c_int, c_int, c_int, POINTER(SaladWeightsC), c_float,
+                                      c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "vpr_salad_aggregate_f32_n": (c_int, [_P, c_longlong, _P, c_longlong, c_int, c_int, c_int, POINTER(SaladWeightsF32C), c_float,
+                                          c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+}
+
 
 def rerank_roundings(D: int, rows_are_f32: bool) -> int:
     """VPR_RERANK_ROUNDINGS: L of the fine score, the roundings on the longest path from a product to the result."""
@@ -203,7 +215,8 @@ def lib() -> ctypes.CDLL:
         handle = ctypes.CDLL(path)
         for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(EXTENSION_PROTOTYPES.items())
                                           + list(EXPAND_PROTOTYPES.items()) + list(PROJECT_PROTOTYPES.items())
-                                          + list(RERANK_PROTOTYPES.items()) + list(SALAD_STAGES_PROTOTYPES.items())):
+                                          + list(RERANK_PROTOTYPES.items()) + list(SALAD_STAGES_PROTOTYPES.items())
+                                          + list(SALAD_ANYRES_PROTOTYPES.items())):
             fn = getattr(handle, name)   # AttributeError if a declared symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

@@ -15,10 +15,13 @@
 //                                 P as two bf16 planes, V = F^T P^T as three exact-product bf16 MFMAs on the (hi, lo) terms
 //                                 (f32 accuracy), the three L2 normalisations, 8448 outputs (f32 + bf16 copy for the kNN stage)
 //   vpr_salad_aggregate_f32: the same at the reference's fp32 precision (three bf16 planes per operand, f32 hidden).
+//   vpr_salad_aggregate_n / _f32_n (include/vpr_amd_salad_anyres.h): any token count 65 .. 576 — stages T and the unfused M
+//   as above, stage A by sinkhorn_aggregate_n_kernel (salad_anyres.hip); everything else here stays n = 256.
 #include <math.h>
 #include "vpr_common.h"
 #include "vpr_internal.h"
 #include "../../include/vpr_amd_salad_stages.h"
+#include "../../include/vpr_amd_salad_anyres.h"
 
 namespace vpr {
 
@@ -475,15 +478,18 @@ struct SaladArgs {
   char* ws;
   SaladPlan p;
 };
+// anyres (include/vpr_amd_salad_anyres.h): m < n <= VPR_SALAD_MAX_N instead of n == 256; `misaligned`: what that call found
+// wrong with its pointers and strides, refused here so that its statuses come in the order of every other call.
 static int salad_args(SaladArgs* a, int B, int n, int C, int m, int l, int t, int hidden, const vpr_salad_weights* w,
-                      void* workspace, size_t workspace_bytes, bool need_w) {
+                      void* workspace, size_t workspace_bytes, bool need_w, bool anyres = false, bool misaligned = false) {
   if (!workspace || B <= 0 || n < 1 || C <= 0) return VPR_ERR_INVALID_ARG;
   if (need_w) {
     if (!w) return VPR_ERR_INVALID_ARG;
     if (!w->w1_sc || !w->b1_sc || !w->w2_s || !w->b2_s || !w->w2_c || !w->b2_c || !w->w1_t || !w->b1_t || !w->w2_t || !w->b2_t)
       return VPR_ERR_INVALID_ARG;
   }
-  if (n != SA_N || m != SA_M || l != SA_L || t != SA_T || (C % 64) || (hidden % 64)) return VPR_ERR_UNSUPPORTED;
+  if (m != SA_M || l != SA_L || t != SA_T || (C % 64) || (hidden % 64)) return VPR_ERR_UNSUPPORTED;
+  if (anyres ? (n <= SA_M || n > VPR_SALAD_MAX_N || misaligned) : n != SA_N) return VPR_ERR_UNSUPPORTED;
   if (!salad_plan(B, n, C, m, l, t, hidden, &a->p)) return VPR_ERR_INVALID_ARG;
   if (workspace_bytes < a->p.total) return VPR_ERR_WORKSPACE;
   a->B = B; a->n = n; a->C = C; a->m = m; a->l = l; a->t = t; a->hidden = hidden; a->w = w;
@@ -655,6 +661,33 @@ extern "C" int vpr_salad_aggregate_split(const uint16_t* patch_tokens, const uin
                    m, l, t, hidden, sinkhorn_iters, out_f32, out_bf16, workspace, workspace_bytes, stream);
 }
 
+// include/vpr_amd_salad_anyres.h: n == 256 is salad_run (the same bits as vpr_salad_aggregate_split); any other n runs stage
+// T, the unfused stage M (salad_slabs() is 1 off n == 256) and the run-time-n stage A.  Everything a stage could refuse is
+// checked here first, so a refused call has launched nothing.
+extern "C" int vpr_salad_aggregate_n(const uint16_t* patch, long long patch_img_stride, const uint16_t* cls, long long cls_stride,
+                                     int B, int n, int C, const vpr_salad_weights* w, float dustbin,
+                                     int m, int l, int t, int hidden, int sinkhorn_iters,
+                                     float* out_f32, uint16_t* out_bf16,
+                                     void* workspace, size_t workspace_bytes, void* stream_) {
+  if (!patch || !cls || !out_f32 || sinkhorn_iters < 1) return VPR_ERR_INVALID_ARG;
+  if (n == SA_N)
+    return salad_run(patch, patch_img_stride, cls, cls_stride, B, n, C, w, dustbin, m, l, t, hidden, sinkhorn_iters, out_f32,
+                     out_bf16, workspace, workspace_bytes, stream_);
+  bool misaligned = (patch_img_stride % 8) || (cls_stride % 8) || cls_stride > 0x7fffffffLL || cls_stride < 0 ||
+                    !aligned16(patch) || !aligned16(cls) || !aligned16(workspace) || !aligned4(out_f32) ||
+                    (reinterpret_cast<uintptr_t>(out_bf16) & 1);
+  if (w) misaligned = misaligned || !aligned16(w->w1_sc) || !aligned16(w->w2_s) || !aligned16(w->w2_c) || !aligned16(w->w1_t) ||
+                      !aligned16(w->w2_t);
+  SaladArgs a;
+  VPR_TRY_LAUNCH(salad_args(&a, B, n, C, m, l, t, hidden, w, workspace, workspace_bytes, true, true, misaligned));
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  VPR_TRY_LAUNCH(salad_stage_token(a, cls, cls_stride, stream));
+  VPR_TRY_LAUNCH(salad_stage_mlps(a, patch, patch_img_stride, stream));
+  return launch_sinkhorn_aggregate_n(reinterpret_cast<const float*>(a.ws + a.p.off_S), reinterpret_cast<const float*>(a.ws + a.p.off_F),
+                                     reinterpret_cast<const float*>(a.ws + a.p.off_g), B, n, m, l, t, dustbin, sinkhorn_iters,
+                                     out_f32, out_bf16, stream);
+}
+
 // Train mode (include/vpr_amd.h, vpr_salad_aggregate_train): the hub model's Dropout layers of score / cluster_features
 // active.  Stage M runs first — it is the stage that may refuse (dropout exists on the fused route only), so a refused call
 // has launched nothing; stages T and A are those of the eval form.
@@ -773,15 +806,18 @@ extern "C" size_t vpr_salad_f32_workspace_bytes(int B, int n, int C, int m, int 
   return salad_f32_plan(B, n, C, m, l, t, hidden, &p) ? p.total : 0;
 }
 
-extern "C" int vpr_salad_aggregate_f32(const float* patch, long long patch_img_stride, const float* cls, long long cls_stride,
-                                       int B, int n, int C, const vpr_salad_weights_f32* w, float dustbin,
-                                       int m, int l, int t, int hidden, int sinkhorn_iters,
-                                       float* out_f32, uint16_t* out_bf16,
-                                       void* workspace, size_t workspace_bytes, void* stream_) {
+// anyres (vpr_salad_aggregate_f32_n): m < n <= VPR_SALAD_MAX_N, stage A by the run-time-n kernel off n == 256
+static int salad_f32_run(const float* patch, long long patch_img_stride, const float* cls, long long cls_stride,
+                         int B, int n, int C, const vpr_salad_weights_f32* w, float dustbin,
+                         int m, int l, int t, int hidden, int sinkhorn_iters,
+                         float* out_f32, uint16_t* out_bf16,
+                         void* workspace, size_t workspace_bytes, void* stream_, bool anyres) {
+  if (anyres && sinkhorn_iters < 1) return VPR_ERR_INVALID_ARG;
   if (!patch || !cls || !w || !out_f32 || !workspace || B <= 0 || n < 1 || C <= 0) return VPR_ERR_INVALID_ARG;
   if (!w->w1_sc || !w->b1_sc || !w->w2_s || !w->b2_s || !w->w2_c || !w->b2_c || !w->w1_t || !w->b1_t || !w->w2_t || !w->b2_t)
     return VPR_ERR_INVALID_ARG;
-  if (n != SA_N || m != SA_M || l != SA_L || t != SA_T || (C % 64) || (hidden % 64)) return VPR_ERR_UNSUPPORTED;
+  if (m != SA_M || l != SA_L || t != SA_T || (C % 64) || (hidden % 64)) return VPR_ERR_UNSUPPORTED;
+  if (anyres ? (n <= SA_M || n > VPR_SALAD_MAX_N) : n != SA_N) return VPR_ERR_UNSUPPORTED;
   if ((patch_img_stride % 4) || (cls_stride % 4) || patch_img_stride < (long long)n * C || cls_stride < C) return VPR_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(patch) | reinterpret_cast<uintptr_t>(cls) | reinterpret_cast<uintptr_t>(w->w1_sc) |
        reinterpret_cast<uintptr_t>(w->w2_s) | reinterpret_cast<uintptr_t>(w->w2_c) | reinterpret_cast<uintptr_t>(w->w1_t) |
@@ -823,5 +859,24 @@ extern "C" int vpr_salad_aggregate_f32(const float* patch, long long patch_img_s
       {H2 + K2, 2 * K2, 0, 0, W2c, K2, w->b2_c, 0, F, l, 0, (int)rows, l, K2, 0, 0},
       {Ht2, K2, 0, 0, W2t, K2, w->b2_t, 0, g, t, 0, B, t, K2, 0, 0}};
   VPR_TRY_LAUNCH(launch_gemm_nt_group(l2, 3, stream));
+  if (n != SA_N) return launch_sinkhorn_aggregate_n(S, F, g, B, n, m, l, t, dustbin, sinkhorn_iters, out_f32, out_bf16, stream);
   return launch_sinkhorn_aggregate(S, F, g, B, n, m, l, t, dustbin, sinkhorn_iters, out_f32, out_bf16, stream);
+}
+
+extern "C" int vpr_salad_aggregate_f32(const float* patch, long long patch_img_stride, const float* cls, long long cls_stride,
+                                       int B, int n, int C, const vpr_salad_weights_f32* w, float dustbin,
+                                       int m, int l, int t, int hidden, int sinkhorn_iters,
+                                       float* out_f32, uint16_t* out_bf16,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+  return salad_f32_run(patch, patch_img_stride, cls, cls_stride, B, n, C, w, dustbin, m, l, t, hidden, sinkhorn_iters, out_f32,
+                       out_bf16, workspace, workspace_bytes, stream, false);
+}
+
+extern "C" int vpr_salad_aggregate_f32_n(const float* patch, long long patch_img_stride, const float* cls, long long cls_stride,
+                                         int B, int n, int C, const vpr_salad_weights_f32* w, float dustbin,
+                                         int m, int l, int t, int hidden, int sinkhorn_iters,
+                                         float* out_f32, uint16_t* out_bf16,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  return salad_f32_run(patch, patch_img_stride, cls, cls_stride, B, n, C, w, dustbin, m, l, t, hidden, sinkhorn_iters, out_f32,
+                       out_bf16, workspace, workspace_bytes, stream, true);
 }

@@ -56,6 +56,11 @@ int launch_sinkhorn_aggregate(const float* scores, const float* feats, const flo
                               float* out_f32, uint16_t* out_bf16, hipStream_t stream, int nslab = 1, long long slab_rows = 0,
                               int* counters = nullptr);
 
+// salad_anyres.hip: stage A for a run-time token count m < n <= VPR_SALAD_MAX_N (one dense slab of scores / feats)
+int launch_sinkhorn_aggregate_n(const float* scores, const float* feats, const float* tokfeat,
+                                int B, int n, int m, int l, int t, float dustbin, int iters,
+                                float* out_f32, uint16_t* out_bf16, hipStream_t stream);
+
 // Launch through hipLaunchKernel(), whose return value is THIS launch's status.  (The
 // hipGetLastError() idiom reads a per-thread sticky value that other libraries in the process —
 // e.g. hipBLASLt's kernel lookups inside PyTorch — leave set, so it cannot be trusted here.)

@@ -303,6 +303,16 @@ def calculate_angle_validation_scores(model, val_csv_path: str, image_dir: str, 
 # ---------------------------------------------------------------------------------------------------------------
 # Retrieval-based geopose (north-star stage; the reference has no retrieval — SURVEY fact 3, §8f-2): the same CSV + image
 # directory conventions as the validation scripts, with the gallery built from the training split.
+def _check_grid(extractor, image_size: int) -> None:
+    """The extractor's position grid is built for one image size (DinoV2Salad(arch, img_size)): refuse another one here, by
+    name, before any device work — not as a shape error inside the position-embedding add."""
+    bb = extractor.backbone
+    got = (int(image_size) // bb.patch) ** 2
+    if got != bb.num_patches:
+        raise ValueError(f"image_size={image_size} gives {got} patch tokens per image (patch {bb.patch}), but the extractor was built "
+                         f"for {bb.num_patches}: construct it with DinoV2Salad(arch, img_size={image_size})")
+
+
 @torch.no_grad()
 def build_gallery_from_images(extractor: DinoV2Salad, csv_path: str, image_dir: str, out_dir: str, *, fp8: bool = False,
                               batch_size: int = 64, device: str = "cuda", image_size: int = 224, graph: bool = True,
@@ -310,12 +320,14 @@ def build_gallery_from_images(extractor: DinoV2Salad, csv_path: str, image_dir: 
     """labels CSV (`filename,timestamp,latitude,longitude,angle,Region_ID`, cleaned_dataset_files/labels_train.csv:1) +
     images -> on-disk gallery (gallery.save_gallery: bf16 rows, or e4m3 rows + per-row scales with fp8=True).
     Preprocessing = the DINOv2+SALAD validation transform (dinov2salad_validation.py:18-22).  Returns the row count.
+    image_size: the size the extractor was built for (DinoV2Salad(arch, img_size=322) with image_size=322); ValueError otherwise.
     projection: None, a projection.DescriptorProjection, or an int d = fit PCA (whiten: with whitening) on this gallery's own
     descriptors (projection.fit_projection) — the rows are projected to d columns on the device (gallery.project_gallery)
     and the projection is saved with the gallery, where calculate_retrieval_scores finds it.
     keep_fine: an e4m3 or projected gallery also keeps the bf16 full descriptors (fine_descriptors.npy), the second tier of
     calculate_retrieval_scores(rerank=); a plain bf16 gallery's rows are those descriptors already, and nothing is added."""
     from . import gallery as G, ops
+    _check_grid(extractor, image_size)
     dev = torch.device(device)
     extractor = extractor.to(dev).to(torch.bfloat16).eval()
     df = _existing_rows(csv_path, image_dir)
@@ -399,6 +411,7 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
     with the batch's bf16 descriptors as fine queries (ShardedGallery.search_reranked); topk_scores are then fine scores."""
     from . import gallery as G
     from .retrieval import ShardedGallery
+    _check_grid(extractor, image_size)
     dev = torch.device(device)
     extractor = extractor.to(dev).to(torch.bfloat16).eval()
     has_fine = os.path.exists(os.path.join(gallery_dir, G.FINE_FILE))

@@ -82,7 +82,7 @@ class SaladAggregator(nn.Module):
     def token_stage(self, cls_rows: torch.Tensor, owner_raw_stream: int, n: int) -> None:
         """The token MLP of these cls rows (images of n patch tokens) on the current stream, into the workspace of
         `owner_raw_stream` (backbone.DinoV2.cls_tail_hook: the backbone's cls-row stream has the cls tokens ~0.3 ms before
-        the main stream has the patch tokens, so the stage costs the step nothing)."""
+        the main stream has the patch tokens, so the stage costs the step nothing).  n == 256 only (vpr_salad_stage_token)."""
         w = self._packed or self.pack()
         ops.salad_stage_token(cls_rows, w, n, owner_raw_stream)
 
@@ -95,6 +95,19 @@ class SaladAggregator(nn.Module):
         never applied here.  The training-mode descriptor (those Dropouts active, as under the fine-tuning script's
         model.train()) is forward_train."""
         first = tokens.patch if isinstance(tokens, SplitTokens) else tokens
+        n = first.shape[1] - (0 if isinstance(tokens, SplitTokens) else 1)
+        if n != 256:        # any other grid (include/vpr_amd_salad_anyres.h): both layouts addressed in place, no token_ready form
+            if isinstance(tokens, SplitTokens):
+                patch, cls = tokens.patch.contiguous(), tokens.cls.contiguous()
+            else:
+                patch, cls = tokens.contiguous(), None
+            if first.dtype == torch.float32:
+                w32 = self._packed_f32 or self.pack_f32()
+                desc, desc16 = _vpr.salad_aggregate_f32_n(patch, cls, torch_ops.weight_list(w32), w32.dustbin, 3)
+            else:
+                w = self._packed or self.pack()
+                desc, desc16 = _vpr.salad_aggregate_n(patch, cls, torch_ops.weight_list(w), w.dustbin, 3)
+            return (desc, desc16) if want_bf16 else desc
         if first.dtype == torch.float32:
             w32 = self._packed_f32 or self.pack_f32()
             if isinstance(tokens, SplitTokens):
@@ -142,11 +155,12 @@ class SaladAggregator(nn.Module):
 
 
 class DinoV2Salad(nn.Module):
-    """`feature_extractor`: images [B,3,224,224] -> L2-normalised descriptor [B, 8448]."""
+    """`feature_extractor`: images [B,3,img_size,img_size] -> L2-normalised descriptor [B, 8448].  img_size: any multiple of
+    the patch size whose grid has 65 .. 576 tokens (322 -> 23 x 23 = 529, the resolution DINOv2-SALAD is published at)."""
 
-    def __init__(self, arch: str = "vit_large"):
+    def __init__(self, arch: str = "vit_large", img_size: int = 224):
         super().__init__()
-        self.backbone = DinoV2(arch)
+        self.backbone = DinoV2(arch, img_size)
         self.aggregator = SaladAggregator(self.backbone.embed_dim)
 
     token_on_cls_stream = True      # SALAD's token MLP rides on the backbone's cls-row stream (bit-identical; A/B switch)
@@ -163,7 +177,9 @@ class DinoV2Salad(nn.Module):
         computed them in (SplitTokens on the HIP path), no re-layout copy before SALAD.
         events: a list -> a (start, end) pair of timing events around the aggregation on the current stream is appended
         (bench.py: the SALAD stage as the step runs it, token MLP on the backbone's cls-row stream)."""
-        self.backbone.cls_tail_hook = self.aggregator.token_stage if self.token_on_cls_stream else None
+        # the token stage on the cls-row stream exists for 256 tokens only; any other grid runs the token MLP in the aggregation
+        hook = self.token_on_cls_stream and self.backbone.num_patches == 256
+        self.backbone.cls_tail_hook = self.aggregator.token_stage if hook else None
         try:
             t = self.backbone(x, split=True)
         finally:

@@ -376,6 +376,53 @@ def salad_sinkhorn_aggregate(scores: torch.Tensor, feats: torch.Tensor, tokfeat:
     return out, out16
 
 
+# ---- any patch-token count 65 .. 576 (include/vpr_amd_salad_anyres.h); the functions above keep their n = 256 domain ----
+def salad_sinkhorn_aggregate_n(scores: torch.Tensor, feats: torch.Tensor, tokfeat: torch.Tensor,
+                               dustbin: float, iters: int = 3,
+                               want_bf16: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """salad_sinkhorn_aggregate for any n in 65 .. 576: scores [B,n,m] f32, feats [B,n,l] f32, tokfeat [B,t] f32 -> descriptor
+    (and its bf16 copy).  Always the run-time-n kernel, n = 256 included.  vpr_salad_sinkhorn_aggregate_n."""
+    _need(scores, torch.float32, "scores", 3)
+    _need(feats, torch.float32, "feats", 3)
+    _need(tokfeat, torch.float32, "tokfeat", 2)
+    B, n, m = scores.shape
+    l, t = feats.shape[2], tokfeat.shape[1]
+    if feats.shape[:2] != (B, n) or tokfeat.shape[0] != B:
+        raise RuntimeError("salad_sinkhorn_aggregate_n: inconsistent shapes")
+    out = torch.empty((B, t + l * m), dtype=torch.float32, device=scores.device)
+    out16 = torch.empty_like(out, dtype=torch.bfloat16) if want_bf16 else None
+    _call("vpr_salad_sinkhorn_aggregate_n", _ptr(scores), _ptr(feats), _ptr(tokfeat), B, n, m, l, t,
+          float(dustbin), int(iters), _ptr(out), _ptr(out16), _stream())
+    return out, out16
+
+
+def salad_aggregate_n(tokens, w: SaladWeights, iters: int = 3,
+                      want_bf16: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The aggregation for any patch-token count n in 65 .. 576: `tokens` = [B, 1+n, C] bf16 (cls first) or a (patch [B,n,C],
+    cls [B,C]) bf16 pair, addressed in place -> (descriptor f32 [B, t+l*m], bf16 copy or None).  n == 256 gives the bits of
+    salad_aggregate_split.  vpr_salad_aggregate_n."""
+    patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, Ct, device = _tokens(tokens, torch.bfloat16, "salad_aggregate_n")
+    (C, hidden, m, l, t), ws, out, out16 = _salad_setup(w, B, n, device, Ct, want_bf16)
+    cw = w.c_struct()
+    _call("vpr_salad_aggregate_n", patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, C,
+          ctypes.byref(cw), float(w.dustbin), m, l, t, hidden, int(iters),
+          _ptr(out), _ptr(out16), _ptr(ws), ws.numel(), _stream())
+    return out, out16
+
+
+def salad_aggregate_f32_n(tokens, w: SaladWeightsF32, iters: int = 3,
+                          want_bf16: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """salad_aggregate_f32 for any n in 65 .. 576 (f32 tokens, hub layout or pair; f32 weights); n == 256 gives its bits.
+    vpr_salad_aggregate_f32_n."""
+    patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, Ct, device = _tokens(tokens, torch.float32, "salad_aggregate_f32_n")
+    (C, hidden, m, l, t), ws, out, out16 = _salad_setup(w, B, n, device, Ct, want_bf16)
+    cw = w.c_struct()
+    _call("vpr_salad_aggregate_f32_n", patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, C,
+          ctypes.byref(cw), float(w.dustbin), m, l, t, hidden, int(iters),
+          _ptr(out), _ptr(out16), _ptr(ws), ws.numel(), _stream())
+    return out, out16
+
+
 def _need_rows(t: torch.Tensor, dtype: torch.dtype, name: str) -> None:
     """A 2-D GPU matrix whose rows may be padded (stride(1) == 1, any stride(0)): the leading dimension goes to C."""
     if not isinstance(t, torch.Tensor) or not t.is_cuda:

@@ -6,6 +6,7 @@ that seam, so the HIP hot path is visible to PyTorch's dispatcher like any other
 
     torch.ops.vpr.salad_aggregate / salad_aggregate_split / salad_aggregate_f32
     torch.ops.vpr.salad_aggregate_train                (training mode: Dropout active in the score / cluster MLPs)
+    torch.ops.vpr.salad_aggregate_n / salad_aggregate_f32_n   (any patch-token count 65 .. 576, e.g. 322 px images)
     torch.ops.vpr.knn_topk / knn_topk_fp8 / topk_merge
     torch.ops.vpr.retrieval_pose                       (geopose and first-hit ranks from the merged top-k)
     torch.ops.vpr.query_expand / query_expand_finish   (alpha-QE / DBA: weighted mean of a query and its best rows)
@@ -112,6 +113,38 @@ def salad_aggregate_train(tokens: Tensor, cls: Optional[Tensor], weights: List[T
 def _(tokens, cls, weights, dustbin, sinkhorn_iters, dropout_p, seed, pass_index, image_base):
     B, D = tokens.shape[0], _desc_width(weights)
     return tokens.new_empty((B, D), dtype=torch.float32), tokens.new_empty((B, D), dtype=torch.bfloat16)
+
+
+@torch.library.custom_op("vpr::salad_aggregate_n", mutates_args=())
+def salad_aggregate_n(patch: Tensor, cls: Optional[Tensor], weights: List[Tensor], dustbin: float,
+                      sinkhorn_iters: int) -> Tuple[Tensor, Tensor]:
+    """The aggregation for any patch-token count n in 65 .. 576 (include/vpr_amd_salad_anyres.h).  cls None: patch = tokens
+    [B, 1+n, C] bf16, cls first; else patch [B, n, C] bf16 and cls [B, C] bf16 — either layout is addressed in place.
+    n == 256: the bits of salad_aggregate_split.  vpr_salad_aggregate_n."""
+    out, out16 = ops.salad_aggregate_n(patch if cls is None else (patch, cls), _weights(weights, dustbin), sinkhorn_iters, True)
+    return out, out16
+
+
+@salad_aggregate_n.register_fake
+def _(patch, cls, weights, dustbin, sinkhorn_iters):
+    B, D = patch.shape[0], _desc_width(weights)
+    return patch.new_empty((B, D), dtype=torch.float32), patch.new_empty((B, D), dtype=torch.bfloat16)
+
+
+@torch.library.custom_op("vpr::salad_aggregate_f32_n", mutates_args=())
+def salad_aggregate_f32_n(patch: Tensor, cls: Optional[Tensor], weights: List[Tensor], dustbin: float,
+                          sinkhorn_iters: int) -> Tuple[Tensor, Tensor]:
+    """salad_aggregate_n at the reference's precision: f32 tokens (cls None: [B, 1+n, C], cls first; else the pair) and f32
+    weights.  n == 256: the bits of salad_aggregate_f32.  vpr_salad_aggregate_f32_n."""
+    out, out16 = ops.salad_aggregate_f32_n(patch if cls is None else (patch, cls), _weights(weights, dustbin, f32=True),
+                                           sinkhorn_iters, True)
+    return out, out16
+
+
+@salad_aggregate_f32_n.register_fake
+def _(patch, cls, weights, dustbin, sinkhorn_iters):
+    B, D = patch.shape[0], _desc_width(weights)
+    return patch.new_empty((B, D), dtype=torch.float32), patch.new_empty((B, D), dtype=torch.bfloat16)
 
 
 # -------------------------------------------------------------------------------------------------------------- kNN
@@ -314,4 +347,4 @@ def _(X, Y, order, batch_size, W1, b1, W2, b2, m, v, first_step, lr, beta1, beta
 
 OPS = ("head_train_epoch", "head_train_epoch_dropout", "salad_aggregate", "salad_aggregate_split", "salad_aggregate_f32", "salad_aggregate_train", "knn_topk", "knn_topk_fp8", "quantize_fp8_rows",
        "topk_merge", "pose_head", "ln_meanpool_head", "retrieval_pose", "query_expand", "query_expand_finish", "project_rows",
-       "rerank_rows")
+       "rerank_rows", "salad_aggregate_n", "salad_aggregate_f32_n")
