@@ -10,16 +10,18 @@ itself verified against PIL); the resampling arithmetic below is an independent 
 import numpy as np
 
 
-def resize_u8(img: np.ndarray, out: int, kx, xb, ky, yb) -> np.ndarray:
-    """img [H,W,3] u8 -> [out,out,3] u8 with Pillow's two-pass fixed-point arithmetic."""
+def resize_u8(img: np.ndarray, out, kx, xb, ky, yb) -> np.ndarray:
+    """img [H,W,3] u8 -> [OH,OW,3] u8 with Pillow's two-pass fixed-point arithmetic.
+    out: an int (square output) or (OH, OW); kx/xb are the tables of the width pass, ky/yb of the height pass."""
     H, W, _ = img.shape
-    tmp = np.zeros((H, out, 3), np.uint8)
-    for xx in range(out):
+    OH, OW = (out, out) if np.isscalar(out) else out
+    tmp = np.zeros((H, OW, 3), np.uint8)
+    for xx in range(OW):
         x0, c = xb[xx]
         acc = (img[:, x0:x0 + c, :].astype(np.int64) * kx[xx, :c][None, :, None]).sum(1) + (1 << 21)
         tmp[:, xx, :] = np.clip(acc >> 22, 0, 255)
-    o = np.zeros((out, out, 3), np.uint8)
-    for yy in range(out):
+    o = np.zeros((OH, OW, 3), np.uint8)
+    for yy in range(OH):
         y0, c = yb[yy]
         acc = (tmp[y0:y0 + c].astype(np.int64) * ky[yy, :c][:, None, None]).sum(0) + (1 << 21)
         o[yy] = np.clip(acc >> 22, 0, 255)

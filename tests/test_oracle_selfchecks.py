@@ -110,6 +110,21 @@ def test_resize_tables_and_oracle_match_pil():
             ky, yb, _ = resample_coeffs(H, 224, filt)
             ref = np.asarray(Image.fromarray(img).resize((224, 224), pf))
             assert np.array_equal(opre.resize_u8(img, 224, kx, xb, ky, yb), ref), (H, W, filt)
+    # the shapes and inputs of tests/test_preprocess_gpu.py (non-square outputs, up- and downscaling, binary images whose
+    # bicubic overshoot is clamped at both ends): the oracle with separate output height and width, on the same images
+    import preprocess_cases as pc
+    for (H, W), (OH, OW), clips in pc.SHAPES:
+        for filt in pc.FILTERS:
+            kx, xb, _ = resample_coeffs(W, OW, filt)
+            ky, yb, _ = resample_coeffs(H, OH, filt)
+            for kind in pc.KINDS:
+                ref = pc.pil_reference(H, W, OH, OW, kind, filt)
+                assert ref.shape == (pc.B, OH, OW, 3)
+                if clips and kind == "binary":
+                    pc.assert_reference_clips(ref, (H, W, OH, OW, filt))
+                for b in range(pc.B):
+                    got = opre.resize_u8(pc.images(H, W, kind)[b], (OH, OW), kx, xb, ky, yb)
+                    assert np.array_equal(got, ref[b]), (H, W, OH, OW, filt, kind, b)
     t = opre.to_tensor_normalize(np.array([[[0, 128, 255]]], dtype=np.uint8), (0.5, 0.5, 0.5), (0.5, 0.5, 0.5))
     assert t.shape == (3, 1, 1) and t[0, 0, 0] == -1.0 and t[2, 0, 0] == 1.0
 

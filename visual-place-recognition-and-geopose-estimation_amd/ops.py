@@ -1188,6 +1188,8 @@ def patchify_bf16(images: torch.Tensor, patch: int, kpad: int, lead_rows: int = 
     B, Cin, H, W = images.shape
     n = (H // patch) * (W // patch)
     out = torch.empty((B * (lead_rows + n), kpad), dtype=torch.bfloat16, device=images.device)
+    if B == 0:                               # no images: nothing to launch (an empty tensor has no data pointer)
+        return out
     _call("vpr_patchify_bf16", _ptr(images), B, Cin, H, W, int(patch), int(kpad), int(lead_rows), _ptr(out), _stream())
     return out
 

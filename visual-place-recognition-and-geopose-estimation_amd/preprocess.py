@@ -73,15 +73,16 @@ def resample_coeffs(in_size: int, out_size: int, filt: str) -> Tuple[np.ndarray,
 
 
 class ResizeNormalize:
-    """uint8 [B,H,W,3] on the GPU -> [B,3,out,out] (bf16 | f32), PIL-exact."""
+    """uint8 [B,H,W,3] on the GPU -> [B,3,OH,OW] (bf16 | f32), PIL-exact.  out_size: an int (square) or (OH, OW)."""
 
-    def __init__(self, out_size: int = 224, filt: str = "bilinear", mean: Sequence[float] = HALF_MEAN,
+    def __init__(self, out_size=224, filt: str = "bilinear", mean: Sequence[float] = HALF_MEAN,
                  std: Sequence[float] = HALF_STD, out_dtype: torch.dtype = torch.bfloat16):
         if filt not in _FILTERS:
             raise ValueError("filt must be 'bilinear' or 'bicubic'")
         if out_dtype not in (torch.bfloat16, torch.float32):
             raise ValueError("out_dtype must be bfloat16 or float32")
         self.out_size, self.filt, self.out_dtype = out_size, filt, out_dtype
+        self.out_h, self.out_w = (out_size, out_size) if isinstance(out_size, int) else (int(out_size[0]), int(out_size[1]))
         self._mean = (ctypes.c_float * 3)(*[float(m) for m in mean])
         self._std = (ctypes.c_float * 3)(*[float(s) for s in std])
         self._tables = {}
@@ -89,8 +90,8 @@ class ResizeNormalize:
     def _device_tables(self, H: int, W: int, device: torch.device):
         key = (H, W, str(device))
         if key not in self._tables:
-            kx, xb, ksx = resample_coeffs(W, self.out_size, self.filt)
-            ky, yb, ksy = resample_coeffs(H, self.out_size, self.filt)
+            kx, xb, ksx = resample_coeffs(W, self.out_w, self.filt)
+            ky, yb, ksy = resample_coeffs(H, self.out_h, self.filt)
             t = lambda a: torch.from_numpy(a.copy()).to(device)
             self._tables[key] = (t(kx), t(xb), ksx, t(ky), t(yb), ksy)
         return self._tables[key]
@@ -103,11 +104,11 @@ class ResizeNormalize:
             raise RuntimeError("images must be [B,H,W,3] RGB")
         dev = images_u8.device
         kx, xb, ksx, ky, yb, ksy = self._device_tables(H, W, dev)
-        O = self.out_size
-        out = torch.empty((B, 3, O, O), dtype=self.out_dtype, device=dev)
-        out_u8 = torch.empty((B, O, O, 3), dtype=torch.uint8, device=dev) if return_bytes else None
-        ws = workspace("preprocess", _lib.lib().vpr_preprocess_workspace_bytes(B, H, O), dev)
-        _call("vpr_preprocess_resize_normalize", _ptr(images_u8), B, H, W, O, O, _ptr(kx), _ptr(xb), ksx, _ptr(ky),
+        OH, OW = self.out_h, self.out_w
+        out = torch.empty((B, 3, OH, OW), dtype=self.out_dtype, device=dev)
+        out_u8 = torch.empty((B, OH, OW, 3), dtype=torch.uint8, device=dev) if return_bytes else None
+        ws = workspace("preprocess", _lib.lib().vpr_preprocess_workspace_bytes(B, H, OW), dev)
+        _call("vpr_preprocess_resize_normalize", _ptr(images_u8), B, H, W, OH, OW, _ptr(kx), _ptr(xb), ksx, _ptr(ky),
               _ptr(yb), ksy, self._mean, self._std, _ptr(out), int(self.out_dtype == torch.bfloat16), _ptr(out_u8),
               _ptr(ws), ws.numel(), _stream())
         return (out, out_u8) if return_bytes else out
