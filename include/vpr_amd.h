@@ -262,7 +262,16 @@ int vpr_knn_topk_fp8(const uint8_t* q, const float* q_scale, const uint8_t* gall
  *      with vpr_knn_topk_exhaustive.  `uncertified` (device int32, may be NULL) is incremented once per status-2
  *      query, so a pipeline can check one word at the end instead of synchronising per batch.
  * gallery_norm_bound: upper bound of the L2 norms of the (dequantised) gallery rows; the unchecked entry points
- * assume L2-normalised descriptors (1.002 bf16, 1.0625 e4m3).  status may be NULL. */
+ * assume L2-normalised descriptors (1.002 bf16, 1.0625 e4m3).  status may be NULL.
+ * e4m3 scales (q_scale, gallery_scale) must be finite and > 0: |q| takes the magnitude of the scale, but a negative
+ * scale turns an exact +0.0 score into -0.0, which the ordering key puts below +0.0 where oracle/knn.py's stable sort
+ * sees a tie; zero, negative, infinite or NaN scales are out of contract.
+ * vpr_knn_select_checked runs the tail on whatever score matrix the workspace holds (vpr_knn_scores_ptr), so its
+ * contract on that matrix is spelled out: every score S[b, n], n < N, is finite or -inf; NaN is out of contract;
+ * -0.0 counts as +0.0 (the level-0 select reads x + 0, and that is also what it writes back when it adds K-slice
+ * slabs); columns N .. ld-1 of a row are never looked at, whatever they hold.  A live -inf score is an ordinary
+ * candidate: it ranks behind every finite score and ahead of the padding.  The candidate lists of the select are
+ * bounded on the device: no score matrix, in or out of contract, makes the select write outside its list. */
 int vpr_knn_topk_checked(const uint16_t* q, const uint16_t* gallery, int B, int N, int D, int k,
                          int index_base, float* out_val, int32_t* out_idx, void* workspace, size_t workspace_bytes,
                          float gallery_norm_bound, int32_t* status, int32_t* uncertified, void* stream);

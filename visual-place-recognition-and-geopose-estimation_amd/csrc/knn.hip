@@ -330,18 +330,24 @@ __device__ __forceinline__ unsigned long long threshold_wave_lists(SelectState<C
 // max, kp - 1 published maxes lie above T and their groups add at most m keys each; the group whose max is T adds
 // that one key; every other group's keys are all below T.  So cnt <= m (kp - 1) + 1, and without a threshold
 // (fewer than kp live groups) cnt <= m (kp - 1).  Every caller says why its CAP covers that.
+// That argument needs kept() and the published maxes to follow ONE order; the slot test below does not: a key that
+// finds the list full is dropped (cnt keeps counting, select_rank reads min(cnt, CAP)), so a threshold that is wrong
+// for whatever reason costs an answer, never memory.
 template <int NSLOT, int CAP, int NOUT, typename P, typename K>
 __device__ __forceinline__ void select_filter(SelectState<CAP, NOUT>& sm, P&& kept, K&& key) {
 #pragma unroll
   for (int i = 0; i < NSLOT; ++i)
-    if (kept(i)) sm.cand[atomicAdd(&sm.cnt, 1)] = key(i);
+    if (kept(i)) {
+      const int slot = atomicAdd(&sm.cnt, 1);
+      if (slot < CAP) sm.cand[slot] = key(i);
+    }
 }
 
 // Step d.  outk[0, kp) is complete and visible to the whole block on return.
 template <int NT, int CAP, int NOUT>
 __device__ __forceinline__ void select_rank(SelectState<CAP, NOUT>& sm, int kp) {
   __syncthreads();
-  const int c = sm.cnt;
+  const int c = sm.cnt < CAP ? sm.cnt : CAP;      // select_filter never writes past CAP
   for (int ci = threadIdx.x; ci < c; ci += NT) {
     const unsigned long long mine = sm.cand[ci];
     int r = 0;
@@ -417,7 +423,7 @@ __device__ __forceinline__ float f4_at(const float4& v, int e) { return e == 0 ?
 // <= 8192).  The chunk is read ONCE: every thread requests its (up to) 8 float4 (32 scores, strided by 1024 so a wave
 // reads 1 KiB lines) before the first compare and keeps them in registers, as floats, for both passes over them:
 //   max     the thread's best (value, then lower index) of its 32 scores, plain f32 compares in index-ascending
-//           order (strict '>' keeps ties right);
+//           order (strict '>' keeps ties right); on scores with one zero (-0.0 read as +0.0) that is the key's order;
 //   filter  a key is built only for a score that reaches the threshold (32 u64 keys would double the registers).
 // The threshold is the wave-list form, the other steps are the shared ones.  m = 32 keys per published max, so the
 // list holds at most 32 (kp - 1) + 1 keys: CAP = 1024 for kp <= 32 (k <= 16), 4096 otherwise (kp <= 128).
@@ -444,17 +450,22 @@ __global__ __launch_bounds__(256) void knn_select_stream_kernel(
   }
   // K-split shards (small N): the score is the sum of the slices' slabs, added in slice order (deterministic); the sum
   // goes back into slab 0 so that the workspace still holds THE score matrix afterwards (vpr_knn_scores_ptr)
-  if (nslab > 1) {
-    for (int z = 1; z < nslab; ++z) {
+  for (int z = 1; z < nslab; ++z) {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int p = tid * 4 + i * 1024;
-        if (p < len) {
-          const float4 t = *reinterpret_cast<const float4*>(v + z * slab_stride + base + p);
-          q[i].x += t.x; q[i].y += t.y; q[i].z += t.z; q[i].w += t.w;
-        }
+    for (int i = 0; i < 8; ++i) {
+      const int p = tid * 4 + i * 1024;
+      if (p < len) {
+        const float4 t = *reinterpret_cast<const float4*>(v + z * slab_stride + base + p);
+        q[i].x += t.x; q[i].y += t.y; q[i].z += t.z; q[i].w += t.w;
       }
     }
+  }
+  // -0.0 counts as +0.0 (x + 0.f): the max pass and the filter below compare plain floats, where the two zeros are
+  // equal, while the packed key puts +0.0 above -0.0; with one zero both are the same order, which the list bound
+  // needs (a chunk of mixed zeros otherwise passes thousands of -0.0 under a (+0.0, index) threshold)
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { q[i].x += 0.f; q[i].y += 0.f; q[i].z += 0.f; q[i].w += 0.f; }
+  if (nslab > 1) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int p = tid * 4 + i * 1024;

@@ -531,7 +531,12 @@ def knn_topk(q: torch.Tensor, gallery: torch.Tensor, k: int, index_base: int = 0
     The kernels certify each query's answer as the exact top-k (include/vpr_amd.h, "Checked forms"):
     `status` (int32 [B]) receives 0 / 1 (certified) or 2 (not certified), `uncertified` (int32 [1]) counts the 2s
     without a host sync; `norm_bound` = upper bound of the gallery row norms.  exact_fallback=True reads the status
-    back (one sync) and re-runs the flagged queries exhaustively, so the result is exact unconditionally."""
+    back (one sync) and re-runs the flagged queries exhaustively, so the result is exact unconditionally — for rows of
+    at most 17408 bytes (D <= 8704 bf16, 17408 e4m3), the exhaustive kernel's limit.  Wider rows: if the checked search
+    flags a query, the call raises the exhaustive entry point's error (VPR_ERR_UNSUPPORTED) after the search has run;
+    a caller's `status` then still reads 2 for the flagged queries (never 3) and 0 / 1 for the others, whose rows a
+    call without exact_fallback returns exact; with no query flagged the call succeeds at any width.
+    e4m3 scales must be finite and > 0 (include/vpr_amd.h)."""
     _need(q, torch.bfloat16, "q", 2)
     _need(gallery, torch.bfloat16, "gallery", 2)
     if gallery.shape[1] != q.shape[1]:
