@@ -350,3 +350,33 @@ def test_retrieval_evaluation_at_322(dev, tmp_path):
     assert res["topk_indices"][:, 0].tolist() == src
     assert res["final_loss"] == pytest.approx(0.5 * (9.0 + 16.0)) and res["maae"] == pytest.approx(5.0)
     assert res["recall_at_1_tau"] == 1.0 and res["recall_at_1_region"] == 1.0
+
+
+def test_a_refused_call_launches_nothing(dev):
+    """Every refusal is decided before the first launch, so a refused call leaves workspace and outputs as they were.
+    (a) vpr_salad_aggregate_split with sinkhorn_iters = 0 -> INVALID_ARG; (b) vpr_salad_aggregate_n at n = 256 with
+    patch_img_stride = 256*C + 4 -> UNSUPPORTED.  Before the pre-check both came back with the same status but a modified
+    workspace: (a) was refused inside the stage-A launcher, after stages T and M had run; (b) by stage M, after stage T."""
+    import ctypes
+    from vpr_amd import _lib, ops
+    lib = _lib.lib()
+    B, n, C, hidden, m, l, t = 1, 256, 128, 512, 64, 128, 256
+    w = _to_dev(_weights(C, seed=5), dev, 1.0)
+    cw = w.c_struct()
+    g = torch.Generator().manual_seed(6)
+    patch = torch.randn(B, n * C + 4, generator=g).to(torch.bfloat16).to(dev)     # room for the stride of (b)
+    cls = torch.randn(B, C, generator=g).to(torch.bfloat16).to(dev)
+    need = lib.vpr_salad_workspace_bytes(B, n, C, m, l, t, hidden)
+    ws = torch.full((need,), 0xA5, dtype=torch.uint8, device=dev)
+    out = torch.full((B, t + l * m), 0xA5, dtype=torch.uint8, device=dev).repeat(1, 4)       # f32-sized
+    out16 = torch.full((B, t + l * m), 0xA5, dtype=torch.uint8, device=dev).repeat(1, 2)     # bf16-sized
+    p = lambda x: ctypes.c_void_p(x.data_ptr())
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    tail = (m, l, t, hidden)
+    st_a = lib.vpr_salad_aggregate_split(p(patch), p(cls), B, n, C, ctypes.byref(cw), 1.0, *tail, 0, p(out), p(out16), p(ws), need, stream)
+    st_b = lib.vpr_salad_aggregate_n(p(patch), n * C + 4, p(cls), C, B, n, C, ctypes.byref(cw), 1.0, *tail, 3, p(out), p(out16),
+                                     p(ws), need, stream)
+    torch.cuda.synchronize(dev)
+    assert (st_a, st_b) == (-1, -2)
+    for name, buf in (("workspace", ws), ("out_f32", out), ("out_bf16", out16)):
+        assert bool((buf == 0xA5).all()), f"{name} was written by a refused call"

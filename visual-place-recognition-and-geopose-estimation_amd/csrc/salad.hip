@@ -25,10 +25,7 @@
 
 namespace vpr {
 
-constexpr int SA_N = 256;   // patch tokens
-constexpr int SA_M = 64;    // clusters
-constexpr int SA_L = 128;   // cluster dim
-constexpr int SA_T = 256;   // token dim
+// SA_N / SA_M / SA_L / SA_T (patch tokens, clusters, cluster dim, token dim): vpr_internal.h
 constexpr int SA_LD = SA_N + 1;   // LDS row stride (words) of the [m+1][n] score matrix
 constexpr int SA_PLD = SA_N + 8;  // row stride (bf16) of the P planes: 528 B, 16-byte aligned rows, rows 4 banks apart
 // LDS: [score matrix 65 x 257 f32  |  later: two P planes 64 x 264 bf16]  then the small arrays (alpha / beta / norms)
@@ -421,7 +418,7 @@ int launch_sinkhorn_aggregate(const float* scores, const float* feats, const flo
                               float* out_f32, uint16_t* out_bf16, hipStream_t stream, int nslab, long long slab_rows,
                               int* counters) {
   if (!scores || !feats || !tokfeat || !out_f32 || B <= 0 || iters < 1) return VPR_ERR_INVALID_ARG;
-  if (n != SA_N || m != SA_M || l != SA_L || t != SA_T || nslab < 1 || nslab > 2) return VPR_ERR_UNSUPPORTED;
+  if (!salad_in_domain(SaladDomain::FixedN, n, m, l, t) || nslab < 1 || nslab > 2) return VPR_ERR_UNSUPPORTED;
   // Four workgroups per image (NQ = 4) — built in round 3 to put all 256 CUs on a 64-image batch, measured, and left OFF:
   // stage A 27.3 us against 20.8 us with one workgroup per image (scripts/salad_ab.py).  Every workgroup needs the whole
   // score matrix, so the batch reads 4 x 8.4 MB of scores + 16.8 MB of features = 50 MB at once and the front becomes
@@ -472,42 +469,72 @@ static int salad_slabs(int n, int C, int m, int l, int hidden) {
   return fused ? 2 : 1;
 }
 
+template <typename W>      // vpr_salad_weights / vpr_salad_weights_f32: the same ten member names
+static bool salad_weights_complete(const W* w) {
+  return w && w->w1_sc && w->b1_sc && w->w2_s && w->b2_s && w->w2_c && w->b2_c && w->w1_t && w->b1_t && w->w2_t && w->b2_t;
+}
+
+// A call: shape, weights and the operands of the stages it runs (null / 0 for the others); salad_args() fills ws and p.
 struct SaladArgs {
   int B, n, C, m, l, t, hidden;
   const vpr_salad_weights* w;
+  const uint16_t* cls; long long cls_stride;                      // stage T
+  const uint16_t* patch; long long patch_img_stride;              // stage M
+  int sinkhorn_iters; float* out_f32; uint16_t* out_bf16;         // stage A
+  bool train; const uint8_t* mask_out;                            // vpr_salad_aggregate_train: the fused route or nothing
   char* ws;
   SaladPlan p;
 };
-// anyres (include/vpr_amd_salad_anyres.h): m < n <= VPR_SALAD_MAX_N instead of n == 256; `misaligned`: what that call found
-// wrong with its pointers and strides, refused here so that its statuses come in the order of every other call.
-static int salad_args(SaladArgs* a, int B, int n, int C, int m, int l, int t, int hidden, const vpr_salad_weights* w,
-                      void* workspace, size_t workspace_bytes, bool need_w, bool anyres = false, bool misaligned = false) {
-  if (!workspace || B <= 0 || n < 1 || C <= 0) return VPR_ERR_INVALID_ARG;
-  if (need_w) {
-    if (!w) return VPR_ERR_INVALID_ARG;
-    if (!w->w1_sc || !w->b1_sc || !w->w2_s || !w->b2_s || !w->w2_c || !w->b2_c || !w->w1_t || !w->b1_t || !w->w2_t || !w->b2_t)
-      return VPR_ERR_INVALID_ARG;
-  }
-  if (m != SA_M || l != SA_L || t != SA_T || (C % 64) || (hidden % 64)) return VPR_ERR_UNSUPPORTED;
-  if (anyres ? (n <= SA_M || n > VPR_SALAD_MAX_N || misaligned) : n != SA_N) return VPR_ERR_UNSUPPORTED;
-  if (!salad_plan(B, n, C, m, l, t, hidden, &a->p)) return VPR_ERR_INVALID_ARG;
-  if (workspace_bytes < a->p.total) return VPR_ERR_WORKSPACE;
-  a->B = B; a->n = n; a->C = C; a->m = m; a->l = l; a->t = t; a->hidden = hidden; a->w = w;
+enum : unsigned { STAGE_T = 1, STAGE_M = 2, STAGE_A = 4, STAGE_ALL = 7 };
+
+// What the launchers of `stages` read as 16-byte chunks (the outputs of the run-time-n kernel: as elements), and the strides.
+static bool salad_misaligned(const SaladArgs& a, unsigned stages) {
+  const vpr_salad_weights* w = a.w;
+  const bool run_time_n = (stages & STAGE_A) && a.n != SA_N;
+  return (((stages & (STAGE_T | STAGE_M)) || run_time_n) && !aligned16(a.ws)) ||
+         ((stages & STAGE_T) && ((a.cls_stride % 8) || a.cls_stride > 0x7fffffffLL || a.cls_stride < 0 || !aligned16(a.cls) ||
+                                 !aligned16(w->w1_t) || !aligned16(w->w2_t))) ||
+         ((stages & STAGE_M) && ((a.patch_img_stride % 8) || !aligned16(a.patch) || !aligned16(w->w1_sc) || !aligned16(w->w2_s) ||
+                                 !aligned16(w->w2_c) || !aligned4(a.mask_out))) ||
+         (run_time_n && (!aligned4(a.out_f32) || (reinterpret_cast<uintptr_t>(a.out_bf16) & 1)));
+}
+
+// The one pre-check of a call that runs `stages`: every refusal a stage or a launcher below could make, decided here, so
+// that a refused call has launched nothing.  The order is the ABI's: INVALID_ARG (sizes, weights), UNSUPPORTED (domain),
+// WORKSPACE, then the operands of the stages.  The any-n entries report sinkhorn_iters < 1 ahead of everything and, where
+// they leave the n = 256 chain, a misaligned operand ahead of WORKSPACE (include/vpr_amd_salad_anyres.h).
+static int salad_args(SaladArgs* a, SaladDomain domain, unsigned stages, void* workspace, size_t workspace_bytes) {
+  const bool iters_bad = (stages & STAGE_A) && a->sinkhorn_iters < 1;
+  if (domain == SaladDomain::AnyN && iters_bad) return VPR_ERR_INVALID_ARG;
+  if (!workspace || a->B <= 0 || a->n < 1 || a->C <= 0) return VPR_ERR_INVALID_ARG;
+  if ((stages & (STAGE_T | STAGE_M)) && !salad_weights_complete(a->w)) return VPR_ERR_INVALID_ARG;
+  if (!salad_in_domain(domain, a->n, a->m, a->l, a->t, a->C, a->hidden)) return VPR_ERR_UNSUPPORTED;
   a->ws = static_cast<char*>(workspace);
-  return VPR_OK;
+  if (a->n != SA_N && salad_misaligned(*a, stages)) return VPR_ERR_UNSUPPORTED;
+  if (!salad_plan(a->B, a->n, a->C, a->m, a->l, a->t, a->hidden, &a->p)) return VPR_ERR_INVALID_ARG;
+  if (workspace_bytes < a->p.total) return VPR_ERR_WORKSPACE;
+  if (((stages & STAGE_T) && !a->cls) || ((stages & STAGE_M) && !a->patch) || ((stages & STAGE_A) && !a->out_f32))
+    return VPR_ERR_INVALID_ARG;
+  if (salad_misaligned(*a, stages)) return VPR_ERR_UNSUPPORTED;
+  if ((stages & STAGE_T) && a->cls_stride < a->C) return VPR_ERR_UNSUPPORTED;           // cls rows that overlap
+  const bool fused = salad_slabs(a->n, a->C, a->m, a->l, a->hidden) == 2;
+  // the fused kernel reads its biases as float4 and the optional fragments as 16-byte chunks
+  if ((stages & STAGE_M) && fused && !(aligned16(a->w->b1_sc) && aligned16(a->w->b2_s) && aligned16(a->w->b2_c) &&
+                                       aligned16(a->w->w2_s_frag) && aligned16(a->w->w2_c_frag)))
+    return VPR_ERR_UNSUPPORTED;
+  if (a->train && !fused) return VPR_ERR_UNSUPPORTED;                                   // no dropout mask on the unfused route
+  return iters_bad ? VPR_ERR_INVALID_ARG : VPR_OK;
 }
 
 // Stage T: token MLP on the B cls rows -> g [B, t] f32 in the workspace.  Independent of stage M (other inputs, other
 // workspace regions): a caller with two streams runs it beside the big GEMM (ops.salad_aggregate_split does).
-static int salad_stage_token(const SaladArgs& a, const uint16_t* cls, long long cls_stride, hipStream_t stream) {
-  if (!cls) return VPR_ERR_INVALID_ARG;
-  if ((cls_stride % 8) || cls_stride > 0x7fffffffLL) return VPR_ERR_UNSUPPORTED;
+static int salad_stage_token(const SaladArgs& a, hipStream_t stream) {
   uint16_t* Ht = reinterpret_cast<uint16_t*>(a.ws + a.p.off_Ht);
   float* g = reinterpret_cast<float*>(a.ws + a.p.off_g);
   const vpr_salad_weights* w = a.w;
-  int st = launch_skinny_linear(cls, (int)cls_stride, w->w1_t, a.C, w->b1_t, 0, 3, Ht, a.hidden, a.B, a.hidden, a.C, nullptr, nullptr, stream);
+  int st = launch_skinny_linear(a.cls, (int)a.cls_stride, w->w1_t, a.C, w->b1_t, 0, 3, Ht, a.hidden, a.B, a.hidden, a.C, nullptr, nullptr, stream);
   if (st == VPR_ERR_UNSUPPORTED) {
-    const GemmProblem l1{cls, (int)cls_stride, 0, 0, w->w1_t, a.C, w->b1_t, 1, Ht, a.hidden, 1, a.B, a.hidden, a.C, 0, 0};
+    const GemmProblem l1{a.cls, (int)a.cls_stride, 0, 0, w->w1_t, a.C, w->b1_t, 1, Ht, a.hidden, 1, a.B, a.hidden, a.C, 0, 0};
     st = launch_gemm_nt_group(&l1, 1, stream);
   }
   if (st != VPR_OK) return st;
@@ -520,24 +547,21 @@ static int salad_stage_token(const SaladArgs& a, const uint16_t* cls, long long 
 }
 
 // Stage M: score + cluster MLPs on the B*n patch rows -> S, F (salad_slabs() partial-sum slabs) in the workspace.
-// patch row r of image b at patch + b*patch_img_stride + r*C (addressed in place).
+// patch row r of image b at a.patch + b*a.patch_img_stride + r*C (addressed in place).
 // drop (may be null): dropout on the hidden layer — the fused route only (VPR_ERR_UNSUPPORTED on the unfused one).
-static int salad_stage_mlps(const SaladArgs& a, const uint16_t* patch, long long patch_img_stride, hipStream_t stream,
-                            const Fuse2Drop* drop = nullptr) {
-  if (!patch) return VPR_ERR_INVALID_ARG;
-  if (patch_img_stride % 8) return VPR_ERR_UNSUPPORTED;
+static int salad_stage_mlps(const SaladArgs& a, hipStream_t stream, const Fuse2Drop* drop = nullptr) {
   uint16_t* H = reinterpret_cast<uint16_t*>(a.ws + a.p.off_H);
   float* S = reinterpret_cast<float*>(a.ws + a.p.off_S);
   float* F = reinterpret_cast<float*>(a.ws + a.p.off_F);
   const vpr_salad_weights* w = a.w;
   const int rows = a.B * a.n, hidden = a.hidden;
   if (salad_slabs(a.n, a.C, a.m, a.l, hidden) == 2)
-    return launch_salad_mlps_fused(patch, a.C, a.n, patch_img_stride, w->w1_sc, w->b1_sc, w->w2_s, w->b2_s, w->w2_c, w->b2_c,
+    return launch_salad_mlps_fused(a.patch, a.C, a.n, a.patch_img_stride, w->w1_sc, w->b1_sc, w->w2_s, w->b2_s, w->w2_c, w->b2_c,
                                    S, F, rows, a.C, hidden, a.m, a.l, stream, w->w2_s_frag, w->w2_c_frag, drop);
   if (drop != nullptr) return VPR_ERR_UNSUPPORTED;
   // unfused: layer 1 on the 256 x 256-tile kernel (34 of SALAD's 38 GFLOP; B tiles x 4 = one full wave of workgroups at
   // B = 64), hidden activations through HBM as bf16, the two second layers as one grouped launch
-  const GemmProblem l1_sc{patch, a.C, a.n, patch_img_stride, w->w1_sc, a.C, w->b1_sc, 1, H, 2 * hidden, 1, rows, 2 * hidden, a.C, 0, 0};
+  const GemmProblem l1_sc{a.patch, a.C, a.n, a.patch_img_stride, w->w1_sc, a.C, w->b1_sc, 1, H, 2 * hidden, 1, rows, 2 * hidden, a.C, 0, 0};
   int st = launch_gemm256(l1_sc, stream);
   if (st == VPR_ERR_UNSUPPORTED) st = launch_gemm_nt_group(&l1_sc, 1, stream);
   if (st != VPR_OK) return st;
@@ -547,16 +571,23 @@ static int salad_stage_mlps(const SaladArgs& a, const uint16_t* patch, long long
   return launch_gemm_nt_group(l2, 2, stream);
 }
 
+// The one choice of the stage-A kernel: the n = 256 kernel on `nslab` partial-sum slabs `slab_rows` rows apart (with the arrival
+// counters, where the caller has them), the run-time-n kernel for any other n: one dense slab, as salad_slabs() says off 256.
+static int salad_launch_aggregate(const float* S, const float* F, const float* g, int B, int n, int m, int l, int t, float dustbin,
+                                  int iters, float* out_f32, uint16_t* out_bf16, hipStream_t stream, int nslab, long long slab_rows,
+                                  int* counters) {
+  if (n != SA_N) return launch_sinkhorn_aggregate_n(S, F, g, B, n, m, l, t, dustbin, iters, out_f32, out_bf16, stream);
+  return launch_sinkhorn_aggregate(S, F, g, B, n, m, l, t, dustbin, iters, out_f32, out_bf16, stream, nslab, slab_rows, counters);
+}
+
 // Stage A: Sinkhorn + aggregation + normalisations on what stages T and M left in the workspace.
-static int salad_stage_aggregate(const SaladArgs& a, float dustbin, int sinkhorn_iters, float* out_f32, uint16_t* out_bf16,
-                                 hipStream_t stream) {
-  if (!out_f32) return VPR_ERR_INVALID_ARG;
+static int salad_stage_aggregate(const SaladArgs& a, float dustbin, hipStream_t stream) {
   const float* S = reinterpret_cast<const float*>(a.ws + a.p.off_S);
   const float* F = reinterpret_cast<const float*>(a.ws + a.p.off_F);
   const float* g = reinterpret_cast<const float*>(a.ws + a.p.off_g);
   int* counters = (size_t)a.B * sizeof(int) <= SALAD_COUNTER_BYTES ? reinterpret_cast<int*>(a.ws + a.p.off_cnt) : nullptr;
-  return launch_sinkhorn_aggregate(S, F, g, a.B, a.n, a.m, a.l, a.t, dustbin, sinkhorn_iters, out_f32, out_bf16, stream,
-                                   salad_slabs(a.n, a.C, a.m, a.l, a.hidden), (long long)a.B * a.n, counters);
+  return salad_launch_aggregate(S, F, g, a.B, a.n, a.m, a.l, a.t, dustbin, a.sinkhorn_iters, a.out_f32, a.out_bf16, stream,
+                                salad_slabs(a.n, a.C, a.m, a.l, a.hidden), (long long)a.B * a.n, counters);
 }
 
 }  // namespace vpr
@@ -586,25 +617,27 @@ extern "C" int vpr_salad_sinkhorn_set_clocks(long long* clocks) {
 extern "C" int vpr_salad_stage_token(const uint16_t* cls_tokens, long long cls_stride, int B, int n, int C,
                                      const vpr_salad_weights* w, int m, int l, int t, int hidden,
                                      void* workspace, size_t workspace_bytes, void* stream) {
-  SaladArgs a;
-  VPR_TRY_LAUNCH(salad_args(&a, B, n, C, m, l, t, hidden, w, workspace, workspace_bytes, true));
-  return salad_stage_token(a, cls_tokens, cls_stride, static_cast<hipStream_t>(stream));
+  SaladArgs a{B, n, C, m, l, t, hidden, w, cls_tokens, cls_stride};
+  VPR_TRY_LAUNCH(salad_args(&a, SaladDomain::FixedN, STAGE_T, workspace, workspace_bytes));
+  return salad_stage_token(a, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int vpr_salad_stage_mlps(const uint16_t* patch_tokens, long long patch_img_stride, int B, int n, int C,
                                     const vpr_salad_weights* w, int m, int l, int t, int hidden,
                                     void* workspace, size_t workspace_bytes, void* stream) {
-  SaladArgs a;
-  VPR_TRY_LAUNCH(salad_args(&a, B, n, C, m, l, t, hidden, w, workspace, workspace_bytes, true));
-  return salad_stage_mlps(a, patch_tokens, patch_img_stride, static_cast<hipStream_t>(stream));
+  SaladArgs a{B, n, C, m, l, t, hidden, w};
+  a.patch = patch_tokens, a.patch_img_stride = patch_img_stride;
+  VPR_TRY_LAUNCH(salad_args(&a, SaladDomain::FixedN, STAGE_M, workspace, workspace_bytes));
+  return salad_stage_mlps(a, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int vpr_salad_stage_aggregate(int B, int n, int C, float dustbin, int m, int l, int t, int hidden,
                                          int sinkhorn_iters, float* out_f32, uint16_t* out_bf16,
                                          void* workspace, size_t workspace_bytes, void* stream) {
-  SaladArgs a;
-  VPR_TRY_LAUNCH(salad_args(&a, B, n, C, m, l, t, hidden, nullptr, workspace, workspace_bytes, false));
-  return salad_stage_aggregate(a, dustbin, sinkhorn_iters, out_f32, out_bf16, static_cast<hipStream_t>(stream));
+  SaladArgs a{B, n, C, m, l, t, hidden};
+  a.sinkhorn_iters = sinkhorn_iters, a.out_f32 = out_f32, a.out_bf16 = out_bf16;
+  VPR_TRY_LAUNCH(salad_args(&a, SaladDomain::FixedN, STAGE_A, workspace, workspace_bytes));
+  return salad_stage_aggregate(a, dustbin, static_cast<hipStream_t>(stream));
 }
 
 // include/vpr_amd_salad_stages.h: where stages T and M leave g, S, F (and, unfused, H) — the plan and the slab rule the
@@ -613,8 +646,8 @@ extern "C" int vpr_salad_stage_outputs(void* workspace, size_t workspace_bytes, 
                                        int hidden, float** S, float** F, float** g, uint16_t** H, int* slabs,
                                        long long* slab_rows) {
   if (!S || !F || !g || !slabs || !slab_rows) return VPR_ERR_INVALID_ARG;
-  SaladArgs a;
-  VPR_TRY_LAUNCH(salad_args(&a, B, n, C, m, l, t, hidden, nullptr, workspace, workspace_bytes, false));
+  SaladArgs a{B, n, C, m, l, t, hidden};
+  VPR_TRY_LAUNCH(salad_args(&a, SaladDomain::FixedN, 0, workspace, workspace_bytes));
   *S = reinterpret_cast<float*>(a.ws + a.p.off_S);
   *F = reinterpret_cast<float*>(a.ws + a.p.off_F);
   *g = reinterpret_cast<float*>(a.ws + a.p.off_g);
@@ -624,19 +657,18 @@ extern "C" int vpr_salad_stage_outputs(void* workspace, size_t workspace_bytes, 
   return VPR_OK;
 }
 
-// patch row r of image b at patch + b*patch_img_stride + r*C; cls token of image b at cls + b*cls_stride
-static int salad_run(const uint16_t* patch, long long patch_img_stride, const uint16_t* cls, long long cls_stride,
-                     int B, int n, int C, const vpr_salad_weights* w, float dustbin,
-                     int m, int l, int t, int hidden, int sinkhorn_iters,
-                     float* out_f32, uint16_t* out_bf16,
-                     void* workspace, size_t workspace_bytes, void* stream_) {
+// The whole aggregation in one stream.  patch row r of image b at patch + b*patch_img_stride + r*C; cls token of image b at
+// cls + b*cls_stride.  A whole call names a null operand ahead of its shape (a stage call: after the workspace size).
+static int salad_run(SaladDomain domain, const uint16_t* patch, long long patch_img_stride, const uint16_t* cls, long long cls_stride,
+                     int B, int n, int C, const vpr_salad_weights* w, float dustbin, int m, int l, int t, int hidden,
+                     int sinkhorn_iters, float* out_f32, uint16_t* out_bf16, void* workspace, size_t workspace_bytes, void* stream_) {
   if (!patch || !cls || !out_f32) return VPR_ERR_INVALID_ARG;
-  SaladArgs a;
-  VPR_TRY_LAUNCH(salad_args(&a, B, n, C, m, l, t, hidden, w, workspace, workspace_bytes, true));
+  SaladArgs a{B, n, C, m, l, t, hidden, w, cls, cls_stride, patch, patch_img_stride, sinkhorn_iters, out_f32, out_bf16};
+  VPR_TRY_LAUNCH(salad_args(&a, domain, STAGE_ALL, workspace, workspace_bytes));
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  VPR_TRY_LAUNCH(salad_stage_token(a, cls, cls_stride, stream));
-  VPR_TRY_LAUNCH(salad_stage_mlps(a, patch, patch_img_stride, stream));
-  return salad_stage_aggregate(a, dustbin, sinkhorn_iters, out_f32, out_bf16, stream);
+  VPR_TRY_LAUNCH(salad_stage_token(a, stream));
+  VPR_TRY_LAUNCH(salad_stage_mlps(a, stream));
+  return salad_stage_aggregate(a, dustbin, stream);
 }
 
 extern "C" int vpr_salad_aggregate(const uint16_t* tokens, int B, int tokens_per_image, int C,
@@ -646,8 +678,8 @@ extern "C" int vpr_salad_aggregate(const uint16_t* tokens, int B, int tokens_per
                                    void* workspace, size_t workspace_bytes, void* stream) {
   if (!tokens || tokens_per_image < 2 || C <= 0) return VPR_ERR_INVALID_ARG;
   const long long img_stride = (long long)tokens_per_image * C;
-  return salad_run(tokens + C, img_stride, tokens, img_stride, B, tokens_per_image - 1, C, w, dustbin, m, l, t, hidden,
-                   sinkhorn_iters, out_f32, out_bf16, workspace, workspace_bytes, stream);
+  return salad_run(SaladDomain::FixedN, tokens + C, img_stride, tokens, img_stride, B, tokens_per_image - 1, C, w, dustbin, m, l, t,
+                   hidden, sinkhorn_iters, out_f32, out_bf16, workspace, workspace_bytes, stream);
 }
 
 extern "C" int vpr_salad_aggregate_split(const uint16_t* patch_tokens, const uint16_t* cls_tokens, int B,
@@ -657,40 +689,23 @@ extern "C" int vpr_salad_aggregate_split(const uint16_t* patch_tokens, const uin
                                          float* out_f32, uint16_t* out_bf16,
                                          void* workspace, size_t workspace_bytes, void* stream) {
   if (patches_per_image < 1 || C <= 0) return VPR_ERR_INVALID_ARG;
-  return salad_run(patch_tokens, (long long)patches_per_image * C, cls_tokens, C, B, patches_per_image, C, w, dustbin,
-                   m, l, t, hidden, sinkhorn_iters, out_f32, out_bf16, workspace, workspace_bytes, stream);
+  return salad_run(SaladDomain::FixedN, patch_tokens, (long long)patches_per_image * C, cls_tokens, C, B, patches_per_image, C, w,
+                   dustbin, m, l, t, hidden, sinkhorn_iters, out_f32, out_bf16, workspace, workspace_bytes, stream);
 }
 
-// include/vpr_amd_salad_anyres.h: n == 256 is salad_run (the same bits as vpr_salad_aggregate_split); any other n runs stage
-// T, the unfused stage M (salad_slabs() is 1 off n == 256) and the run-time-n stage A.  Everything a stage could refuse is
-// checked here first, so a refused call has launched nothing.
+// include/vpr_amd_salad_anyres.h: the same run in the any-n domain.  n == 256 takes the stages of vpr_salad_aggregate_split
+// (the same bits); any other n the unfused stage M (salad_slabs() is 1 off n == 256) and the run-time-n stage A.
 extern "C" int vpr_salad_aggregate_n(const uint16_t* patch, long long patch_img_stride, const uint16_t* cls, long long cls_stride,
                                      int B, int n, int C, const vpr_salad_weights* w, float dustbin,
                                      int m, int l, int t, int hidden, int sinkhorn_iters,
                                      float* out_f32, uint16_t* out_bf16,
-                                     void* workspace, size_t workspace_bytes, void* stream_) {
-  if (!patch || !cls || !out_f32 || sinkhorn_iters < 1) return VPR_ERR_INVALID_ARG;
-  if (n == SA_N)
-    return salad_run(patch, patch_img_stride, cls, cls_stride, B, n, C, w, dustbin, m, l, t, hidden, sinkhorn_iters, out_f32,
-                     out_bf16, workspace, workspace_bytes, stream_);
-  bool misaligned = (patch_img_stride % 8) || (cls_stride % 8) || cls_stride > 0x7fffffffLL || cls_stride < 0 ||
-                    !aligned16(patch) || !aligned16(cls) || !aligned16(workspace) || !aligned4(out_f32) ||
-                    (reinterpret_cast<uintptr_t>(out_bf16) & 1);
-  if (w) misaligned = misaligned || !aligned16(w->w1_sc) || !aligned16(w->w2_s) || !aligned16(w->w2_c) || !aligned16(w->w1_t) ||
-                      !aligned16(w->w2_t);
-  SaladArgs a;
-  VPR_TRY_LAUNCH(salad_args(&a, B, n, C, m, l, t, hidden, w, workspace, workspace_bytes, true, true, misaligned));
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  VPR_TRY_LAUNCH(salad_stage_token(a, cls, cls_stride, stream));
-  VPR_TRY_LAUNCH(salad_stage_mlps(a, patch, patch_img_stride, stream));
-  return launch_sinkhorn_aggregate_n(reinterpret_cast<const float*>(a.ws + a.p.off_S), reinterpret_cast<const float*>(a.ws + a.p.off_F),
-                                     reinterpret_cast<const float*>(a.ws + a.p.off_g), B, n, m, l, t, dustbin, sinkhorn_iters,
-                                     out_f32, out_bf16, stream);
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  return salad_run(SaladDomain::AnyN, patch, patch_img_stride, cls, cls_stride, B, n, C, w, dustbin, m, l, t, hidden, sinkhorn_iters,
+                   out_f32, out_bf16, workspace, workspace_bytes, stream);
 }
 
 // Train mode (include/vpr_amd.h, vpr_salad_aggregate_train): the hub model's Dropout layers of score / cluster_features
-// active.  Stage M runs first — it is the stage that may refuse (dropout exists on the fused route only), so a refused call
-// has launched nothing; stages T and A are those of the eval form.
+// active — on the fused route only, which salad_args() insists on; stages T and A are those of the eval form.
 extern "C" int vpr_salad_aggregate_train(const uint16_t* patch, long long patch_img_stride, const uint16_t* cls,
                                          long long cls_stride, int B, int n, int C, const vpr_salad_weights* w, float dustbin,
                                          int m, int l, int t, int hidden, int sinkhorn_iters, double dropout_p, uint64_t seed,
@@ -699,23 +714,16 @@ extern "C" int vpr_salad_aggregate_train(const uint16_t* patch, long long patch_
   if (!(dropout_p >= 0.0 && dropout_p < 1.0)) return VPR_ERR_INVALID_ARG;          // NaN fails both comparisons
   if (image_base < 0 || B <= 0 || image_base + B > (1LL << 32)) return VPR_ERR_INVALID_ARG;
   if (!patch || !cls || !out_f32) return VPR_ERR_INVALID_ARG;
-  SaladArgs a;
-  VPR_TRY_LAUNCH(salad_args(&a, B, n, C, m, l, t, hidden, w, workspace, workspace_bytes, true));
-  if (salad_slabs(n, C, m, l, hidden) != 2) return VPR_ERR_UNSUPPORTED;           // no mask on the unfused route
-  if ((cls_stride % 8) || cls_stride > 0x7fffffffLL) return VPR_ERR_UNSUPPORTED;  // stage T's own refusal, checked up front
+  SaladArgs a{B, n, C, m, l, t, hidden, w, cls, cls_stride, patch, patch_img_stride, sinkhorn_iters, out_f32, out_bf16};
+  a.train = true, a.mask_out = mask_out;
+  VPR_TRY_LAUNCH(salad_args(&a, SaladDomain::FixedN, STAGE_ALL, workspace, workspace_bytes));
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  Fuse2Drop d;
-  d.t = (uint32_t)floor(dropout_p * 4294967296.0);   // p * 2^32 < 2^32: fits
-  d.s = (float)(1.0 / (1.0 - dropout_p));
-  d.k0 = (uint32_t)(seed & 0xffffffffu);
-  d.k1 = (uint32_t)(seed >> 32);
-  d.pass = pass;
-  d.image_base = (uint32_t)image_base;
-  d.mask_out = mask_out;
+  const Fuse2Drop d{(uint32_t)floor(dropout_p * 4294967296.0) /* p * 2^32 < 2^32: fits */, (uint32_t)(seed & 0xffffffffu),
+                    (uint32_t)(seed >> 32), pass, (uint32_t)image_base, (float)(1.0 / (1.0 - dropout_p)), mask_out};
   const bool drop = dropout_p > 0.0 || mask_out != nullptr;      // p = 0 without a mask: the eval kernel (the same bits)
-  VPR_TRY_LAUNCH(salad_stage_mlps(a, patch, patch_img_stride, stream, drop ? &d : nullptr));
-  VPR_TRY_LAUNCH(salad_stage_token(a, cls, cls_stride, stream));
-  return salad_stage_aggregate(a, dustbin, sinkhorn_iters, out_f32, out_bf16, stream);
+  VPR_TRY_LAUNCH(salad_stage_mlps(a, stream, drop ? &d : nullptr));
+  VPR_TRY_LAUNCH(salad_stage_token(a, stream));
+  return salad_stage_aggregate(a, dustbin, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -806,26 +814,24 @@ extern "C" size_t vpr_salad_f32_workspace_bytes(int B, int n, int C, int m, int 
   return salad_f32_plan(B, n, C, m, l, t, hidden, &p) ? p.total : 0;
 }
 
-// anyres (vpr_salad_aggregate_f32_n): m < n <= VPR_SALAD_MAX_N, stage A by the run-time-n kernel off n == 256
-static int salad_f32_run(const float* patch, long long patch_img_stride, const float* cls, long long cls_stride,
-                         int B, int n, int C, const vpr_salad_weights_f32* w, float dustbin,
-                         int m, int l, int t, int hidden, int sinkhorn_iters,
-                         float* out_f32, uint16_t* out_bf16,
-                         void* workspace, size_t workspace_bytes, void* stream_, bool anyres) {
-  if (anyres && sinkhorn_iters < 1) return VPR_ERR_INVALID_ARG;
-  if (!patch || !cls || !w || !out_f32 || !workspace || B <= 0 || n < 1 || C <= 0) return VPR_ERR_INVALID_ARG;
-  if (!w->w1_sc || !w->b1_sc || !w->w2_s || !w->b2_s || !w->w2_c || !w->b2_c || !w->w1_t || !w->b1_t || !w->w2_t || !w->b2_t)
-    return VPR_ERR_INVALID_ARG;
-  if (m != SA_M || l != SA_L || t != SA_T || (C % 64) || (hidden % 64)) return VPR_ERR_UNSUPPORTED;
-  if (anyres ? (n <= SA_M || n > VPR_SALAD_MAX_N) : n != SA_N) return VPR_ERR_UNSUPPORTED;
+// Every refusal comes before the first launch, in the order of salad_args(); the f32 forms always put alignment ahead of
+// WORKSPACE.  Stage A is salad_launch_aggregate()'s choice: one dense slab, no counters.
+static int salad_f32_run(SaladDomain domain, const float* patch, long long patch_img_stride, const float* cls, long long cls_stride,
+                         int B, int n, int C, const vpr_salad_weights_f32* w, float dustbin, int m, int l, int t, int hidden,
+                         int sinkhorn_iters, float* out_f32, uint16_t* out_bf16, void* workspace, size_t workspace_bytes, void* stream_) {
+  if (domain == SaladDomain::AnyN && sinkhorn_iters < 1) return VPR_ERR_INVALID_ARG;
+  if (!patch || !cls || !out_f32 || !workspace || B <= 0 || n < 1 || C <= 0) return VPR_ERR_INVALID_ARG;
+  if (!salad_weights_complete(w)) return VPR_ERR_INVALID_ARG;
+  if (!salad_in_domain(domain, n, m, l, t, C, hidden)) return VPR_ERR_UNSUPPORTED;
   if ((patch_img_stride % 4) || (cls_stride % 4) || patch_img_stride < (long long)n * C || cls_stride < C) return VPR_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(patch) | reinterpret_cast<uintptr_t>(cls) | reinterpret_cast<uintptr_t>(w->w1_sc) |
-       reinterpret_cast<uintptr_t>(w->w2_s) | reinterpret_cast<uintptr_t>(w->w2_c) | reinterpret_cast<uintptr_t>(w->w1_t) |
-       reinterpret_cast<uintptr_t>(w->w2_t) | reinterpret_cast<uintptr_t>(workspace)) & 15)
+  if (!aligned16(patch) || !aligned16(cls) || !aligned16(w->w1_sc) || !aligned16(w->w2_s) || !aligned16(w->w2_c) ||
+      !aligned16(w->w1_t) || !aligned16(w->w2_t) || !aligned16(workspace))
     return VPR_ERR_UNSUPPORTED;
   SaladF32Plan p;
   if (!salad_f32_plan(B, n, C, m, l, t, hidden, &p)) return VPR_ERR_INVALID_ARG;
   if (workspace_bytes < p.total) return VPR_ERR_WORKSPACE;
+  if (sinkhorn_iters < 1) return VPR_ERR_INVALID_ARG;
+  if (n != SA_N && (!aligned4(out_f32) || (reinterpret_cast<uintptr_t>(out_bf16) & 1))) return VPR_ERR_UNSUPPORTED;   // the run-time-n kernel's
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   char* ws = static_cast<char*>(workspace);
   auto u16 = [&](size_t off) { return reinterpret_cast<uint16_t*>(ws + off); };
@@ -859,8 +865,7 @@ static int salad_f32_run(const float* patch, long long patch_img_stride, const f
       {H2 + K2, 2 * K2, 0, 0, W2c, K2, w->b2_c, 0, F, l, 0, (int)rows, l, K2, 0, 0},
       {Ht2, K2, 0, 0, W2t, K2, w->b2_t, 0, g, t, 0, B, t, K2, 0, 0}};
   VPR_TRY_LAUNCH(launch_gemm_nt_group(l2, 3, stream));
-  if (n != SA_N) return launch_sinkhorn_aggregate_n(S, F, g, B, n, m, l, t, dustbin, sinkhorn_iters, out_f32, out_bf16, stream);
-  return launch_sinkhorn_aggregate(S, F, g, B, n, m, l, t, dustbin, sinkhorn_iters, out_f32, out_bf16, stream);
+  return salad_launch_aggregate(S, F, g, B, n, m, l, t, dustbin, sinkhorn_iters, out_f32, out_bf16, stream, 1, 0, nullptr);
 }
 
 extern "C" int vpr_salad_aggregate_f32(const float* patch, long long patch_img_stride, const float* cls, long long cls_stride,
@@ -868,8 +873,8 @@ extern "C" int vpr_salad_aggregate_f32(const float* patch, long long patch_img_s
                                        int m, int l, int t, int hidden, int sinkhorn_iters,
                                        float* out_f32, uint16_t* out_bf16,
                                        void* workspace, size_t workspace_bytes, void* stream) {
-  return salad_f32_run(patch, patch_img_stride, cls, cls_stride, B, n, C, w, dustbin, m, l, t, hidden, sinkhorn_iters, out_f32,
-                       out_bf16, workspace, workspace_bytes, stream, false);
+  return salad_f32_run(SaladDomain::FixedN, patch, patch_img_stride, cls, cls_stride, B, n, C, w, dustbin, m, l, t, hidden,
+                       sinkhorn_iters, out_f32, out_bf16, workspace, workspace_bytes, stream);
 }
 
 extern "C" int vpr_salad_aggregate_f32_n(const float* patch, long long patch_img_stride, const float* cls, long long cls_stride,
@@ -877,6 +882,6 @@ extern "C" int vpr_salad_aggregate_f32_n(const float* patch, long long patch_img
                                          int m, int l, int t, int hidden, int sinkhorn_iters,
                                          float* out_f32, uint16_t* out_bf16,
                                          void* workspace, size_t workspace_bytes, void* stream) {
-  return salad_f32_run(patch, patch_img_stride, cls, cls_stride, B, n, C, w, dustbin, m, l, t, hidden, sinkhorn_iters, out_f32,
-                       out_bf16, workspace, workspace_bytes, stream, true);
+  return salad_f32_run(SaladDomain::AnyN, patch, patch_img_stride, cls, cls_stride, B, n, C, w, dustbin, m, l, t, hidden,
+                       sinkhorn_iters, out_f32, out_bf16, workspace, workspace_bytes, stream);
 }

@@ -30,9 +30,7 @@
 namespace vpr {
 namespace {
 
-constexpr int AN_M = 64;     // clusters
-constexpr int AN_L = 128;    // cluster dim
-constexpr int AN_T = 256;    // token dim (= threads per workgroup)
+constexpr int AN_M = SA_M, AN_L = SA_L, AN_T = SA_T;   // the kernel's names for clusters, cluster dim, token dim (= threads per workgroup)
 constexpr int AN_QMAX = 18;  // score float4 per thread and staging batch: n <= 288 in one round trip, n <= 576 in two
 constexpr int AN_RC = VPR_SALAD_MAX_N / 32;   // 18: row entries per lane of a half-wave
 constexpr int AN_CQ = (VPR_SALAD_MAX_N + 255) / 256;   // 3: columns per thread
@@ -343,7 +341,7 @@ int launch_sinkhorn_aggregate_n(const float* scores, const float* feats, const f
                                 int B, int n, int m, int l, int t, float dustbin, int iters,
                                 float* out_f32, uint16_t* out_bf16, hipStream_t stream) {
   if (!scores || !feats || !tokfeat || !out_f32 || B <= 0 || n < 1 || iters < 1) return VPR_ERR_INVALID_ARG;
-  if (m != AN_M || l != AN_L || t != AN_T || n <= m || n > VPR_SALAD_MAX_N) return VPR_ERR_UNSUPPORTED;
+  if (!salad_in_domain(SaladDomain::AnyN, n, m, l, t)) return VPR_ERR_UNSUPPORTED;
   if (!aligned16(scores) || !aligned16(feats) || !aligned4(tokfeat) || !aligned4(out_f32) || (reinterpret_cast<uintptr_t>(out_bf16) & 1))
     return VPR_ERR_UNSUPPORTED;
   // > 64 KiB of dynamic LDS needs the opt-in: once per device, for the largest n (smaller n then needs no second call)

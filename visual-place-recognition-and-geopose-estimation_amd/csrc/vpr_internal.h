@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <type_traits>
 #include "../../include/vpr_amd.h"
+#include "../../include/vpr_amd_salad_anyres.h"
 
 namespace vpr {
 
@@ -50,6 +51,18 @@ int launch_gemm256_fp8(const uint8_t* A, int lda, const float* a_scale, const ui
 int launch_skinny_linear(const uint16_t* in, int ldi, const uint16_t* W, int ldw, const void* bias, int bias_is_bf16,
                          int mode, uint16_t* out, int ldo, int M, int N, int K, const float* stats_bias,
                          float* row_stats, void* stream);
+
+// ---- SALAD: the one description of what the aggregation is built for (salad.hip, salad_anyres.hip) ------------------
+constexpr int SA_N = 256;   // patch tokens of the fixed-n kernels (224 px at patch 14)
+constexpr int SA_M = 64;    // clusters
+constexpr int SA_L = 128;   // cluster dim
+constexpr int SA_T = 256;   // token dim
+enum class SaladDomain { FixedN, AnyN };       // n == SA_N (include/vpr_amd.h) / SA_M < n <= VPR_SALAD_MAX_N (the any-n extension)
+// The stage-A launchers see neither C nor hidden and leave the defaults.
+inline bool salad_in_domain(SaladDomain d, int n, int m, int l, int t, int C = 64, int hidden = 64) {
+  if (m != SA_M || l != SA_L || t != SA_T || (C % 64) || (hidden % 64)) return false;
+  return d == SaladDomain::AnyN ? (n > SA_M && n <= VPR_SALAD_MAX_N) : n == SA_N;
+}
 
 int launch_sinkhorn_aggregate(const float* scores, const float* feats, const float* tokfeat,
                               int B, int n, int m, int l, int t, float dustbin, int iters,

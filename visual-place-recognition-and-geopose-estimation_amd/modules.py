@@ -94,36 +94,26 @@ class SaladAggregator(nn.Module):
         Always eval arithmetic, whatever `.training` says: the two Dropout(0.3) layers of score / cluster_features are
         never applied here.  The training-mode descriptor (those Dropouts active, as under the fine-tuning script's
         model.train()) is forward_train."""
-        first = tokens.patch if isinstance(tokens, SplitTokens) else tokens
-        n = first.shape[1] - (0 if isinstance(tokens, SplitTokens) else 1)
-        if n != 256:        # any other grid (include/vpr_amd_salad_anyres.h): both layouts addressed in place, no token_ready form
-            if isinstance(tokens, SplitTokens):
-                patch, cls = tokens.patch.contiguous(), tokens.cls.contiguous()
+        split = isinstance(tokens, SplitTokens)
+        first = tokens.patch if split else tokens
+        f32, n = first.dtype == torch.float32, first.shape[1] - (0 if split else 1)
+        w = (self._packed_f32 or self.pack_f32()) if f32 else (self._packed or self.pack())
+        weights = torch_ops.weight_list(w)
+        if n == 256 and not f32:        # the n = 256 bf16 ops take their layout as it comes; only they have a token_ready form
+            if split:
+                desc, desc16 = _vpr.salad_aggregate_split(tokens.patch, tokens.cls, weights, w.dustbin, 3, bool(tokens.token_ready))
             else:
-                patch, cls = tokens.contiguous(), None
-            if first.dtype == torch.float32:
-                w32 = self._packed_f32 or self.pack_f32()
-                desc, desc16 = _vpr.salad_aggregate_f32_n(patch, cls, torch_ops.weight_list(w32), w32.dustbin, 3)
-            else:
-                w = self._packed or self.pack()
-                desc, desc16 = _vpr.salad_aggregate_n(patch, cls, torch_ops.weight_list(w), w.dustbin, 3)
+                desc, desc16 = _vpr.salad_aggregate(tokens, weights, w.dustbin, 3)
             return (desc, desc16) if want_bf16 else desc
-        if first.dtype == torch.float32:
-            w32 = self._packed_f32 or self.pack_f32()
-            if isinstance(tokens, SplitTokens):
-                patch, cls = tokens.patch.contiguous(), tokens.cls.contiguous()
-            else:
-                patch, cls = tokens[:, 1:].contiguous(), tokens[:, 0].contiguous()
-            desc, desc16 = _vpr.salad_aggregate_f32(patch, cls, torch_ops.weight_list(w32), w32.dustbin, 3)
-            return (desc, desc16) if want_bf16 else desc
-        w = self._packed or self.pack()
-        if isinstance(tokens, SplitTokens):
-            desc, desc16 = _vpr.salad_aggregate_split(tokens.patch, tokens.cls, torch_ops.weight_list(w), w.dustbin, 3,
-                                                      bool(tokens.token_ready))
-        else:
-            desc, desc16 = _vpr.salad_aggregate(tokens, torch_ops.weight_list(w), w.dustbin, 3)
+        if split:
+            patch, cls = tokens.patch.contiguous(), tokens.cls.contiguous()
+        elif n == 256:                  # salad_aggregate_f32 takes the pair only
+            patch, cls = tokens[:, 1:].contiguous(), tokens[:, 0].contiguous()
+        else:                           # any other grid (include/vpr_amd_salad_anyres.h): the hub layout addressed in place
+            patch, cls = tokens.contiguous(), None
+        op = _vpr.salad_aggregate_f32 if n == 256 else (_vpr.salad_aggregate_f32_n if f32 else _vpr.salad_aggregate_n)
+        desc, desc16 = op(patch, cls, weights, w.dustbin, 3)
         return (desc, desc16) if want_bf16 else desc
-
 
     def dropout_p(self) -> float:
         """p of the two Dropout layers (score[1], cluster_features[1]); the fused kernel draws one mask rate for both."""

@@ -278,6 +278,20 @@ def salad_aggregate_split(patch: torch.Tensor, cls: torch.Tensor, w: SaladWeight
     return out, out16
 
 
+def _salad_whole(entry: str, dtype: torch.dtype, tokens, w: SaladWeights, iters: int, want_bf16: bool,
+                 out: Optional[torch.Tensor] = None, extra=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The whole aggregation through `entry`, one of the C calls that address either token layout in place: `tokens` of
+    `dtype` as _tokens() takes them.  extra(B, n, hidden) -> (arguments between sinkhorn_iters and the outputs, arguments
+    between the outputs and the workspace): what vpr_salad_aggregate_train adds to the common parameter list."""
+    patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, Ct, device = _tokens(tokens, dtype, entry[len("vpr_"):])
+    (C, hidden, m, l, t), ws, out, out16 = _salad_setup(w, B, n, device, Ct, want_bf16, out)
+    before, after = extra(B, n, hidden) if extra is not None else ((), ())
+    cw = w.c_struct()
+    _call(entry, patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, C, ctypes.byref(cw), float(w.dustbin), m, l, t, hidden,
+          int(iters), *before, _ptr(out), _ptr(out16), *after, _ptr(ws), ws.numel(), _stream())
+    return out, out16
+
+
 def salad_aggregate_train(tokens, w: SaladWeights, dropout_p: float, seed: int, pass_index: int, image_base: int = 0,
                           sinkhorn_iters: int = 3, want_bf16: bool = True, mask_out: Optional[torch.Tensor] = None,
                           out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
@@ -288,22 +302,19 @@ def salad_aggregate_train(tokens, w: SaladWeights, dropout_p: float, seed: int, 
     mask_out (uint8 [B*n, 2*hidden], optional) receives the mask, 1 = kept.  dropout_p = 0 gives the bits of
     salad_aggregate_split.  out (f32 [B, t+l*m], contiguous, optional): where the descriptor goes (e.g. rows of a
     fine-tuning buffer).  -> (descriptor f32 [B, t+l*m], bf16 copy or None)."""
-    patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, Ct, device = _tokens(tokens, torch.bfloat16, "salad_aggregate_train")
-    (C, hidden, m, l, t), ws, out, out16 = _salad_setup(w, B, n, device, Ct, want_bf16, out)
     if not 0 <= int(seed) < 1 << 64:
         raise ValueError(f"salad_aggregate_train: seed must be an unsigned 64-bit integer, got {seed!r}")
     if not 0 <= int(pass_index) < 1 << 32:
         raise ValueError(f"salad_aggregate_train: pass_index must be an unsigned 32-bit integer, got {pass_index!r}")
-    if mask_out is not None:
-        _need(mask_out, torch.uint8, "mask_out", 2)
-        if tuple(mask_out.shape) != (B * n, 2 * hidden):
-            raise RuntimeError(f"mask_out must be [B*n, 2*hidden] = {(B * n, 2 * hidden)}, got {tuple(mask_out.shape)}")
-    cw = w.c_struct()
-    _call("vpr_salad_aggregate_train", patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, C,
-          ctypes.byref(cw), float(w.dustbin), m, l, t, hidden, int(sinkhorn_iters),
-          float(dropout_p), int(seed), int(pass_index), int(image_base), _ptr(out), _ptr(out16),
-          _ptr(mask_out), _ptr(ws), ws.numel(), _stream())
-    return out, out16
+
+    def train_args(B: int, n: int, hidden: int):
+        if mask_out is not None:
+            _need(mask_out, torch.uint8, "mask_out", 2)
+            if tuple(mask_out.shape) != (B * n, 2 * hidden):
+                raise RuntimeError(f"mask_out must be [B*n, 2*hidden] = {(B * n, 2 * hidden)}, got {tuple(mask_out.shape)}")
+        return (float(dropout_p), int(seed), int(pass_index), int(image_base)), (_ptr(mask_out),)
+
+    return _salad_whole("vpr_salad_aggregate_train", torch.bfloat16, tokens, w, sinkhorn_iters, want_bf16, out, train_args)
 
 
 class SaladStageViews(NamedTuple):
@@ -349,12 +360,22 @@ def salad_aggregate_f32(tokens, w: SaladWeightsF32, sinkhorn_iters: int = 3,
                         want_bf16: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """The aggregation at the reference's precision: `tokens` = [B, 1+n, C] f32 (cls first) or a (patch [B,n,C], cls [B,C])
     pair of f32 tensors, f32 weights -> (descriptor f32 [B, t+l*m], bf16 copy or None).  vpr_salad_aggregate_f32."""
-    patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, Ct, device = _tokens(tokens, torch.float32, "salad_aggregate_f32")
-    (C, hidden, m, l, t), ws, out, out16 = _salad_setup(w, B, n, device, Ct, want_bf16)
-    cw = w.c_struct()
-    _call("vpr_salad_aggregate_f32", patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, C,
-          ctypes.byref(cw), float(w.dustbin), m, l, t, hidden, int(sinkhorn_iters),
-          _ptr(out), _ptr(out16), _ptr(ws), ws.numel(), _stream())
+    return _salad_whole("vpr_salad_aggregate_f32", torch.float32, tokens, w, sinkhorn_iters, want_bf16)
+
+
+def _salad_stage_a(entry: str, scores: torch.Tensor, feats: torch.Tensor, tokfeat: torch.Tensor, dustbin: float, iters: int,
+                   want_bf16: bool) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """Stage A alone through `entry` (vpr_salad_sinkhorn_aggregate or its run-time-n form: the same parameter list)."""
+    _need(scores, torch.float32, "scores", 3)
+    _need(feats, torch.float32, "feats", 3)
+    _need(tokfeat, torch.float32, "tokfeat", 2)
+    B, n, m = scores.shape
+    l, t = feats.shape[2], tokfeat.shape[1]
+    if feats.shape[:2] != (B, n) or tokfeat.shape[0] != B:
+        raise RuntimeError(f"{entry[len('vpr_'):]}: inconsistent shapes")
+    out = torch.empty((B, t + l * m), dtype=torch.float32, device=scores.device)
+    out16 = torch.empty_like(out, dtype=torch.bfloat16) if want_bf16 else None
+    _call(entry, _ptr(scores), _ptr(feats), _ptr(tokfeat), B, n, m, l, t, float(dustbin), int(iters), _ptr(out), _ptr(out16), _stream())
     return out, out16
 
 
@@ -362,18 +383,7 @@ def salad_sinkhorn_aggregate(scores: torch.Tensor, feats: torch.Tensor, tokfeat:
                              dustbin: float, sinkhorn_iters: int = 3,
                              want_bf16: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """scores [B,n,m] f32, feats [B,n,l] f32, tokfeat [B,t] f32 -> descriptor (Sinkhorn stage only)."""
-    _need(scores, torch.float32, "scores", 3)
-    _need(feats, torch.float32, "feats", 3)
-    _need(tokfeat, torch.float32, "tokfeat", 2)
-    B, n, m = scores.shape
-    l, t = feats.shape[2], tokfeat.shape[1]
-    if feats.shape[:2] != (B, n) or tokfeat.shape[0] != B:
-        raise RuntimeError("salad_sinkhorn_aggregate: inconsistent shapes")
-    out = torch.empty((B, t + l * m), dtype=torch.float32, device=scores.device)
-    out16 = torch.empty_like(out, dtype=torch.bfloat16) if want_bf16 else None
-    _call("vpr_salad_sinkhorn_aggregate", _ptr(scores), _ptr(feats), _ptr(tokfeat), B, n, m, l, t,
-          float(dustbin), int(sinkhorn_iters), _ptr(out), _ptr(out16), _stream())
-    return out, out16
+    return _salad_stage_a("vpr_salad_sinkhorn_aggregate", scores, feats, tokfeat, dustbin, sinkhorn_iters, want_bf16)
 
 
 # ---- any patch-token count 65 .. 576 (include/vpr_amd_salad_anyres.h); the functions above keep their n = 256 domain ----
@@ -382,18 +392,7 @@ def salad_sinkhorn_aggregate_n(scores: torch.Tensor, feats: torch.Tensor, tokfea
                                want_bf16: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """salad_sinkhorn_aggregate for any n in 65 .. 576: scores [B,n,m] f32, feats [B,n,l] f32, tokfeat [B,t] f32 -> descriptor
     (and its bf16 copy).  Always the run-time-n kernel, n = 256 included.  vpr_salad_sinkhorn_aggregate_n."""
-    _need(scores, torch.float32, "scores", 3)
-    _need(feats, torch.float32, "feats", 3)
-    _need(tokfeat, torch.float32, "tokfeat", 2)
-    B, n, m = scores.shape
-    l, t = feats.shape[2], tokfeat.shape[1]
-    if feats.shape[:2] != (B, n) or tokfeat.shape[0] != B:
-        raise RuntimeError("salad_sinkhorn_aggregate_n: inconsistent shapes")
-    out = torch.empty((B, t + l * m), dtype=torch.float32, device=scores.device)
-    out16 = torch.empty_like(out, dtype=torch.bfloat16) if want_bf16 else None
-    _call("vpr_salad_sinkhorn_aggregate_n", _ptr(scores), _ptr(feats), _ptr(tokfeat), B, n, m, l, t,
-          float(dustbin), int(iters), _ptr(out), _ptr(out16), _stream())
-    return out, out16
+    return _salad_stage_a("vpr_salad_sinkhorn_aggregate_n", scores, feats, tokfeat, dustbin, iters, want_bf16)
 
 
 def salad_aggregate_n(tokens, w: SaladWeights, iters: int = 3,
@@ -401,26 +400,14 @@ def salad_aggregate_n(tokens, w: SaladWeights, iters: int = 3,
     """The aggregation for any patch-token count n in 65 .. 576: `tokens` = [B, 1+n, C] bf16 (cls first) or a (patch [B,n,C],
     cls [B,C]) bf16 pair, addressed in place -> (descriptor f32 [B, t+l*m], bf16 copy or None).  n == 256 gives the bits of
     salad_aggregate_split.  vpr_salad_aggregate_n."""
-    patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, Ct, device = _tokens(tokens, torch.bfloat16, "salad_aggregate_n")
-    (C, hidden, m, l, t), ws, out, out16 = _salad_setup(w, B, n, device, Ct, want_bf16)
-    cw = w.c_struct()
-    _call("vpr_salad_aggregate_n", patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, C,
-          ctypes.byref(cw), float(w.dustbin), m, l, t, hidden, int(iters),
-          _ptr(out), _ptr(out16), _ptr(ws), ws.numel(), _stream())
-    return out, out16
+    return _salad_whole("vpr_salad_aggregate_n", torch.bfloat16, tokens, w, iters, want_bf16)
 
 
 def salad_aggregate_f32_n(tokens, w: SaladWeightsF32, iters: int = 3,
                           want_bf16: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """salad_aggregate_f32 for any n in 65 .. 576 (f32 tokens, hub layout or pair; f32 weights); n == 256 gives its bits.
     vpr_salad_aggregate_f32_n."""
-    patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, Ct, device = _tokens(tokens, torch.float32, "salad_aggregate_f32_n")
-    (C, hidden, m, l, t), ws, out, out16 = _salad_setup(w, B, n, device, Ct, want_bf16)
-    cw = w.c_struct()
-    _call("vpr_salad_aggregate_f32_n", patch_ptr, patch_stride, cls_ptr, cls_stride, B, n, C,
-          ctypes.byref(cw), float(w.dustbin), m, l, t, hidden, int(iters),
-          _ptr(out), _ptr(out16), _ptr(ws), ws.numel(), _stream())
-    return out, out16
+    return _salad_whole("vpr_salad_aggregate_f32_n", torch.float32, tokens, w, iters, want_bf16)
 
 
 def _need_rows(t: torch.Tensor, dtype: torch.dtype, name: str) -> None:

@@ -59,12 +59,6 @@ def salad_aggregate(tokens: Tensor, weights: List[Tensor], dustbin: float, sinkh
     return out, out16
 
 
-@salad_aggregate.register_fake
-def _(tokens, weights, dustbin, sinkhorn_iters):
-    B, D = tokens.shape[0], _desc_width(weights)
-    return tokens.new_empty((B, D), dtype=torch.float32), tokens.new_empty((B, D), dtype=torch.bfloat16)
-
-
 @torch.library.custom_op("vpr::salad_aggregate_split", mutates_args=())
 def salad_aggregate_split(patch: Tensor, cls: Tensor, weights: List[Tensor], dustbin: float,
                           sinkhorn_iters: int, token_done: bool = False) -> Tuple[Tensor, Tensor]:
@@ -75,24 +69,12 @@ def salad_aggregate_split(patch: Tensor, cls: Tensor, weights: List[Tensor], dus
     return out, out16
 
 
-@salad_aggregate_split.register_fake
-def _(patch, cls, weights, dustbin, sinkhorn_iters, token_done=False):
-    B, D = patch.shape[0], _desc_width(weights)
-    return patch.new_empty((B, D), dtype=torch.float32), patch.new_empty((B, D), dtype=torch.bfloat16)
-
-
 @torch.library.custom_op("vpr::salad_aggregate_f32", mutates_args=())
 def salad_aggregate_f32(patch: Tensor, cls: Tensor, weights: List[Tensor], dustbin: float,
                         sinkhorn_iters: int) -> Tuple[Tensor, Tensor]:
     """f32 patch [B, n, C] + cls [B, C], f32 weights: the aggregation at the reference's precision.  vpr_salad_aggregate_f32."""
     out, out16 = ops.salad_aggregate_f32((patch, cls), _weights(weights, dustbin, f32=True), sinkhorn_iters, True)
     return out, out16
-
-
-@salad_aggregate_f32.register_fake
-def _(patch, cls, weights, dustbin, sinkhorn_iters):
-    B, D = patch.shape[0], _desc_width(weights)
-    return patch.new_empty((B, D), dtype=torch.float32), patch.new_empty((B, D), dtype=torch.bfloat16)
 
 
 @torch.library.custom_op("vpr::salad_aggregate_train", mutates_args=())
@@ -109,12 +91,6 @@ def salad_aggregate_train(tokens: Tensor, cls: Optional[Tensor], weights: List[T
     return out, out16
 
 
-@salad_aggregate_train.register_fake
-def _(tokens, cls, weights, dustbin, sinkhorn_iters, dropout_p, seed, pass_index, image_base):
-    B, D = tokens.shape[0], _desc_width(weights)
-    return tokens.new_empty((B, D), dtype=torch.float32), tokens.new_empty((B, D), dtype=torch.bfloat16)
-
-
 @torch.library.custom_op("vpr::salad_aggregate_n", mutates_args=())
 def salad_aggregate_n(patch: Tensor, cls: Optional[Tensor], weights: List[Tensor], dustbin: float,
                       sinkhorn_iters: int) -> Tuple[Tensor, Tensor]:
@@ -123,12 +99,6 @@ def salad_aggregate_n(patch: Tensor, cls: Optional[Tensor], weights: List[Tensor
     n == 256: the bits of salad_aggregate_split.  vpr_salad_aggregate_n."""
     out, out16 = ops.salad_aggregate_n(patch if cls is None else (patch, cls), _weights(weights, dustbin), sinkhorn_iters, True)
     return out, out16
-
-
-@salad_aggregate_n.register_fake
-def _(patch, cls, weights, dustbin, sinkhorn_iters):
-    B, D = patch.shape[0], _desc_width(weights)
-    return patch.new_empty((B, D), dtype=torch.float32), patch.new_empty((B, D), dtype=torch.bfloat16)
 
 
 @torch.library.custom_op("vpr::salad_aggregate_f32_n", mutates_args=())
@@ -141,10 +111,14 @@ def salad_aggregate_f32_n(patch: Tensor, cls: Optional[Tensor], weights: List[Te
     return out, out16
 
 
-@salad_aggregate_f32_n.register_fake
-def _(patch, cls, weights, dustbin, sinkhorn_iters):
-    B, D = patch.shape[0], _desc_width(weights)
-    return patch.new_empty((B, D), dtype=torch.float32), patch.new_empty((B, D), dtype=torch.bfloat16)
+def _salad_fake(tokens, *rest, **_):
+    """Descriptor and its bf16 copy, [B, t + l*m]: the first argument carries B and the device, the weight list the width."""
+    B, D = tokens.shape[0], _desc_width(next(a for a in rest if isinstance(a, (list, tuple))))
+    return tokens.new_empty((B, D), dtype=torch.float32), tokens.new_empty((B, D), dtype=torch.bfloat16)
+
+
+for _op in (salad_aggregate, salad_aggregate_split, salad_aggregate_f32, salad_aggregate_train, salad_aggregate_n, salad_aggregate_f32_n):
+    _op.register_fake(_salad_fake)
 
 
 # -------------------------------------------------------------------------------------------------------------- kNN
