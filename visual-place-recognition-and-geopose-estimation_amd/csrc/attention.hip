@@ -292,19 +292,14 @@ static int attention_launch(const uint16_t* qkv, uint16_t* out, int B, int T, in
   hipStream_t st = static_cast<hipStream_t>(stream);
 #define VPR_ATTN_LAUNCH(NW, PIPE)                                                                        \
   do {                                                                                                   \
-    static PerDeviceFlag attr = {};                                                                      \
-    VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(attention_kernel<NW, PIPE>), AT_LDS, attr)); \
-    VPR_TRY_LAUNCH(launch_kernel(attention_kernel<NW, PIPE>, dim3((unsigned)(B * H)), dim3(NW * 64), AT_LDS, st, \
-                                 qkv, out, T, Tp, tail_row0, H, c, dephase));                                           \
+    VPR_TRY_LAUNCH((launch_kernel_lds<attention_kernel<NW, PIPE>>(dim3((unsigned)(B * H)), dim3(NW * 64), AT_LDS, st, \
+                                                                  qkv, out, T, Tp, tail_row0, H, c, dephase)));     \
   } while (0)
 #ifdef VPR_ABLATION
 #define VPR_ATTN_ABL(A)                                                                                   \
   do {                                                                                                   \
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<8, false, A>),                \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)AT_LDS) != hipSuccess)      \
-      return VPR_ERR_LAUNCH;                                                                             \
-    VPR_TRY_LAUNCH(launch_kernel(attention_kernel<8, false, A>, dim3((unsigned)(B * H)), dim3(512), AT_LDS, st, \
-                                 qkv, out, T, Tp, tail_row0, H, c, 0));                                  \
+    VPR_TRY_LAUNCH((launch_kernel_lds<attention_kernel<8, false, A>>(dim3((unsigned)(B * H)), dim3(512), AT_LDS, st, \
+                                                                     qkv, out, T, Tp, tail_row0, H, c, 0)));        \
   } while (0)
 #endif
   // Ablations (variants 12-14, timing only, -DVPR_ABLATION builds: `make ablation`): K/V + Q staging alone 11.4 us

@@ -92,25 +92,6 @@ extern "C" const char* vpr_status_string(int status) {
 
 extern "C" int vpr_abi_version(void) { return VPR_AMD_ABI_VERSION; }
 
-extern "C" int vpr_gemm_nt_bf16(const uint16_t* A, int lda, int a_group_rows, long long a_group_stride,
-                                const uint16_t* W, int ldw, const float* bias, int relu, void* C, int ldc,
-                                int out_is_bf16, int M, int N, int K, void* stream) {
-  return launch_gemm_nt(A, lda, a_group_rows, a_group_stride, W, ldw, bias, relu, C, ldc, out_is_bf16, M, N, K,
-                        static_cast<hipStream_t>(stream));
-}
-
-extern "C" int vpr_gemm_nt_group_bf16(const vpr_gemm_problem* probs, int count, void* stream) {
-  if (!probs || count < 1 || count > GEMM_MAX_GROUP) return VPR_ERR_INVALID_ARG;
-  GemmProblem g[GEMM_MAX_GROUP] = {};
-  for (int i = 0; i < count; ++i) {
-    const vpr_gemm_problem& p = probs[i];
-    g[i].A = p.A; g[i].lda = p.lda; g[i].a_group_rows = p.a_group_rows; g[i].a_group_stride = p.a_group_stride;
-    g[i].W = p.W; g[i].ldw = p.ldw; g[i].bias = p.bias; g[i].relu = p.relu;
-    g[i].C = p.C; g[i].ldc = p.ldc; g[i].out_is_bf16 = p.out_is_bf16; g[i].M = p.M; g[i].N = p.N; g[i].K = p.K;
-  }
-  return launch_gemm_nt_group(g, count, static_cast<hipStream_t>(stream));
-}
-
 extern "C" int vpr_f32_to_bf16(const float* src, uint16_t* dst, long long count, void* stream) {
   if (!src || !dst || count < 0) return VPR_ERR_INVALID_ARG;
   if (count == 0) return VPR_OK;

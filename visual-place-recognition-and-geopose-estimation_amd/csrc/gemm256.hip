@@ -87,12 +87,7 @@ __device__ __forceinline__ void g2_mainloop(const GemmProblem& pr, char* smem, G
   const int wr = wave >> 2, wc = wave & 3;
 
   // XCD-aware bijective remap; consecutive tiles of one XCD share the A panel (tile_n fastest)
-  const int nwg = pr.tiles_m * pr.tiles_n;
-  int tile;
-  {
-    const int orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  }
+  const int tile = xcd_tile(blockIdx.x, pr.tiles_m * pr.tiles_n);
   // grouped raster inside the XCD's contiguous range: the ~32 tiles an XCD runs concurrently form
   // a 4 (M) x 8 (N) patch, i.e. 12 operand panels through its L2 instead of 33 for a 1 x 32 strip
   int tm, tn;
@@ -527,50 +522,37 @@ __global__ __launch_bounds__(512, 2) void gemm256_fuse2_kernel(GemmProblem pr, F
 
 constexpr size_t G2_LDS = 128 * (G2_BN * 4 + 16);   // >= the two K-tile buffers (128 KB); sized by the f32 epilogue staging
 
-const char* gemm256_kernel_name(bool fp8) {      // what launch_gemm256 (bf16) / launch_gemm256_fp8 launch
-  if (fp8) return "vpr::gemm256_kernel<true, 10>";
+// What runs a problem: the name a kernel trace prints and the launch.  VPR_GEMM256_DEPTH (timing-only build, bf16): the
+// shallower prefetch distances of g2_wait_vm (same results).
+struct Gemm256Kernel { const char* name; int (*launch)(const GemmProblem& g, dim3 grid, hipStream_t stream); };
+
+template <auto Kernel>
+static int gemm256_run(const GemmProblem& g, dim3 grid, hipStream_t stream) {
+  return launch_kernel_lds<Kernel>(grid, dim3(512), G2_LDS, stream, g);
+}
+// = gemm256_run<gemm256_kernel<true>>, named at the end of this file: kernels are emitted in the order the source first names
+// them, and the e4m3 one stays the last of the code object, where it has always been
+static int gemm256_run_e4m3(const GemmProblem& g, dim3 grid, hipStream_t stream);
+
+static Gemm256Kernel gemm256_choose(bool e4m3) {
+  if (e4m3) return {"vpr::gemm256_kernel<true, 10>", gemm256_run_e4m3};
 #ifdef VPR_ABLATION
   const int depth = tune_or(TUNE_GEMM256_DEPTH, 10);
-  if (depth == 6 || depth == 2) return depth == 6 ? "vpr::gemm256_kernel<false, 6>" : "vpr::gemm256_kernel<false, 2>";
+  if (depth == 6) return {"vpr::gemm256_kernel<false, 6>", gemm256_run<gemm256_kernel<false, 6>>};
+  if (depth == 2) return {"vpr::gemm256_kernel<false, 2>", gemm256_run<gemm256_kernel<false, 2>>};
 #endif
-  return "vpr::gemm256_kernel<false, 10>";
+  return {"vpr::gemm256_kernel<false, 10>", gemm256_run<gemm256_kernel<false>>};
 }
 
-int launch_gemm256(const GemmProblem& in, hipStream_t stream) {
+const char* gemm256_kernel_name(bool e4m3) { return gemm256_choose(e4m3).name; }
+
+int launch_gemm256(const GemmProblem& in, bool e4m3, hipStream_t stream) {
+  VPR_TRY_LAUNCH(gemm_check(in, e4m3, GemmTile::T256));
   GemmProblem g = in;
-  if (!g.A || !g.W || !g.C || g.M <= 0 || g.N <= 0 || g.K <= 0) return VPR_ERR_INVALID_ARG;
-  if (g.K % 64 != 0 || g.K < 128 || g.lda < g.K || g.ldw < g.K || g.ldc < g.N) return VPR_ERR_UNSUPPORTED;
-  if ((g.lda % 8) || (g.ldw % 8) || (g.ldc % 4) || (g.a_group_rows > 0 && (g.a_group_stride % 8))) return VPR_ERR_UNSUPPORTED;
-  // the epilogue reads the bias as float4 (a null bias is fine)
-  if ((reinterpret_cast<uintptr_t>(g.A) | reinterpret_cast<uintptr_t>(g.W) | reinterpret_cast<uintptr_t>(g.C) |
-       reinterpret_cast<uintptr_t>(g.bias)) & 15)
-    return VPR_ERR_UNSUPPORTED;
   g.tiles_m = (g.M + G2_BM - 1) / G2_BM;
   g.tiles_n = (g.N + G2_BN - 1) / G2_BN;
-  g.a_scale = g.w_scale = nullptr;
   g.kstagger = tune_or(TUNE_GEMM256_STAGGER, 0);
-  const int ksplit = g.ksplit > 1 ? g.ksplit : 1;
-  if (ksplit > 1 && (g.bias != nullptr || g.relu || g.K / 64 < 2 * ksplit)) return VPR_ERR_UNSUPPORTED;   // slabs are linear partial sums
-#ifdef VPR_ABLATION
-  {   // timing-only build: shallower prefetch distance (same results)
-    const int depth = tune_or(TUNE_GEMM256_DEPTH, 10);
-    if (depth == 6 || depth == 2) {
-      static PerDeviceFlag a6 = {}, a2 = {};
-      if (depth == 6) {
-        VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(gemm256_kernel<false, 6>), G2_LDS, a6));
-        VPR_TRY_LAUNCH(launch_kernel(gemm256_kernel<false, 6>, dim3(g.tiles_m * g.tiles_n, ksplit), dim3(512), G2_LDS, stream, g));
-      } else {
-        VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(gemm256_kernel<false, 2>), G2_LDS, a2));
-        VPR_TRY_LAUNCH(launch_kernel(gemm256_kernel<false, 2>, dim3(g.tiles_m * g.tiles_n, ksplit), dim3(512), G2_LDS, stream, g));
-      }
-      return VPR_OK;
-    }
-  }
-#endif
-  static PerDeviceFlag attr = {};
-  VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(gemm256_kernel<false>), G2_LDS, attr));
-  VPR_TRY_LAUNCH(launch_kernel(gemm256_kernel<false>, dim3(g.tiles_m * g.tiles_n, ksplit), dim3(512), G2_LDS, stream, g));
-  return VPR_OK;
+  return gemm256_choose(e4m3).launch(g, dim3(g.tiles_m * g.tiles_n, g.ksplit > 1 ? g.ksplit : 1), stream);
 }
 
 __global__ __launch_bounds__(256) void pack_w2_fragments_kernel(const uint16_t* __restrict__ w2, int n_out, int hidden,
@@ -612,22 +594,18 @@ int launch_salad_mlps_fused(const uint16_t* X, int ldx, int group_rows, long lon
        reinterpret_cast<uintptr_t>(W2c) | reinterpret_cast<uintptr_t>(b1) | reinterpret_cast<uintptr_t>(b2s) |
        reinterpret_cast<uintptr_t>(b2c) | reinterpret_cast<uintptr_t>(S) | reinterpret_cast<uintptr_t>(F)) & 15)
     return VPR_ERR_UNSUPPORTED;
-  GemmProblem g{X, ldx, group_rows, group_stride, W1, C, b1, 1, nullptr, 0, 1, M, 2 * hidden, C, M / G2_BM, 2 * hidden / G2_BN,
-                nullptr, nullptr, 1, 0, tune_or(TUNE_GEMM256_STAGGER, 0)};
+  GemmProblem g = gemm_problem(X, ldx, W1, C, b1, 1, nullptr, 0, 1, M, 2 * hidden, C);    // H stays in LDS: no C
+  g.a_group_rows = group_rows; g.a_group_stride = group_stride;
+  g.tiles_m = M / G2_BM; g.tiles_n = 2 * hidden / G2_BN;
+  g.ksplit = 1; g.kstagger = tune_or(TUNE_GEMM256_STAGGER, 0);
   if ((reinterpret_cast<uintptr_t>(W2s_frag) | reinterpret_cast<uintptr_t>(W2c_frag)) & 15) return VPR_ERR_UNSUPPORTED;
   Fuse2 f{{W2s, W2c}, {W2s_frag, W2c_frag}, {b2s, b2c}, {S, F}, {m, l}, hidden};
+  const dim3 grid(g.tiles_m * g.tiles_n);
   if (drop != nullptr) {
     if (group_rows != G2_BM || (reinterpret_cast<uintptr_t>(drop->mask_out) & 3)) return VPR_ERR_UNSUPPORTED;
-    static PerDeviceFlag attr_drop = {};
-    VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(gemm256_fuse2_kernel<true, Fuse2Drop>), G2_LDS, attr_drop));
-    VPR_TRY_LAUNCH(launch_kernel(gemm256_fuse2_kernel<true, Fuse2Drop>, dim3(g.tiles_m * g.tiles_n), dim3(512), G2_LDS, stream, g, f,
-                                 *drop));
-    return VPR_OK;
+    return launch_kernel_lds<gemm256_fuse2_kernel<true, Fuse2Drop>>(grid, dim3(512), G2_LDS, stream, g, f, *drop);
   }
-  static PerDeviceFlag attr = {};
-  VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(gemm256_fuse2_kernel<false>), G2_LDS, attr));
-  VPR_TRY_LAUNCH(launch_kernel(gemm256_fuse2_kernel<false>, dim3(g.tiles_m * g.tiles_n), dim3(512), G2_LDS, stream, g, f));
-  return VPR_OK;
+  return launch_kernel_lds<gemm256_fuse2_kernel<false>>(grid, dim3(512), G2_LDS, stream, g, f);
 }
 
 #ifdef VPR_ABLATION
@@ -635,23 +613,7 @@ extern "C" int vpr_gemm256_fuse2_set_clocks(long long* clocks) {
   return hipMemcpyToSymbol(HIP_SYMBOL(g_fuse2_clocks), &clocks, sizeof(clocks)) == hipSuccess ? VPR_OK : VPR_ERR_LAUNCH;
 }
 #endif
-// e4m3 operands with per-row scales, f32 out: C[m][n] = a_scale[m] * w_scale[n] * sum_k A[m][k] W[n][k]; K % 128 == 0, K >= 256.
-int launch_gemm256_fp8(const uint8_t* A, int lda, const float* a_scale, const uint8_t* W, int ldw, const float* w_scale,
-                       float* C, int ldc, int M, int N, int K, hipStream_t stream, int ksplit, long long slab_stride) {
-  if (!A || !W || !C || !a_scale || !w_scale || M <= 0 || N <= 0 || K <= 0) return VPR_ERR_INVALID_ARG;
-  if (ksplit < 1) ksplit = 1;
-  if (K / 128 < 2 * ksplit) return VPR_ERR_UNSUPPORTED;
-  if ((K % 128) || K < 256 || lda < K || ldw < K || ldc < N || (lda % 16) || (ldw % 16) || (ldc % 4)) return VPR_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(C)) & 15)
-    return VPR_ERR_UNSUPPORTED;
-  GemmProblem g{reinterpret_cast<const uint16_t*>(A), lda, 0, 0, reinterpret_cast<const uint16_t*>(W), ldw, nullptr, 0,
-                C, ldc, 0, M, N, K, (M + G2_BM - 1) / G2_BM, (N + G2_BN - 1) / G2_BN, a_scale, w_scale, ksplit, slab_stride,
-                tune_or(TUNE_GEMM256_STAGGER, 0)};
-  static PerDeviceFlag attr = {};
-  VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(gemm256_kernel<true>), G2_LDS, attr));
-  VPR_TRY_LAUNCH(launch_kernel(gemm256_kernel<true>, dim3(g.tiles_m * g.tiles_n, ksplit), dim3(512), G2_LDS, stream, g));
-  return VPR_OK;
-}
+static int gemm256_run_e4m3(const GemmProblem& g, dim3 grid, hipStream_t stream) { return gemm256_run<gemm256_kernel<true>>(g, grid, stream); }
 
 }  // namespace vpr
 
@@ -659,12 +621,4 @@ using namespace vpr;
 
 extern "C" int vpr_salad_pack_w2_fragments(const uint16_t* w2, int n_out, int hidden, uint16_t* out, void* stream) {
   return launch_pack_w2_fragments(w2, n_out, hidden, out, static_cast<hipStream_t>(stream));
-}
-
-// Same contract as vpr_gemm_nt_bf16 (K >= 128, ldc % 4 == 0, C and bias 16-byte aligned), 256 x 256 tiles.
-extern "C" int vpr_gemm256_nt_bf16(const uint16_t* A, int lda, int a_group_rows, long long a_group_stride,
-                                   const uint16_t* W, int ldw, const float* bias, int relu, void* C, int ldc,
-                                   int out_is_bf16, int M, int N, int K, void* stream) {
-  const GemmProblem g{A, lda, a_group_rows, a_group_stride, W, ldw, bias, relu, C, ldc, out_is_bf16, M, N, K, 0, 0};
-  return launch_gemm256(g, static_cast<hipStream_t>(stream));
 }

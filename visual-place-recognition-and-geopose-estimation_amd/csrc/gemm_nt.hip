@@ -35,13 +35,7 @@ __device__ __forceinline__ void gemm_nt_tile(const GemmProblem& pr, int orig, ch
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave / WN, wn = wave % WN;
 
-  // XCD-aware bijective remap (cdna guide §5 "XCD swizzle must be bijective").
-  const int nwg = tiles_m * tiles_n;
-  int tile;
-  {
-    const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  }
+  const int tile = xcd_tile(orig, tiles_m * tiles_n);
   const int tm = tile / tiles_n, tn = tile % tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
 
@@ -196,12 +190,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_fp8_kernel(GemmFp8Problem pr) 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave / WN, wn = wave % WN;
-  const int nwg = pr.tiles_m * pr.tiles_n;
-  int tile;
-  {
-    const int orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  }
+  const int tile = xcd_tile(blockIdx.x, pr.tiles_m * pr.tiles_n);
   // tile_m fastest: the (few) query tiles that share a gallery panel run back to back on one XCD
   const int tm = tile % pr.tiles_m, tn = tile / pr.tiles_m;
   const int m0 = tm * BM, n0 = tn * BN;
@@ -283,101 +272,118 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_fp8_kernel(GemmFp8Problem pr) 
     }
 }
 
-int launch_gemm_nt_fp8(const uint8_t* A, int lda, const float* a_scale, const uint8_t* W, int ldw, const float* w_scale,
-                       float* C, int ldc, int M, int N, int K, hipStream_t stream) {
-  if (!A || !W || !C || !a_scale || !w_scale || M <= 0 || N <= 0 || K <= 0) return VPR_ERR_INVALID_ARG;
-  if ((K % 128) || lda < K || ldw < K || ldc < N || (lda % 16) || (ldw % 16)) return VPR_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W)) & 15) return VPR_ERR_UNSUPPORTED;
-  GemmFp8Problem g{A, lda, W, ldw, a_scale, w_scale, C, ldc, M, N, K, (M + 127) / 128, (N + 127) / 128};
-  constexpr size_t lds = 2 * (128 + 128) * TILE_ROW_BYTES;
-  VPR_TRY_LAUNCH(launch_kernel(gemm_nt_fp8_kernel, dim3(g.tiles_m * g.tiles_n), dim3(256), lds, stream, g));
+// ---- host side: one rule set, one kernel choice, two launchers ---------------------------------------------------------
+// The argument rules of every GEMM launch of the library, in bytes; es = operand element size.  INVALID_ARG (nulls,
+// non-positive sizes) comes before UNSUPPORTED (shape, pitch, alignment).
+int gemm_check(const GemmProblem& g, bool e4m3, GemmTile tile) {
+  const long long es = e4m3 ? 1 : 2;
+  if (!g.A || !g.W || !g.C || (e4m3 && (!g.a_scale || !g.w_scale)) || g.M <= 0 || g.N <= 0 || g.K <= 0) return VPR_ERR_INVALID_ARG;
+  // K is whole 128-byte tile rows; rows do not overlap; every 16-byte LDS-DMA piece of A and W is aligned
+  if ((g.K * es % 128) || g.lda < g.K || g.ldw < g.K || g.ldc < g.N) return VPR_ERR_UNSUPPORTED;
+  if ((g.lda * es % 16) || (g.ldw * es % 16) || (g.a_group_rows > 0 && (g.a_group_stride * es % 16))) return VPR_ERR_UNSUPPORTED;
+  if (!aligned16(g.A) || !aligned16(g.W)) return VPR_ERR_UNSUPPORTED;
+  // the e4m3 kernels are the plain scaled product: no bias, no activation, f32 out, dense rows (no caller asks otherwise)
+  if (e4m3 && (g.bias || g.relu || g.out_is_bf16 || g.a_group_rows > 0)) return VPR_ERR_UNSUPPORTED;
+  const int ktiles = (int)(g.K * es / 128), ksplit = g.ksplit > 1 ? g.ksplit : 1;
+  // 128-row tiles have no split-K.  No caller asks for one; until this rule existed the request was silently ignored.
+  if (tile == GemmTile::T128) return ksplit > 1 ? VPR_ERR_UNSUPPORTED : VPR_OK;
+  // 256 x 256 tiles: the pipeline's prologue issues two K-tiles; the epilogue stores 8 / 16 bytes at once and reads the
+  // bias as float4 (a null bias is fine); split-K slabs are linear partial sums of at least two K-tiles each
+  if (ktiles < 2 || (g.ldc % 4) || !aligned16(g.C) || !aligned16(g.bias)) return VPR_ERR_UNSUPPORTED;
+  if (ksplit > 1 && (g.bias != nullptr || g.relu || ktiles < 2 * ksplit)) return VPR_ERR_UNSUPPORTED;
   return VPR_OK;
 }
 
-static int gemm_check(const GemmProblem& g) {
-  if (!g.A || !g.W || !g.C || g.M <= 0 || g.N <= 0 || g.K <= 0) return VPR_ERR_INVALID_ARG;
-  if (g.K % 64 != 0 || g.lda < g.K || g.ldw < g.K || g.ldc < g.N) return VPR_ERR_UNSUPPORTED;
-  if ((g.lda % 8) || (g.ldw % 8) || (g.a_group_rows > 0 && (g.a_group_stride % 8))) return VPR_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(g.A) | reinterpret_cast<uintptr_t>(g.W)) & 15) return VPR_ERR_UNSUPPORTED;
-  return VPR_OK;
+// What runs a problem of N output columns: the name a kernel trace prints, the output-tile width, and the launch.
+struct GemmNtKernel { const char* name; int bn; int (*launch)(const GemmProblem& g, hipStream_t stream); };
+
+template <auto Kernel, int BN, int STAGES>
+static int gemm_nt_run(const GemmProblem& g, hipStream_t stream) {
+  return launch_kernel_lds<Kernel>(dim3(g.tiles_m * g.tiles_n), dim3(256), (size_t)STAGES * (128 + BN) * TILE_ROW_BYTES, stream, g);
+}
+static int gemm_nt_run_fp8(const GemmProblem& g, hipStream_t stream) {
+  const GemmFp8Problem f{reinterpret_cast<const uint8_t*>(g.A), g.lda, reinterpret_cast<const uint8_t*>(g.W), g.ldw, g.a_scale,
+                         g.w_scale, static_cast<float*>(g.C), g.ldc, g.M, g.N, g.K, g.tiles_m, g.tiles_n};
+  return launch_kernel_lds<gemm_nt_fp8_kernel>(dim3(g.tiles_m * g.tiles_n), dim3(256), (size_t)2 * (128 + 128) * TILE_ROW_BYTES, stream, f);
 }
 
-// launch_gemm_nt's two decisions, shared with gemm_nt_kernel_name: 128-column tiles (else one 64-column tile), and the A/B
-// switch VPR_GEMM_NT_STAGES, 3 = three-deep ring (96 KB: one workgroup per CU).  Measured on the kNN score tile, 2 vs 3
-// stages: 128 x 50k 217 / 291 us, 512 x 12.5k 141 / 205 us — two workgroups per CU beat the deeper ring.
-static bool gemm_nt_wide(int N) { return N > 64; }
-static bool gemm_nt_three_stages() { return tune_or(TUNE_GEMM_NT_STAGES, 2) == 3; }
-
-const char* gemm_nt_kernel_name(bool fp8, int N) {
-  if (fp8) return "vpr::gemm_nt_fp8_kernel";
-  if (!gemm_nt_wide(N)) return "vpr::gemm_nt_kernel<64, 4, 1, 2>";
-  return gemm_nt_three_stages() ? "vpr::gemm_nt_kernel<128, 2, 2, 3>" : "vpr::gemm_nt_kernel<128, 2, 2, 2>";
+// bf16: 128-column tiles, or one 64-column tile for N <= 64; and the A/B switch VPR_GEMM_NT_STAGES, 3 = three-deep ring
+// (96 KB: one workgroup per CU).  Measured on the kNN score tile, 2 vs 3 stages: 128 x 50k 217 / 291 us, 512 x 12.5k
+// 141 / 205 us — two workgroups per CU beat the deeper ring.
+static GemmNtKernel gemm_nt_choose(bool e4m3, int N) {
+  if (e4m3) return {"vpr::gemm_nt_fp8_kernel", 128, gemm_nt_run_fp8};
+  if (N > 64 && tune_or(TUNE_GEMM_NT_STAGES, 2) == 3)
+    return {"vpr::gemm_nt_kernel<128, 2, 2, 3>", 128, gemm_nt_run<gemm_nt_kernel<128, 2, 2, 3>, 128, 3>};
+  if (N > 64) return {"vpr::gemm_nt_kernel<128, 2, 2, 2>", 128, gemm_nt_run<gemm_nt_kernel<128, 2, 2>, 128, 2>};
+  return {"vpr::gemm_nt_kernel<64, 4, 1, 2>", 64, gemm_nt_run<gemm_nt_kernel<64, 4, 1>, 64, 2>};
 }
 
-int launch_gemm_nt(const uint16_t* A, int lda, int a_group_rows, long long a_group_stride,
-                   const uint16_t* W, int ldw, const float* bias, int relu, void* C, int ldc,
-                   int out_is_bf16, int M, int N, int K, hipStream_t stream) {
-  GemmProblem g{A, lda, a_group_rows, a_group_stride, W, ldw, bias, relu, C, ldc, out_is_bf16, M, N, K, 0, 0};
-  const int st = gemm_check(g);
-  if (st != VPR_OK) return st;
-  g.tiles_m = (M + 127) / 128;
-  if (gemm_nt_wide(N)) {
-    g.tiles_n = (N + 127) / 128;
-    if (gemm_nt_three_stages()) {
-      constexpr size_t lds3 = 3 * (128 + 128) * TILE_ROW_BYTES;
-      static PerDeviceFlag attr = {};
-      VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(gemm_nt_kernel<128, 2, 2, 3>), lds3, attr));
-      VPR_TRY_LAUNCH(launch_kernel((gemm_nt_kernel<128, 2, 2, 3>), dim3(g.tiles_m * g.tiles_n), dim3(256), lds3, stream, g));
-      return VPR_OK;
-    }
-    constexpr size_t lds = 2 * (128 + 128) * TILE_ROW_BYTES;
-    VPR_TRY_LAUNCH(launch_kernel((gemm_nt_kernel<128, 2, 2>), dim3(g.tiles_m * g.tiles_n), dim3(256), lds, stream, g));
-  } else {
-    g.tiles_n = 1;
-    constexpr size_t lds = 2 * (128 + 64) * TILE_ROW_BYTES;
-    VPR_TRY_LAUNCH(launch_kernel((gemm_nt_kernel<64, 4, 1>), dim3(g.tiles_m * g.tiles_n), dim3(256), lds, stream, g));
-  }
-  return VPR_OK;
+const char* gemm_nt_kernel_name(bool e4m3, int N) { return gemm_nt_choose(e4m3, N).name; }
+
+int launch_gemm_nt(const GemmProblem& in, bool e4m3, hipStream_t stream) {
+  VPR_TRY_LAUNCH(gemm_check(in, e4m3, GemmTile::T128));
+  const GemmNtKernel k = gemm_nt_choose(e4m3, in.N);
+  GemmProblem g = in;
+  g.tiles_m = (g.M + 127) / 128;
+  g.tiles_n = (g.N + k.bn - 1) / k.bn;
+  return k.launch(g, stream);
 }
 
-// Grouped launch with 128x128 tiles for every member (a member with N <= 64 wastes MFMA work on
-// its half-empty tile, which is cheaper than a launch of its own).
+// Grouped launch, one tile shape for every member.  The grouped problems are short (K = 512: 8 K-tiles) and about one
+// workgroup per CU: with the 2-deep ring each K-step waits out one full memory round trip.  Variant 1 keeps two tiles in
+// flight (3-deep ring) on 128 x 64 tiles (72 KB of LDS: still two workgroups per CU, so the ~390 workgroups stay one
+// resident round; a 3-deep ring on 128 x 128 tiles is 96 KB = one workgroup per CU and 258 workgroups then need a second
+// round: measured 101.6 vs 88.9 us for the whole SALAD stage).  Variant 0: 128 x 128 tiles, 2-deep ring (a member with
+// N <= 64 wastes MFMA work on its half-empty tile, which is cheaper than a launch of its own).
 int launch_gemm_nt_group(const GemmProblem* probs, int count, hipStream_t stream) {
   if (!probs || count < 1 || count > GEMM_MAX_GROUP) return VPR_ERR_INVALID_ARG;
+  const bool narrow = tune_or(TUNE_GEMM_GROUP_VARIANT, 1) == 1;   // A/B switch: 0 = 89.9 us; 1 = default (84.4 us)
+  const int bn = narrow ? 64 : 128;
   GemmGroup grp;
   grp.count = count;
   int total = 0;
-  for (int i = 0; i < count; ++i) {
-    grp.p[i] = probs[i];
-    const int st = gemm_check(grp.p[i]);
-    if (st != VPR_OK) return st;
-    grp.p[i].tiles_m = (grp.p[i].M + 127) / 128;
-    grp.p[i].tiles_n = (grp.p[i].N + 127) / 128;
-    total += grp.p[i].tiles_m * grp.p[i].tiles_n;
+  for (int i = 0; i < GEMM_MAX_GROUP; ++i) {
+    if (i >= count) { grp.p[i] = grp.p[0]; continue; }          // padding: never read by the kernel
+    GemmProblem& g = grp.p[i] = probs[i];
+    VPR_TRY_LAUNCH(gemm_check(g, false, GemmTile::T128));
+    g.tiles_m = (g.M + 127) / 128;
+    g.tiles_n = (g.N + bn - 1) / bn;
+    total += g.tiles_m * g.tiles_n;
   }
-  for (int i = count; i < GEMM_MAX_GROUP; ++i) grp.p[i] = grp.p[0];
-  // The grouped problems are short (K = 512: 8 K-tiles) and about one workgroup per CU: with the 2-deep ring each
-  // K-step waits out one full memory round trip.  Variant 1 keeps two tiles in flight (3-deep ring) on 128 x 64
-  // tiles (72 KB of LDS: still two workgroups per CU, so the ~390 workgroups stay one resident round; a 3-deep
-  // ring on 128 x 128 tiles is 96 KB = one workgroup per CU and 258 workgroups then need a second round:
-  // measured 101.6 vs 88.9 us for the whole SALAD stage).
-  const int variant = tune_or(TUNE_GEMM_GROUP_VARIANT, 1);   // A/B switch: 0 = 128 x 128 tiles, 2-deep ring (89.9 us); 1 = default (84.4 us)
-  if (variant == 1) {
-    total = 0;
-    for (int i = 0; i < count; ++i) {
-      grp.p[i].tiles_n = (grp.p[i].N + 63) / 64;
-      total += grp.p[i].tiles_m * grp.p[i].tiles_n;
-    }
-    for (int i = count; i < GEMM_MAX_GROUP; ++i) grp.p[i] = grp.p[0];
-    constexpr size_t lds3 = 3 * (128 + 64) * TILE_ROW_BYTES;
-    static PerDeviceFlag attr = {};
-    VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(gemm_nt_group_kernel<64, 4, 1, 3>), lds3, attr));
-    VPR_TRY_LAUNCH(launch_kernel((gemm_nt_group_kernel<64, 4, 1, 3>), dim3(total), dim3(256), lds3, stream, grp));
-    return VPR_OK;
-  }
-  constexpr size_t lds = 2 * (128 + 128) * TILE_ROW_BYTES;
-  VPR_TRY_LAUNCH(launch_kernel((gemm_nt_group_kernel<128, 2, 2, 2>), dim3(total), dim3(256), lds, stream, grp));
-  return VPR_OK;
+  if (narrow)
+    return launch_kernel_lds<gemm_nt_group_kernel<64, 4, 1, 3>>(dim3(total), dim3(256), (size_t)3 * (128 + 64) * TILE_ROW_BYTES, stream, grp);
+  return launch_kernel_lds<gemm_nt_group_kernel<128, 2, 2, 2>>(dim3(total), dim3(256), (size_t)2 * (128 + 128) * TILE_ROW_BYTES, stream, grp);
 }
 
 }  // namespace vpr
+
+using namespace vpr;
+
+// ---- the three GEMM entries of the C ABI (include/vpr_amd.h) -----------------------------------------------------------
+static GemmProblem gemm_problem_c(const vpr_gemm_problem& p) {
+  GemmProblem g = gemm_problem(p.A, p.lda, p.W, p.ldw, p.bias, p.relu, p.C, p.ldc, p.out_is_bf16, p.M, p.N, p.K);
+  g.a_group_rows = p.a_group_rows; g.a_group_stride = p.a_group_stride;
+  return g;
+}
+
+extern "C" int vpr_gemm_nt_bf16(const uint16_t* A, int lda, int a_group_rows, long long a_group_stride,
+                                const uint16_t* W, int ldw, const float* bias, int relu, void* C, int ldc,
+                                int out_is_bf16, int M, int N, int K, void* stream) {
+  const vpr_gemm_problem p{A, lda, a_group_rows, a_group_stride, W, ldw, bias, relu, C, ldc, out_is_bf16, M, N, K};
+  return launch_gemm_nt(gemm_problem_c(p), false, static_cast<hipStream_t>(stream));
+}
+
+// Same contract as vpr_gemm_nt_bf16 (K >= 128, ldc % 4 == 0, C and bias 16-byte aligned), 256 x 256 tiles.
+extern "C" int vpr_gemm256_nt_bf16(const uint16_t* A, int lda, int a_group_rows, long long a_group_stride,
+                                   const uint16_t* W, int ldw, const float* bias, int relu, void* C, int ldc,
+                                   int out_is_bf16, int M, int N, int K, void* stream) {
+  const vpr_gemm_problem p{A, lda, a_group_rows, a_group_stride, W, ldw, bias, relu, C, ldc, out_is_bf16, M, N, K};
+  return launch_gemm256(gemm_problem_c(p), false, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int vpr_gemm_nt_group_bf16(const vpr_gemm_problem* probs, int count, void* stream) {
+  if (!probs || count < 1 || count > GEMM_MAX_GROUP) return VPR_ERR_INVALID_ARG;
+  GemmProblem g[GEMM_MAX_GROUP];
+  for (int i = 0; i < count; ++i) g[i] = gemm_problem_c(probs[i]);
+  return launch_gemm_nt_group(g, count, static_cast<hipStream_t>(stream));
+}

@@ -1098,12 +1098,9 @@ struct KnnCall {
 template <int TR, int WGPC, int FLAGS>
 static int knn_launch_stream(const KnnCall& c, dim3 grid, float* S, hipStream_t stream) {
   return knn_dispatch_fp8(c.o.fp8, [&](auto fp8) {
-    static PerDeviceFlag attr = {};                    // one per instantiation
-    const auto kernel = knn_scores_kernel<decltype(fp8)::value, TR, WGPC, FLAGS>;
     constexpr size_t lds = (size_t)2 * (TR + KNN_QT) * TILE_ROW_BYTES;
-    if (lds > 65536) VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(kernel), lds, attr));
-    return launch_kernel(kernel, grid, dim3(256), lds, stream, c.o.q, c.o.g, c.o.q_scale, c.o.g_scale, S, c.B, c.N,
-                         c.row_bytes, c.p.ldS);
+    return launch_kernel_lds<knn_scores_kernel<decltype(fp8)::value, TR, WGPC, FLAGS>>(
+        grid, dim3(256), lds, stream, c.o.q, c.o.g, c.o.q_scale, c.o.g_scale, S, c.B, c.N, c.row_bytes, c.p.ldS);
   });
 }
 
@@ -1152,21 +1149,14 @@ static int knn_scores(const KnnCall& c, hipStream_t stream) {
   const int B = c.B, N = c.N, D = c.D;
   float* S = reinterpret_cast<float*>(c.ws + p.off_S);
   const long long slab_stride = (long long)B * p.ldS;
-  if (c.route == ROUTE_GEMM256 && o.fp8)
-    return launch_gemm256_fp8(static_cast<const uint8_t*>(o.q), D, o.q_scale, static_cast<const uint8_t*>(o.g), D,
-                              o.g_scale, S, p.ldS, B, N, D, stream, c.nslab, slab_stride);
-  if (c.route == ROUTE_GEMM128 && o.fp8)      // block-scaled fp8 MFMA GEMM (twice the bf16 rate), scales in its epilogue
-    return launch_gemm_nt_fp8(static_cast<const uint8_t*>(o.q), D, o.q_scale, static_cast<const uint8_t*>(o.g), D,
-                              o.g_scale, S, p.ldS, B, N, D, stream);
-  if (c.route == ROUTE_GEMM256) {
-    GemmProblem g{static_cast<const uint16_t*>(o.q), D, 0, 0, static_cast<const uint16_t*>(o.g), D, nullptr, 0,
-                  S, p.ldS, 0, B, N, D, 0, 0};
-    g.ksplit = c.nslab; g.slab_stride = slab_stride;
-    return launch_gemm256(g, stream);
+  if (c.route != ROUTE_STREAM) {      // e4m3: block-scaled fp8 MFMA (twice the bf16 rate), scales in the epilogue
+    GemmProblem g = o.fp8 ? gemm_problem_e4m3(static_cast<const uint8_t*>(o.q), D, o.q_scale, static_cast<const uint8_t*>(o.g), D,
+                                              o.g_scale, S, p.ldS, B, N, D)
+                          : gemm_problem(static_cast<const uint16_t*>(o.q), D, static_cast<const uint16_t*>(o.g), D, nullptr, 0,
+                                         S, p.ldS, 0, B, N, D);
+    g.ksplit = c.nslab; g.slab_stride = slab_stride;      // ROUTE_GEMM128 never splits K (knn_route)
+    return (c.route == ROUTE_GEMM256 ? launch_gemm256 : launch_gemm_nt)(g, o.fp8, stream);
   }
-  if (c.route == ROUTE_GEMM128)
-    return launch_gemm_nt(static_cast<const uint16_t*>(o.q), D, 0, 0, static_cast<const uint16_t*>(o.g), D, nullptr,
-                          0, S, p.ldS, 0, B, N, D, stream);
   // Streaming kernel.  Fully resident, balanced grid; never more workgroups than 16-row blocks of gallery.
   int nwg = device_cu_count() * c.stream->k.wgpc;
   const int max_useful = (N + 15) / 16;

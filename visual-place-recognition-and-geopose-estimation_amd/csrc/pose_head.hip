@@ -654,9 +654,7 @@ static bool pose_fused_plan(int B, int D, int hidden, PoseFusedPlan* p) {
 // Opts kernel K (a caller of pose_l1_split_tile) in to its PH_SPLIT_LDS bytes of dynamic LDS, once per device, and launches it.
 template <auto K, typename... Args>
 static int launch_split_l1(dim3 grid, int waves, hipStream_t stream, Args... args) {
-  static PerDeviceFlag attr = {};
-  VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(K), PH_SPLIT_LDS, attr));
-  return launch_kernel(K, grid, dim3(waves * 64), PH_SPLIT_LDS, stream, args...);
+  return launch_kernel_lds<K>(grid, dim3(waves * 64), PH_SPLIT_LDS, stream, args...);
 }
 
 template <class Slab>

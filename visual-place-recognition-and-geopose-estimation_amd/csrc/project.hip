@@ -198,18 +198,11 @@ extern "C" int vpr_project_rows(const uint16_t* x, long long x_stride, int rows,
   if (route == 0) {
     const PjPlan plan = pj_plan(D, d);
     nslab = plan.nslice;
-    static PerDeviceFlag attr = {};
-    VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(project_split_kernel), PJ_SPLIT_LDS, attr));
-    VPR_TRY_LAUNCH(launch_kernel(project_split_kernel, dim3(d / 64, plan.nslice, (rows + 63) / 64), dim3(PJ_WAVES * 64),
-                                 PJ_SPLIT_LDS, stream, x, x_stride, rows, D, P, d, part, plan.steps));
+    VPR_TRY_LAUNCH(launch_kernel_lds<project_split_kernel>(dim3(d / 64, plan.nslice, (rows + 63) / 64), dim3(PJ_WAVES * 64),
+                                                           PJ_SPLIT_LDS, stream, x, x_stride, rows, D, P, d, part, plan.steps));
   } else {
-    if (D >= 128 && d >= 256) {
-      GemmProblem g{x, (int)x_stride, 0, 0, P, D, nullptr, 0, part, d, 0, rows, d, D, 0, 0};
-      g.a_scale = g.w_scale = nullptr; g.ksplit = 1; g.slab_stride = 0; g.kstagger = 0;
-      VPR_TRY_LAUNCH(launch_gemm256(g, stream));
-    } else {
-      VPR_TRY_LAUNCH(launch_gemm_nt(x, (int)x_stride, 0, 0, P, D, nullptr, 0, part, d, 0, rows, d, D, stream));
-    }
+    const GemmProblem g = gemm_problem(x, (int)x_stride, P, D, nullptr, 0, part, d, 0, rows, d, D);
+    VPR_TRY_LAUNCH(D >= 128 && d >= 256 ? launch_gemm256(g, false, stream) : launch_gemm_nt(g, false, stream));
   }
   return launch_kernel(project_finish_kernel, dim3((unsigned)rows), dim3(PJ_FIN_THREADS), 0, stream, part, nslab,
                        (long long)rows * d, c, d, normalize, out_f32, out_bf16);

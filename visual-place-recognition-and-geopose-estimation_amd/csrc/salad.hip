@@ -428,10 +428,8 @@ int launch_sinkhorn_aggregate(const float* scores, const float* feats, const flo
   const int rpx = (!quarters && nslab == 2 && B % 8 == 0 && tune_or(TUNE_SALAD_VARIANT, 0) == 4) ? B / 8 : 0;
 #define VPR_SINKHORN_LAUNCH(NS, NQV, LDS, GRID)                                                                              \
   do {                                                                                                                       \
-    static PerDeviceFlag attr = {};   /* > 64 KiB of dynamic LDS needs the opt-in once per device */                         \
-    VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(sinkhorn_aggregate_kernel<NS, NQV>), LDS, attr));         \
-    VPR_TRY_LAUNCH(launch_kernel((sinkhorn_aggregate_kernel<NS, NQV>), dim3(GRID), dim3(256), LDS, stream, scores, feats, tokfeat, \
-                                 nslab == 2 ? slab_rows : 0LL, dustbin, iters, out_f32, out_bf16, counters, rpx));            \
+    VPR_TRY_LAUNCH((launch_kernel_lds<sinkhorn_aggregate_kernel<NS, NQV>>(dim3(GRID), dim3(256), LDS, stream, scores, feats, tokfeat, \
+                    nslab == 2 ? slab_rows : 0LL, dustbin, iters, out_f32, out_bf16, counters, rpx)));                       \
   } while (0)
   if (quarters) {
     if (nslab == 2) VPR_SINKHORN_LAUNCH(2, 4, SINKHORN_LDS_Q, 4 * B); else VPR_SINKHORN_LAUNCH(1, 4, SINKHORN_LDS_Q, 4 * B);
@@ -534,7 +532,7 @@ static int salad_stage_token(const SaladArgs& a, hipStream_t stream) {
   const vpr_salad_weights* w = a.w;
   int st = launch_skinny_linear(a.cls, (int)a.cls_stride, w->w1_t, a.C, w->b1_t, 0, 3, Ht, a.hidden, a.B, a.hidden, a.C, nullptr, nullptr, stream);
   if (st == VPR_ERR_UNSUPPORTED) {
-    const GemmProblem l1{a.cls, (int)a.cls_stride, 0, 0, w->w1_t, a.C, w->b1_t, 1, Ht, a.hidden, 1, a.B, a.hidden, a.C, 0, 0};
+    const GemmProblem l1 = gemm_problem(a.cls, (int)a.cls_stride, w->w1_t, a.C, w->b1_t, 1, Ht, a.hidden, 1, a.B, a.hidden, a.C);
     st = launch_gemm_nt_group(&l1, 1, stream);
   }
   if (st != VPR_OK) return st;
@@ -542,7 +540,7 @@ static int salad_stage_token(const SaladArgs& a, hipStream_t stream) {
   st = launch_skinny_linear(Ht, a.hidden, w->w2_t, a.hidden, w->b2_t, 0, 5, reinterpret_cast<uint16_t*>(g), a.t, a.B, a.t, a.hidden,
                             nullptr, nullptr, stream);
   if (st != VPR_ERR_UNSUPPORTED) return st;
-  const GemmProblem l2{Ht, a.hidden, 0, 0, w->w2_t, a.hidden, w->b2_t, 0, g, a.t, 0, a.B, a.t, a.hidden, 0, 0};
+  const GemmProblem l2 = gemm_problem(Ht, a.hidden, w->w2_t, a.hidden, w->b2_t, 0, g, a.t, 0, a.B, a.t, a.hidden);
   return launch_gemm_nt_group(&l2, 1, stream);
 }
 
@@ -561,13 +559,14 @@ static int salad_stage_mlps(const SaladArgs& a, hipStream_t stream, const Fuse2D
   if (drop != nullptr) return VPR_ERR_UNSUPPORTED;
   // unfused: layer 1 on the 256 x 256-tile kernel (34 of SALAD's 38 GFLOP; B tiles x 4 = one full wave of workgroups at
   // B = 64), hidden activations through HBM as bf16, the two second layers as one grouped launch
-  const GemmProblem l1_sc{a.patch, a.C, a.n, a.patch_img_stride, w->w1_sc, a.C, w->b1_sc, 1, H, 2 * hidden, 1, rows, 2 * hidden, a.C, 0, 0};
-  int st = launch_gemm256(l1_sc, stream);
+  GemmProblem l1_sc = gemm_problem(a.patch, a.C, w->w1_sc, a.C, w->b1_sc, 1, H, 2 * hidden, 1, rows, 2 * hidden, a.C);
+  l1_sc.a_group_rows = a.n; l1_sc.a_group_stride = a.patch_img_stride;
+  int st = launch_gemm256(l1_sc, false, stream);
   if (st == VPR_ERR_UNSUPPORTED) st = launch_gemm_nt_group(&l1_sc, 1, stream);
   if (st != VPR_OK) return st;
   const GemmProblem l2[2] = {
-      {H, 2 * hidden, 0, 0, w->w2_s, hidden, w->b2_s, 0, S, a.m, 0, rows, a.m, hidden, 0, 0},
-      {H + hidden, 2 * hidden, 0, 0, w->w2_c, hidden, w->b2_c, 0, F, a.l, 0, rows, a.l, hidden, 0, 0}};
+      gemm_problem(H, 2 * hidden, w->w2_s, hidden, w->b2_s, 0, S, a.m, 0, rows, a.m, hidden),
+      gemm_problem(H + hidden, 2 * hidden, w->w2_c, hidden, w->b2_c, 0, F, a.l, 0, rows, a.l, hidden)};
   return launch_gemm_nt_group(l2, 2, stream);
 }
 
@@ -850,20 +849,20 @@ static int salad_f32_run(SaladDomain domain, const float* patch, long long patch
   VPR_TRY_LAUNCH(launch_split3(w->w2_c, l, hidden, hidden, 0, 0, W2c, K2, 1, stream));
   VPR_TRY_LAUNCH(launch_split3(w->w2_t, t, hidden, hidden, 0, 0, W2t, K2, 1, stream));
   // layer 1 (f32 out, bias + ReLU in the epilogue)
-  const GemmProblem l1_sc{A1, K1, 0, 0, W1, K1, w->b1_sc, 1, H, 2 * hidden, 0, (int)rows, 2 * hidden, K1, 0, 0};
-  int st = launch_gemm256(l1_sc, stream);
+  const GemmProblem l1_sc = gemm_problem(A1, K1, W1, K1, w->b1_sc, 1, H, 2 * hidden, 0, (int)rows, 2 * hidden, K1);
+  int st = launch_gemm256(l1_sc, false, stream);
   if (st == VPR_ERR_UNSUPPORTED) st = launch_gemm_nt_group(&l1_sc, 1, stream);
   if (st != VPR_OK) return st;
-  const GemmProblem l1_t{cls3, K1, 0, 0, W1t, K1, w->b1_t, 1, Ht, hidden, 0, B, hidden, K1, 0, 0};
+  const GemmProblem l1_t = gemm_problem(cls3, K1, W1t, K1, w->b1_t, 1, Ht, hidden, 0, B, hidden, K1);
   VPR_TRY_LAUNCH(launch_gemm_nt_group(&l1_t, 1, stream));
   // hidden activations: f32 -> planes ([score 6h | cluster 6h] per row)
   VPR_TRY_LAUNCH(launch_split3(H, rows, hidden, 2 * hidden, 0, 0, H2, 2 * K2, 0, stream));
   VPR_TRY_LAUNCH(launch_split3(H + hidden, rows, hidden, 2 * hidden, 0, 0, H2 + K2, 2 * K2, 0, stream));
   VPR_TRY_LAUNCH(launch_split3(Ht, B, hidden, hidden, 0, 0, Ht2, K2, 0, stream));
   const GemmProblem l2[3] = {
-      {H2, 2 * K2, 0, 0, W2s, K2, w->b2_s, 0, S, m, 0, (int)rows, m, K2, 0, 0},
-      {H2 + K2, 2 * K2, 0, 0, W2c, K2, w->b2_c, 0, F, l, 0, (int)rows, l, K2, 0, 0},
-      {Ht2, K2, 0, 0, W2t, K2, w->b2_t, 0, g, t, 0, B, t, K2, 0, 0}};
+      gemm_problem(H2, 2 * K2, W2s, K2, w->b2_s, 0, S, m, 0, (int)rows, m, K2),
+      gemm_problem(H2 + K2, 2 * K2, W2c, K2, w->b2_c, 0, F, l, 0, (int)rows, l, K2),
+      gemm_problem(Ht2, K2, W2t, K2, w->b2_t, 0, g, t, 0, B, t, K2)};
   VPR_TRY_LAUNCH(launch_gemm_nt_group(l2, 3, stream));
   return salad_launch_aggregate(S, F, g, B, n, m, l, t, dustbin, sinkhorn_iters, out_f32, out_bf16, stream, 1, 0, nullptr);
 }

@@ -344,9 +344,8 @@ int launch_sinkhorn_aggregate_n(const float* scores, const float* feats, const f
   if (!salad_in_domain(SaladDomain::AnyN, n, m, l, t)) return VPR_ERR_UNSUPPORTED;
   if (!aligned16(scores) || !aligned16(feats) || !aligned4(tokfeat) || !aligned4(out_f32) || (reinterpret_cast<uintptr_t>(out_bf16) & 1))
     return VPR_ERR_UNSUPPORTED;
-  // > 64 KiB of dynamic LDS needs the opt-in: once per device, for the largest n (smaller n then needs no second call)
-  static PerDeviceFlag attr = {};
-  VPR_TRY_LAUNCH(optin_dynamic_lds(reinterpret_cast<const void*>(sinkhorn_aggregate_n_kernel), anyres_lds(VPR_SALAD_MAX_N).total, attr));
+  // the opt-in once per device, for the largest n (smaller n then needs no second call)
+  VPR_TRY_LAUNCH(optin_dynamic_lds<sinkhorn_aggregate_n_kernel>(anyres_lds(VPR_SALAD_MAX_N).total));
   return launch_kernel(sinkhorn_aggregate_n_kernel, dim3(B), dim3(256), anyres_lds(n).total, stream, scores, feats, tokfeat, n,
                        dustbin, iters, out_f32, out_bf16);
 }

@@ -152,6 +152,14 @@ __device__ __forceinline__ bf16x8 lds_frag(const char* tile, int row, int chunk)
   return *reinterpret_cast<const bf16x8*>(tile + tile_off(row, chunk));
 }
 
+// XCD-aware remap of a workgroup id to a tile (cdna guide §5: "XCD swizzle must be bijective").  Workgroup `orig` of `nwg`
+// runs on XCD orig % 8; the workgroups of one XCD get a contiguous run of tiles (the first nwg % 8 XCDs one more each), so
+// neighbouring tiles re-use an operand panel out of that XCD's L2.
+__device__ __forceinline__ int xcd_tile(int orig, int nwg) {
+  const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+}
+
 // Philox4x32-10 (Salmon et al., SC'11; the Random123 constants): ten rounds of two 32x32 -> 64 multiplies.  The dropout
 // masks of the head-training step and of the SALAD MLPs (include/vpr_amd.h) are words of it.
 __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {

@@ -9,30 +9,46 @@
 
 namespace vpr {
 
-int launch_gemm_nt(const uint16_t* A, int lda, int a_group_rows, long long a_group_stride,
-                   const uint16_t* W, int ldw, const float* bias, int relu, void* C, int ldc,
-                   int out_is_bf16, int M, int N, int K, hipStream_t stream);
-
-// One member of a (grouped) GEMM launch: C = act(A W^T + bias); see gemm_nt.hip.  tiles_* are filled in
-// by the launcher.
+// One member of a (grouped) GEMM launch: C = act(A W^T + bias); see gemm_nt.hip.  tiles_* and kstagger are filled in by the
+// launcher.  The struct is a kernel argument: its layout is part of the kernels' code.
 struct GemmProblem {
   const uint16_t* A; int lda; int a_group_rows; long long a_group_stride;
   const uint16_t* W; int ldw; const float* bias; int relu;
   void* C; int ldc; int out_is_bf16; int M, N, K; int tiles_m, tiles_n;
-  const float* a_scale; const float* w_scale;       // gemm256 fp8 form only (per-row scales of A and W); null otherwise
+  const float* a_scale; const float* w_scale;       // e4m3 form only (per-row scales of A and W); null otherwise
   int ksplit; long long slab_stride;                // gemm256 split-K: K slices (0 / 1 = none); slice z writes C + z * slab_stride elements
   int kstagger;                                     // gemm256: order in which a tile walks its K-tiles (0 = 0, 1, 2, ...; see g2_mainloop)
 };
+// The two ways to make one: named operands, everything else zero (no row groups, no split-K: set those by member).
+inline GemmProblem gemm_problem(const uint16_t* A, int lda, const uint16_t* W, int ldw, const float* bias, int relu,
+                                void* C, int ldc, int out_is_bf16, int M, int N, int K) {
+  GemmProblem g = {};
+  g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.bias = bias; g.relu = relu;
+  g.C = C; g.ldc = ldc; g.out_is_bf16 = out_is_bf16; g.M = M; g.N = N; g.K = K;
+  return g;
+}
+// e4m3 operands (lda / ldw / K in bytes = elements) with per-row f32 scales, f32 out:
+// C[m][n] = a_scale[m] * w_scale[n] * sum_k A[m][k] W[n][k]
+inline GemmProblem gemm_problem_e4m3(const uint8_t* A, int lda, const float* a_scale, const uint8_t* W, int ldw,
+                                     const float* w_scale, float* C, int ldc, int M, int N, int K) {
+  GemmProblem g = gemm_problem(reinterpret_cast<const uint16_t*>(A), lda, reinterpret_cast<const uint16_t*>(W), ldw, nullptr, 0,
+                               C, ldc, 0, M, N, K);
+  g.a_scale = a_scale; g.w_scale = w_scale;
+  return g;
+}
 constexpr int GEMM_MAX_GROUP = 3;
-int launch_gemm_nt_group(const GemmProblem* probs, int count, hipStream_t stream);
-// gemm_nt.hip: fp8 e4m3 operands with per-row scales, f32 out (kNN score tile for > 64 queries); K % 128 == 0
-int launch_gemm_nt_fp8(const uint8_t* A, int lda, const float* a_scale, const uint8_t* W, int ldw, const float* w_scale,
-                       float* C, int ldc, int M, int N, int K, hipStream_t stream);
-int launch_gemm256(const GemmProblem& problem, hipStream_t stream);   // gemm256.hip: 256x256 tiles, K >= 128
-// What launch_gemm_nt[_fp8] (N output columns) / launch_gemm256[_fp8] launch, by the name a kernel trace prints: each sits
-// beside its launch function and takes the same decisions.
-const char* gemm_nt_kernel_name(bool fp8, int N);
-const char* gemm256_kernel_name(bool fp8);
+// The one launch entry of each tile family; e4m3: the operands are e4m3 bytes (gemm_problem_e4m3), else bf16.
+//   launch_gemm_nt  (gemm_nt.hip): 128-row tiles, any K of whole 128-byte tile rows; no split-K.
+//   launch_gemm256  (gemm256.hip): 256 x 256 tiles, at least two K-tiles, stricter C / bias alignment, split-K.
+// Both refuse by gemm_check and launch what gemm_nt_kernel_name / gemm256_kernel_name say.
+enum class GemmTile { T128, T256 };
+int gemm_check(const GemmProblem& g, bool e4m3, GemmTile tile);
+int launch_gemm_nt(const GemmProblem& problem, bool e4m3, hipStream_t stream);
+int launch_gemm256(const GemmProblem& problem, bool e4m3, hipStream_t stream);
+int launch_gemm_nt_group(const GemmProblem* probs, int count, hipStream_t stream);    // bf16, gemm_check(T128) per member
+// The kernel such a launch runs (N output columns), by the name a kernel trace prints.
+const char* gemm_nt_kernel_name(bool e4m3, int N);
+const char* gemm256_kernel_name(bool e4m3);
 // gemm256.hip: SALAD score + cluster MLPs with the second layers fused into the layer-1 tile epilogue; S / F receive
 // hidden / 256 partial-sum slabs of [M][m] / [M][l] f32 (slab 0 carries the bias), to be added in slab order.
 // Fuse2Drop: dropout on the hidden layer (vpr_salad_aggregate_train): unit u of token `token` of image image_base + b is kept
@@ -44,9 +60,6 @@ int launch_salad_mlps_fused(const uint16_t* X, int ldx, int group_rows, long lon
                             float* S, float* F, int M, int C, int hidden, int m, int l, hipStream_t stream,
                             const uint16_t* W2s_frag = nullptr, const uint16_t* W2c_frag = nullptr,
                             const Fuse2Drop* drop = nullptr);
-// gemm256.hip, fp8 form: e4m3 operands with per-row scales, f32 out (kNN score tile of a >= 384-query gathered batch)
-int launch_gemm256_fp8(const uint8_t* A, int lda, const float* a_scale, const uint8_t* W, int ldw, const float* w_scale,
-                       float* C, int ldc, int M, int N, int K, hipStream_t stream, int ksplit = 1, long long slab_stride = 0);
 // skinny.hip: a few rows x [N, K]^T; mode 0 bias, 1 bias+tanh-GELU, 2 accumulate into out, 3 bias+ReLU, 4 bias+erf-GELU
 int launch_skinny_linear(const uint16_t* in, int ldi, const uint16_t* W, int ldw, const void* bias, int bias_is_bf16,
                          int mode, uint16_t* out, int ldo, int M, int N, int K, const float* stats_bias,
@@ -104,20 +117,32 @@ int tune(TuneOpt o);
 inline int tune_or(TuneOpt o, int dflt) { const int v = tune(o); return v == TUNE_UNSET ? dflt : v; }
 
 // ---- per-device launch state ---------------------------------------------------------------------------------------
-// hipFuncSetAttribute (the > 64 KB dynamic-LDS opt-in) and the CU count belong to a DEVICE, not to the process: one
+// hipFuncSetAttribute (the dynamic-LDS opt-in from 64 KB up) and the CU count belong to a DEVICE, not to the process: one
 // flag / one cached value per device ordinal, looked up through hipGetDevice() at every launch (~50 ns).  A process
 // that drives several GPUs (or switches device between calls) gets the opt-in on each of them.
 constexpr int VPR_MAX_DEVICES = 64;
-struct PerDeviceFlag { unsigned char set[VPR_MAX_DEVICES]; };
-inline int optin_dynamic_lds(const void* kernel, size_t bytes, PerDeviceFlag& flag) {
+// The opt-in for `bytes` of dynamic LDS of Kernel: nothing to do below 64 KiB; AT 64 KiB it is made, because a kernel may
+// hold static LDS beside its dynamic 64 KiB (pose_fused_kernel does).  The per-device flag is a static of this
+// instantiation, i.e. of Kernel: no two kernels can share one, which would leave the second without its opt-in.
+template <auto Kernel>
+inline int optin_dynamic_lds(size_t bytes) {
+  static unsigned char done[VPR_MAX_DEVICES] = {};
+  if (bytes < 65536) return VPR_OK;
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= VPR_MAX_DEVICES) return VPR_ERR_LAUNCH;
-  if (!flag.set[dev]) {      // two threads racing here both set the attribute: harmless
-    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+  if (!done[dev]) {          // two threads racing here both set the attribute: harmless
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
       return VPR_ERR_LAUNCH;
-    flag.set[dev] = 1;
+    done[dev] = 1;
   }
   return VPR_OK;
+}
+// launch_kernel with the opt-in for the launch's own LDS size.  (A kernel whose LDS size varies per call opts in for its
+// maximum through optin_dynamic_lds and then calls launch_kernel: salad_anyres.hip.)
+template <auto Kernel, typename... Args>
+inline int launch_kernel_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, Args... args) {
+  const int st = optin_dynamic_lds<Kernel>(lds_bytes);
+  return st != VPR_OK ? st : launch_kernel(Kernel, grid, block, lds_bytes, stream, args...);
 }
 int device_cu_count();      // capi.hip: multiProcessorCount of the current device, cached per device (256 on MI355X)
 
