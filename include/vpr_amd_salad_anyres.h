@@ -48,8 +48,8 @@
  *   VPR_ERR_UNSUPPORTED   shape or alignment outside the domain above.
  *   VPR_ERR_WORKSPACE     workspace_bytes below the size call's answer.
  *
- * Out of scope.  n > 576 (448 / 518 px) needs a kernel that does not keep one image's score matrix in one CU's LDS.  The
- * fused MLP kernel serves whole 256-row tiles per image only, so n != 256 pays the hidden activations' round trip through
+ * Out of scope.  n > 576 (448 / 518 px) is served by include/vpr_amd_salad_hires.h, whose stage A keeps no score matrix in LDS;
+ * the calls here keep refusing it.  The fused MLP kernel serves whole 256-row tiles per image only, so n != 256 pays the hidden activations' round trip through
  * HBM.  Train-mode aggregation (vpr_salad_aggregate_train) keeps refusing n != 256: its dropout mask lives in the fused kernel.
  */
 #ifndef VPR_AMD_SALAD_ANYRES_H

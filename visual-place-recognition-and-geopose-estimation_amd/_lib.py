@@ -191,6 +191,15 @@ SALAD_ANYRES_PROTOTYPES = {
                                           c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
 }
 
+# include/vpr_amd_salad_hires.h, the seventh table: the aggregation for 65 .. 1369 patch tokens (448 / 518 px); the parameter
+# lists of the sixth table
+SALAD_HIRES_MAX_N = 1369                      # VPR_SALAD_HIRES_MAX_N
+SALAD_HIRES_PROTOTYPES = {
+    "vpr_salad_sinkhorn_aggregate_hires": SALAD_ANYRES_PROTOTYPES["vpr_salad_sinkhorn_aggregate_n"],
+    "vpr_salad_aggregate_hires": SALAD_ANYRES_PROTOTYPES["vpr_salad_aggregate_n"],
+    "vpr_salad_aggregate_f32_hires": SALAD_ANYRES_PROTOTYPES["vpr_salad_aggregate_f32_n"],
+}
+
 
 def rerank_roundings(D: int, rows_are_f32: bool) -> int:
     """VPR_RERANK_ROUNDINGS: L of the fine score, the roundings on the longest path from a product to the result."""
@@ -216,7 +225,7 @@ def lib() -> ctypes.CDLL:
         for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(EXTENSION_PROTOTYPES.items())
                                           + list(EXPAND_PROTOTYPES.items()) + list(PROJECT_PROTOTYPES.items())
                                           + list(RERANK_PROTOTYPES.items()) + list(SALAD_STAGES_PROTOTYPES.items())
-                                          + list(SALAD_ANYRES_PROTOTYPES.items())):
+                                          + list(SALAD_ANYRES_PROTOTYPES.items()) + list(SALAD_HIRES_PROTOTYPES.items())):
             fn = getattr(handle, name)   # AttributeError if a declared symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

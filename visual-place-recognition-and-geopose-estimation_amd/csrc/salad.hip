@@ -17,11 +17,14 @@
 //   vpr_salad_aggregate_f32: the same at the reference's fp32 precision (three bf16 planes per operand, f32 hidden).
 //   vpr_salad_aggregate_n / _f32_n (include/vpr_amd_salad_anyres.h): any token count 65 .. 576 — stages T and the unfused M
 //   as above, stage A by sinkhorn_aggregate_n_kernel (salad_anyres.hip); everything else here stays n = 256.
+//   vpr_salad_aggregate_hires / _f32_hires (include/vpr_amd_salad_hires.h): 65 .. 1369 tokens — the same stages, stage A above
+//   576 tokens by sinkhorn_aggregate_hires_kernel (salad_hires.hip), which keeps no score matrix in LDS.
 #include <math.h>
 #include "vpr_common.h"
 #include "vpr_internal.h"
 #include "../../include/vpr_amd_salad_stages.h"
 #include "../../include/vpr_amd_salad_anyres.h"
+#include "../../include/vpr_amd_salad_hires.h"
 
 namespace vpr {
 
@@ -499,11 +502,12 @@ static bool salad_misaligned(const SaladArgs& a, unsigned stages) {
 
 // The one pre-check of a call that runs `stages`: every refusal a stage or a launcher below could make, decided here, so
 // that a refused call has launched nothing.  The order is the ABI's: INVALID_ARG (sizes, weights), UNSUPPORTED (domain),
-// WORKSPACE, then the operands of the stages.  The any-n entries report sinkhorn_iters < 1 ahead of everything and, where
-// they leave the n = 256 chain, a misaligned operand ahead of WORKSPACE (include/vpr_amd_salad_anyres.h).
+// WORKSPACE, then the operands of the stages.  The any-n and high-resolution entries report sinkhorn_iters < 1 ahead of
+// everything and, where they leave the n = 256 chain, a misaligned operand ahead of WORKSPACE
+// (include/vpr_amd_salad_anyres.h, include/vpr_amd_salad_hires.h).
 static int salad_args(SaladArgs* a, SaladDomain domain, unsigned stages, void* workspace, size_t workspace_bytes) {
   const bool iters_bad = (stages & STAGE_A) && a->sinkhorn_iters < 1;
-  if (domain == SaladDomain::AnyN && iters_bad) return VPR_ERR_INVALID_ARG;
+  if (domain != SaladDomain::FixedN && iters_bad) return VPR_ERR_INVALID_ARG;
   if (!workspace || a->B <= 0 || a->n < 1 || a->C <= 0) return VPR_ERR_INVALID_ARG;
   if ((stages & (STAGE_T | STAGE_M)) && !salad_weights_complete(a->w)) return VPR_ERR_INVALID_ARG;
   if (!salad_in_domain(domain, a->n, a->m, a->l, a->t, a->C, a->hidden)) return VPR_ERR_UNSUPPORTED;
@@ -571,10 +575,12 @@ static int salad_stage_mlps(const SaladArgs& a, hipStream_t stream, const Fuse2D
 }
 
 // The one choice of the stage-A kernel: the n = 256 kernel on `nslab` partial-sum slabs `slab_rows` rows apart (with the arrival
-// counters, where the caller has them), the run-time-n kernel for any other n: one dense slab, as salad_slabs() says off 256.
+// counters, where the caller has them); for any other n one dense slab, as salad_slabs() says off 256: the run-time-n kernel
+// up to VPR_SALAD_MAX_N tokens, above that the high-resolution kernel, which keeps no score matrix in LDS.
 static int salad_launch_aggregate(const float* S, const float* F, const float* g, int B, int n, int m, int l, int t, float dustbin,
                                   int iters, float* out_f32, uint16_t* out_bf16, hipStream_t stream, int nslab, long long slab_rows,
                                   int* counters) {
+  if (n > VPR_SALAD_MAX_N) return launch_sinkhorn_aggregate_hires(S, F, g, B, n, m, l, t, dustbin, iters, out_f32, out_bf16, stream);
   if (n != SA_N) return launch_sinkhorn_aggregate_n(S, F, g, B, n, m, l, t, dustbin, iters, out_f32, out_bf16, stream);
   return launch_sinkhorn_aggregate(S, F, g, B, n, m, l, t, dustbin, iters, out_f32, out_bf16, stream, nslab, slab_rows, counters);
 }
@@ -703,6 +709,17 @@ extern "C" int vpr_salad_aggregate_n(const uint16_t* patch, long long patch_img_
                    out_f32, out_bf16, workspace, workspace_bytes, stream);
 }
 
+// include/vpr_amd_salad_hires.h: the same run for 64 < n <= 1369.  salad_launch_aggregate() chooses stage A by n, so n == 256 and
+// every other n <= 576 are the calls above, bit for bit; above 576 tokens the unfused stage M feeds the high-resolution stage A.
+extern "C" int vpr_salad_aggregate_hires(const uint16_t* patch, long long patch_img_stride, const uint16_t* cls, long long cls_stride,
+                                         int B, int n, int C, const vpr_salad_weights* w, float dustbin,
+                                         int m, int l, int t, int hidden, int sinkhorn_iters,
+                                         float* out_f32, uint16_t* out_bf16,
+                                         void* workspace, size_t workspace_bytes, void* stream) {
+  return salad_run(SaladDomain::HiRes, patch, patch_img_stride, cls, cls_stride, B, n, C, w, dustbin, m, l, t, hidden, sinkhorn_iters,
+                   out_f32, out_bf16, workspace, workspace_bytes, stream);
+}
+
 // Train mode (include/vpr_amd.h, vpr_salad_aggregate_train): the hub model's Dropout layers of score / cluster_features
 // active — on the fused route only, which salad_args() insists on; stages T and A are those of the eval form.
 extern "C" int vpr_salad_aggregate_train(const uint16_t* patch, long long patch_img_stride, const uint16_t* cls,
@@ -818,7 +835,7 @@ extern "C" size_t vpr_salad_f32_workspace_bytes(int B, int n, int C, int m, int 
 static int salad_f32_run(SaladDomain domain, const float* patch, long long patch_img_stride, const float* cls, long long cls_stride,
                          int B, int n, int C, const vpr_salad_weights_f32* w, float dustbin, int m, int l, int t, int hidden,
                          int sinkhorn_iters, float* out_f32, uint16_t* out_bf16, void* workspace, size_t workspace_bytes, void* stream_) {
-  if (domain == SaladDomain::AnyN && sinkhorn_iters < 1) return VPR_ERR_INVALID_ARG;
+  if (domain != SaladDomain::FixedN && sinkhorn_iters < 1) return VPR_ERR_INVALID_ARG;
   if (!patch || !cls || !out_f32 || !workspace || B <= 0 || n < 1 || C <= 0) return VPR_ERR_INVALID_ARG;
   if (!salad_weights_complete(w)) return VPR_ERR_INVALID_ARG;
   if (!salad_in_domain(domain, n, m, l, t, C, hidden)) return VPR_ERR_UNSUPPORTED;
@@ -830,7 +847,7 @@ static int salad_f32_run(SaladDomain domain, const float* patch, long long patch
   if (!salad_f32_plan(B, n, C, m, l, t, hidden, &p)) return VPR_ERR_INVALID_ARG;
   if (workspace_bytes < p.total) return VPR_ERR_WORKSPACE;
   if (sinkhorn_iters < 1) return VPR_ERR_INVALID_ARG;
-  if (n != SA_N && (!aligned4(out_f32) || (reinterpret_cast<uintptr_t>(out_bf16) & 1))) return VPR_ERR_UNSUPPORTED;   // the run-time-n kernel's
+  if (n != SA_N && (!aligned4(out_f32) || (reinterpret_cast<uintptr_t>(out_bf16) & 1))) return VPR_ERR_UNSUPPORTED;   // the run-time-n kernels'
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   char* ws = static_cast<char*>(workspace);
   auto u16 = [&](size_t off) { return reinterpret_cast<uint16_t*>(ws + off); };
@@ -882,5 +899,14 @@ extern "C" int vpr_salad_aggregate_f32_n(const float* patch, long long patch_img
                                          float* out_f32, uint16_t* out_bf16,
                                          void* workspace, size_t workspace_bytes, void* stream) {
   return salad_f32_run(SaladDomain::AnyN, patch, patch_img_stride, cls, cls_stride, B, n, C, w, dustbin, m, l, t, hidden,
+                       sinkhorn_iters, out_f32, out_bf16, workspace, workspace_bytes, stream);
+}
+
+extern "C" int vpr_salad_aggregate_f32_hires(const float* patch, long long patch_img_stride, const float* cls, long long cls_stride,
+                                             int B, int n, int C, const vpr_salad_weights_f32* w, float dustbin,
+                                             int m, int l, int t, int hidden, int sinkhorn_iters,
+                                             float* out_f32, uint16_t* out_bf16,
+                                             void* workspace, size_t workspace_bytes, void* stream) {
+  return salad_f32_run(SaladDomain::HiRes, patch, patch_img_stride, cls, cls_stride, B, n, C, w, dustbin, m, l, t, hidden,
                        sinkhorn_iters, out_f32, out_bf16, workspace, workspace_bytes, stream);
 }

@@ -6,6 +6,7 @@
 #include <type_traits>
 #include "../../include/vpr_amd.h"
 #include "../../include/vpr_amd_salad_anyres.h"
+#include "../../include/vpr_amd_salad_hires.h"
 
 namespace vpr {
 
@@ -65,16 +66,19 @@ int launch_skinny_linear(const uint16_t* in, int ldi, const uint16_t* W, int ldw
                          int mode, uint16_t* out, int ldo, int M, int N, int K, const float* stats_bias,
                          float* row_stats, void* stream);
 
-// ---- SALAD: the one description of what the aggregation is built for (salad.hip, salad_anyres.hip) ------------------
+// ---- SALAD: the one description of what the aggregation is built for (salad.hip, salad_anyres.hip, salad_hires.hip) -
 constexpr int SA_N = 256;   // patch tokens of the fixed-n kernels (224 px at patch 14)
 constexpr int SA_M = 64;    // clusters
 constexpr int SA_L = 128;   // cluster dim
 constexpr int SA_T = 256;   // token dim
-enum class SaladDomain { FixedN, AnyN };       // n == SA_N (include/vpr_amd.h) / SA_M < n <= VPR_SALAD_MAX_N (the any-n extension)
+// n == SA_N (include/vpr_amd.h) / SA_M < n <= VPR_SALAD_MAX_N (the any-n extension) / SA_M < n <= VPR_SALAD_HIRES_MAX_N (the
+// high-resolution extension)
+enum class SaladDomain { FixedN, AnyN, HiRes };
 // The stage-A launchers see neither C nor hidden and leave the defaults.
 inline bool salad_in_domain(SaladDomain d, int n, int m, int l, int t, int C = 64, int hidden = 64) {
   if (m != SA_M || l != SA_L || t != SA_T || (C % 64) || (hidden % 64)) return false;
-  return d == SaladDomain::AnyN ? (n > SA_M && n <= VPR_SALAD_MAX_N) : n == SA_N;
+  if (d == SaladDomain::FixedN) return n == SA_N;
+  return n > SA_M && n <= (d == SaladDomain::AnyN ? VPR_SALAD_MAX_N : VPR_SALAD_HIRES_MAX_N);
 }
 
 int launch_sinkhorn_aggregate(const float* scores, const float* feats, const float* tokfeat,
@@ -86,6 +90,11 @@ int launch_sinkhorn_aggregate(const float* scores, const float* feats, const flo
 int launch_sinkhorn_aggregate_n(const float* scores, const float* feats, const float* tokfeat,
                                 int B, int n, int m, int l, int t, float dustbin, int iters,
                                 float* out_f32, uint16_t* out_bf16, hipStream_t stream);
+
+// salad_hires.hip: stage A for m < n <= VPR_SALAD_HIRES_MAX_N without an image's score matrix in LDS (one dense slab)
+int launch_sinkhorn_aggregate_hires(const float* scores, const float* feats, const float* tokfeat,
+                                    int B, int n, int m, int l, int t, float dustbin, int iters,
+                                    float* out_f32, uint16_t* out_bf16, hipStream_t stream);
 
 // Launch through hipLaunchKernel(), whose return value is THIS launch's status.  (The
 // hipGetLastError() idiom reads a per-thread sticky value that other libraries in the process —

@@ -23,12 +23,13 @@ All forwards are inference-only (torch.no_grad) and require GPU tensors.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import _lib, ops
 from . import torch_ops  # noqa: F401  registers torch.ops.vpr.* (torch.library custom ops over the C ABI)
 from .backbone import DinoV2, SplitTokens
 
@@ -97,6 +98,10 @@ class SaladAggregator(nn.Module):
         split = isinstance(tokens, SplitTokens)
         first = tokens.patch if split else tokens
         f32, n = first.dtype == torch.float32, first.shape[1] - (0 if split else 1)
+        if n > _lib.SALAD_HIRES_MAX_N:  # before any launch: the backbone may have run, the aggregation has no kernel for this grid
+            side = math.isqrt(_lib.SALAD_HIRES_MAX_N)
+            raise ValueError(f"SaladAggregator: {n} patch tokens per image, but the aggregation takes at most {_lib.SALAD_HIRES_MAX_N} "
+                             f"({side} x {side}: {side * 14} px images at patch 14, DINOv2's own position grid)")
         w = (self._packed_f32 or self.pack_f32()) if f32 else (self._packed or self.pack())
         weights = torch_ops.weight_list(w)
         if n == 256 and not f32:        # the n = 256 bf16 ops take their layout as it comes; only they have a token_ready form
@@ -109,9 +114,14 @@ class SaladAggregator(nn.Module):
             patch, cls = tokens.patch.contiguous(), tokens.cls.contiguous()
         elif n == 256:                  # salad_aggregate_f32 takes the pair only
             patch, cls = tokens[:, 1:].contiguous(), tokens[:, 0].contiguous()
-        else:                           # any other grid (include/vpr_amd_salad_anyres.h): the hub layout addressed in place
+        else:                           # any other grid (include/vpr_amd_salad_anyres.h, _hires.h): the hub layout addressed in place
             patch, cls = tokens.contiguous(), None
-        op = _vpr.salad_aggregate_f32 if n == 256 else (_vpr.salad_aggregate_f32_n if f32 else _vpr.salad_aggregate_n)
+        if n == 256:
+            op = _vpr.salad_aggregate_f32
+        elif n <= _lib.SALAD_MAX_N:
+            op = _vpr.salad_aggregate_f32_n if f32 else _vpr.salad_aggregate_n
+        else:                           # 577 .. 1369 tokens (448 / 518 px): the stage A that keeps no score matrix in LDS
+            op = _vpr.salad_aggregate_f32_hires if f32 else _vpr.salad_aggregate_hires
         desc, desc16 = op(patch, cls, weights, w.dustbin, 3)
         return (desc, desc16) if want_bf16 else desc
 
@@ -146,7 +156,8 @@ class SaladAggregator(nn.Module):
 
 class DinoV2Salad(nn.Module):
     """`feature_extractor`: images [B,3,img_size,img_size] -> L2-normalised descriptor [B, 8448].  img_size: any multiple of
-    the patch size whose grid has 65 .. 576 tokens (322 -> 23 x 23 = 529, the resolution DINOv2-SALAD is published at)."""
+    the patch size whose grid has 65 .. 1369 tokens (322 -> 23 x 23 = 529, the resolution DINOv2-SALAD is published at; 448 ->
+    1024; 518 -> 37 x 37 = 1369, DINOv2's own position grid and the largest the aggregation takes)."""
 
     def __init__(self, arch: str = "vit_large", img_size: int = 224):
         super().__init__()

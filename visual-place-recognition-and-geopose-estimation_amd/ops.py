@@ -410,6 +410,32 @@ def salad_aggregate_f32_n(tokens, w: SaladWeightsF32, iters: int = 3,
     return _salad_whole("vpr_salad_aggregate_f32_n", torch.float32, tokens, w, iters, want_bf16)
 
 
+# ---- 65 .. 1369 patch tokens, i.e. up to 518 px (include/vpr_amd_salad_hires.h); the functions above keep their domains ----
+def salad_sinkhorn_aggregate_hires(scores: torch.Tensor, feats: torch.Tensor, tokfeat: torch.Tensor,
+                                   dustbin: float, iters: int = 3,
+                                   want_bf16: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """salad_sinkhorn_aggregate for any n in 65 .. 1369: scores [B,n,m] f32, feats [B,n,l] f32, tokfeat [B,t] f32 -> descriptor
+    (and its bf16 copy).  Always the high-resolution kernel, which recomputes K from the scores on every pass instead of
+    keeping it in LDS, n <= 576 included.  vpr_salad_sinkhorn_aggregate_hires."""
+    return _salad_stage_a("vpr_salad_sinkhorn_aggregate_hires", scores, feats, tokfeat, dustbin, iters, want_bf16)
+
+
+def salad_aggregate_hires(tokens, w: SaladWeights, iters: int = 3,
+                          want_bf16: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The aggregation for any patch-token count n in 65 .. 1369 (448 px = 1024, 518 px = 1369): `tokens` = [B, 1+n, C] bf16
+    (cls first) or a (patch [B,n,C], cls [B,C]) bf16 pair, addressed in place -> (descriptor f32 [B, t+l*m], bf16 copy or
+    None).  n == 256 gives the bits of salad_aggregate_split, any other n <= 576 those of salad_aggregate_n.
+    vpr_salad_aggregate_hires."""
+    return _salad_whole("vpr_salad_aggregate_hires", torch.bfloat16, tokens, w, iters, want_bf16)
+
+
+def salad_aggregate_f32_hires(tokens, w: SaladWeightsF32, iters: int = 3,
+                              want_bf16: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """salad_aggregate_f32 for any n in 65 .. 1369 (f32 tokens, hub layout or pair; f32 weights); n == 256 gives its bits,
+    any other n <= 576 those of salad_aggregate_f32_n.  vpr_salad_aggregate_f32_hires."""
+    return _salad_whole("vpr_salad_aggregate_f32_hires", torch.float32, tokens, w, iters, want_bf16)
+
+
 def _need_rows(t: torch.Tensor, dtype: torch.dtype, name: str) -> None:
     """A 2-D GPU matrix whose rows may be padded (stride(1) == 1, any stride(0)): the leading dimension goes to C."""
     if not isinstance(t, torch.Tensor) or not t.is_cuda:

@@ -7,6 +7,7 @@ that seam, so the HIP hot path is visible to PyTorch's dispatcher like any other
     torch.ops.vpr.salad_aggregate / salad_aggregate_split / salad_aggregate_f32
     torch.ops.vpr.salad_aggregate_train                (training mode: Dropout active in the score / cluster MLPs)
     torch.ops.vpr.salad_aggregate_n / salad_aggregate_f32_n   (any patch-token count 65 .. 576, e.g. 322 px images)
+    torch.ops.vpr.salad_aggregate_hires / salad_aggregate_f32_hires   (65 .. 1369 patch tokens: 448 / 518 px images)
     torch.ops.vpr.knn_topk / knn_topk_fp8 / topk_merge
     torch.ops.vpr.retrieval_pose                       (geopose and first-hit ranks from the merged top-k)
     torch.ops.vpr.query_expand / query_expand_finish   (alpha-QE / DBA: weighted mean of a query and its best rows)
@@ -111,13 +112,34 @@ def salad_aggregate_f32_n(patch: Tensor, cls: Optional[Tensor], weights: List[Te
     return out, out16
 
 
+@torch.library.custom_op("vpr::salad_aggregate_hires", mutates_args=())
+def salad_aggregate_hires(patch: Tensor, cls: Optional[Tensor], weights: List[Tensor], dustbin: float,
+                          sinkhorn_iters: int) -> Tuple[Tensor, Tensor]:
+    """The aggregation for any patch-token count n in 65 .. 1369 (include/vpr_amd_salad_hires.h; 448 px = 1024 tokens, 518 px
+    = 1369).  The layouts of salad_aggregate_n.  n == 256: the bits of salad_aggregate_split; other n <= 576: those of
+    salad_aggregate_n.  vpr_salad_aggregate_hires."""
+    out, out16 = ops.salad_aggregate_hires(patch if cls is None else (patch, cls), _weights(weights, dustbin), sinkhorn_iters, True)
+    return out, out16
+
+
+@torch.library.custom_op("vpr::salad_aggregate_f32_hires", mutates_args=())
+def salad_aggregate_f32_hires(patch: Tensor, cls: Optional[Tensor], weights: List[Tensor], dustbin: float,
+                              sinkhorn_iters: int) -> Tuple[Tensor, Tensor]:
+    """salad_aggregate_hires at the reference's precision: f32 tokens (cls None: [B, 1+n, C], cls first; else the pair) and f32
+    weights.  vpr_salad_aggregate_f32_hires."""
+    out, out16 = ops.salad_aggregate_f32_hires(patch if cls is None else (patch, cls), _weights(weights, dustbin, f32=True),
+                                               sinkhorn_iters, True)
+    return out, out16
+
+
 def _salad_fake(tokens, *rest, **_):
     """Descriptor and its bf16 copy, [B, t + l*m]: the first argument carries B and the device, the weight list the width."""
     B, D = tokens.shape[0], _desc_width(next(a for a in rest if isinstance(a, (list, tuple))))
     return tokens.new_empty((B, D), dtype=torch.float32), tokens.new_empty((B, D), dtype=torch.bfloat16)
 
 
-for _op in (salad_aggregate, salad_aggregate_split, salad_aggregate_f32, salad_aggregate_train, salad_aggregate_n, salad_aggregate_f32_n):
+for _op in (salad_aggregate, salad_aggregate_split, salad_aggregate_f32, salad_aggregate_train, salad_aggregate_n, salad_aggregate_f32_n,
+            salad_aggregate_hires, salad_aggregate_f32_hires):
     _op.register_fake(_salad_fake)
 
 
@@ -321,4 +343,4 @@ def _(X, Y, order, batch_size, W1, b1, W2, b2, m, v, first_step, lr, beta1, beta
 
 OPS = ("head_train_epoch", "head_train_epoch_dropout", "salad_aggregate", "salad_aggregate_split", "salad_aggregate_f32", "salad_aggregate_train", "knn_topk", "knn_topk_fp8", "quantize_fp8_rows",
        "topk_merge", "pose_head", "ln_meanpool_head", "retrieval_pose", "query_expand", "query_expand_finish", "project_rows",
-       "rerank_rows", "salad_aggregate_n", "salad_aggregate_f32_n")
+       "rerank_rows", "salad_aggregate_n", "salad_aggregate_f32_n", "salad_aggregate_hires", "salad_aggregate_f32_hires")
