@@ -200,6 +200,17 @@ SALAD_HIRES_PROTOTYPES = {
     "vpr_salad_aggregate_f32_hires": SALAD_ANYRES_PROTOTYPES["vpr_salad_aggregate_f32_n"],
 }
 
+# include/vpr_amd_local.h, the eighth table: local-feature re-ranking by mutual-nearest-neighbour patch matches
+LOCAL_MAX_N, LOCAL_MAX_L, LOCAL_MAX_KC = 256, 256, 128      # VPR_LOCAL_MAX_N, VPR_LOCAL_MAX_L, VPR_LOCAL_MAX_KC
+LOCAL_SUM_ROUNDINGS = 10                                    # VPR_LOCAL_SUM_ROUNDINGS: L_sum of the score
+LOCAL_PROTOTYPES = {
+    "vpr_local_workspace_bytes": (c_size_t, [c_int] * 2),                   # B kc
+    # q_local n_q | idx B kc | g_local n_g l n_local index_base min_sim | k_out vals_out idx_out matches_out |
+    # pair_score pair_matches row_nn col_nn | workspace workspace_bytes | stream
+    "vpr_local_rerank": (c_int, [_P, c_int, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P, _P, _P,
+                                 _P, _P, _P, _P, _P, c_size_t, _P]),
+}
+
 
 def rerank_roundings(D: int, rows_are_f32: bool) -> int:
     """VPR_RERANK_ROUNDINGS: L of the fine score, the roundings on the longest path from a product to the result."""
@@ -225,7 +236,8 @@ def lib() -> ctypes.CDLL:
         for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(EXTENSION_PROTOTYPES.items())
                                           + list(EXPAND_PROTOTYPES.items()) + list(PROJECT_PROTOTYPES.items())
                                           + list(RERANK_PROTOTYPES.items()) + list(SALAD_STAGES_PROTOTYPES.items())
-                                          + list(SALAD_ANYRES_PROTOTYPES.items()) + list(SALAD_HIRES_PROTOTYPES.items())):
+                                          + list(SALAD_ANYRES_PROTOTYPES.items()) + list(SALAD_HIRES_PROTOTYPES.items())
+                                          + list(LOCAL_PROTOTYPES.items())):
             fn = getattr(handle, name)   # AttributeError if a declared symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

@@ -4,8 +4,8 @@
 // right after the staging barrier, before any row access.  The query is staged once per workgroup as f32 in LDS; a lane then
 // requests up to RR_NJ 16-byte chunks of its row before it adds the first (the row's address is wave-uniform, its chunks are
 // lane + 64 u), so the scattered row reads overlap while the order of the sum stays the one the header states.
-// order: one 128-thread workgroup per query; thread j builds candidate j's key (the merge key of vpr_common.h; a NaN score
-// gets a key below every numeric one and above the padding), counts the keys ahead of it and writes it if that rank < k_out.
+// order: one 128-thread workgroup per query; thread j ranks candidate j (order_rank of vpr_common.h, shared with
+// local_match.hip) and writes it if that rank < k_out.
 #include <math.h>
 #include "vpr_common.h"
 #include "vpr_internal.h"
@@ -17,8 +17,8 @@ constexpr int RR_WAVES = 8;                       // candidates (= waves) per sc
 constexpr int RR_THREADS = RR_WAVES * WAVE;
 constexpr int RR_NJ = 8;                          // row chunks a lane has in flight
 constexpr int RR_MAX_KC = VPR_RERANK_MAX_KC;      // = the order kernel's workgroup: thread j ranks candidate j
+static_assert(RR_MAX_KC == ORDER_MAX_KC, "order_rank is written for one thread per candidate");
 constexpr int RR_MAX_D = VPR_RERANK_MAX_D;        // 4 * D bytes of LDS <= 64 KB
-constexpr unsigned long long RR_KEY_NAN_HI = 1ull << 32;   // above KEY_DEAD, below orderable(-inf) = 0x007fffff
 
 // a[e] = fmaf(q[e], row[e], a[e]) over the E elements of one 16-byte row chunk; q is the chunk's E staged f32 values
 template <bool ROWS_F32>
@@ -98,30 +98,11 @@ __global__ __launch_bounds__(RR_MAX_KC) void rerank_order_kernel(
     const float* __restrict__ scores, const int32_t* __restrict__ idx, int kc, int n_local, int index_base, int k_out,
     float* __restrict__ vals_out, int32_t* __restrict__ idx_out) {
   __shared__ unsigned long long s_key[RR_MAX_KC];
-  const int j = threadIdx.x;
   const long long b = blockIdx.x;
-  unsigned long long key = KEY_DEAD;
-  float val = -INFINITY;
-  int id = -1;
-  if (j < kc) {
-    const int cand = idx[b * kc + j];
-    long long r;
-    if (shard_row(cand, n_local, index_base, r)) {                    // only a live candidate's score was written
-      const float s = scores[b * kc + j];
-      id = cand;
-      if (isnan(s)) key = RR_KEY_NAN_HI | (uint32_t)(0x7fffffff - cand);
-      else { key = make_key(s, cand); val = s; }
-    }
-  }
-  s_key[j] = key;
-  __syncthreads();
-  if (j >= kc) return;
-  int rank = 0;
-  for (int i = 0; i < kc; ++i) {                                      // s_key[i]: the same address for every thread
-    const unsigned long long o = s_key[i];
-    rank += (o > key || (o == key && i < j)) ? 1 : 0;
-  }
-  if (rank < k_out) {
+  float val;
+  int id;
+  const int rank = order_rank(scores, idx, b, kc, n_local, index_base, s_key, val, id);
+  if (rank >= 0 && rank < k_out) {
     vals_out[b * k_out + rank] = val;
     idx_out[b * k_out + rank] = id;
   }

@@ -87,7 +87,7 @@ __device__ __forceinline__ float row16_sum(float v) {
 
 // ---- the packed top-k key ---------------------------------------------------------------------------------
 // Key order: value desc, index asc (packed into one u64 so a max-reduction does both).  Shared by the kNN selects, the
-// shard merge (knn.hip) and the re-rank order kernel (rerank.hip).
+// shard merge (knn.hip) and the re-rank order stage (order_rank below).
 __device__ __forceinline__ uint32_t f32_orderable(float f) {
   const uint32_t u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -261,6 +261,41 @@ __device__ __forceinline__ uint2 pack_bf16x4(f32x4 v) {
 __device__ __forceinline__ bool shard_row(int id, int n_local, int index_base, long long& r) {
   r = (long long)id - index_base;
   return r >= 0 && r < n_local;
+}
+
+// ---- the order stage of a re-rank (rerank.hip, local_match.hip) ------------------------------------------------------
+// One workgroup of ORDER_MAX_KC threads per query b; thread j builds candidate j's key from scores[b, j] and idx[b, j] (the
+// merge key above; a NaN score gets a key below every numeric one and above the padding; a candidate the shard does not own
+// is KEY_DEAD, and its score is not read), and counts the keys ahead of it (kc^2 comparisons per query; equal keys by
+// position).  Returns that rank, or -1 for a thread past kc; (val, id) is the entry to write at the rank: (score, index),
+// (-inf, index) for a NaN score, (-inf, -1) for a candidate that is not live.  One barrier; s_key is LDS.
+constexpr int ORDER_MAX_KC = 128;
+constexpr unsigned long long KEY_NAN_HI = 1ull << 32;   // above KEY_DEAD, below orderable(-inf) = 0x007fffff
+__device__ __forceinline__ int order_rank(const float* __restrict__ scores, const int32_t* __restrict__ idx, long long b, int kc,
+                                          int n_local, int index_base, unsigned long long* s_key, float& val, int& id) {
+  const int j = threadIdx.x;
+  unsigned long long key = KEY_DEAD;
+  val = -INFINITY;
+  id = -1;
+  if (j < kc) {
+    const int cand = idx[b * kc + j];
+    long long r;
+    if (shard_row(cand, n_local, index_base, r)) {                    // only a live candidate's score was written
+      const float s = scores[b * kc + j];
+      id = cand;
+      if (isnan(s)) key = KEY_NAN_HI | (uint32_t)(0x7fffffff - cand);
+      else { key = make_key(s, cand); val = s; }
+    }
+  }
+  s_key[j] = key;
+  __syncthreads();
+  if (j >= kc) return -1;
+  int rank = 0;
+  for (int i = 0; i < kc; ++i) {                                      // s_key[i]: the same address for every thread
+    const unsigned long long o = s_key[i];
+    rank += (o > key || (o == key && i < j)) ? 1 : 0;
+  }
+  return rank;
 }
 
 // The sums of a workgroup's NWAVES waves (wave_total = wave_sum(...) of the caller's value) added in ascending wave order

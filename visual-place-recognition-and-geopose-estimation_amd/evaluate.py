@@ -316,7 +316,7 @@ def _check_grid(extractor, image_size: int) -> None:
 @torch.no_grad()
 def build_gallery_from_images(extractor: DinoV2Salad, csv_path: str, image_dir: str, out_dir: str, *, fp8: bool = False,
                               batch_size: int = 64, device: str = "cuda", image_size: int = 224, graph: bool = True,
-                              projection=None, whiten: bool = True, keep_fine: bool = False) -> int:
+                              projection=None, whiten: bool = True, keep_fine: bool = False, keep_local: bool = False) -> int:
     """labels CSV (`filename,timestamp,latitude,longitude,angle,Region_ID`, cleaned_dataset_files/labels_train.csv:1) +
     images -> on-disk gallery (gallery.save_gallery: bf16 rows, or e4m3 rows + per-row scales with fp8=True).
     Preprocessing = the DINOv2+SALAD validation transform (dinov2salad_validation.py:18-22).  Returns the row count.
@@ -325,7 +325,10 @@ def build_gallery_from_images(extractor: DinoV2Salad, csv_path: str, image_dir: 
     descriptors (projection.fit_projection) — the rows are projected to d columns on the device (gallery.project_gallery)
     and the projection is saved with the gallery, where calculate_retrieval_scores finds it.
     keep_fine: an e4m3 or projected gallery also keeps the bf16 full descriptors (fine_descriptors.npy), the second tier of
-    calculate_retrieval_scores(rerank=); a plain bf16 gallery's rows are those descriptors already, and nothing is added."""
+    calculate_retrieval_scores(rerank=); a plain bf16 gallery's rows are those descriptors already, and nothing is added.
+    keep_local: the gallery also keeps every image's local features (local_features.npy: [N, n, 128] bf16 from the same
+    backbone pass, DinoV2Salad.features(want_local=True); at most 256 patch tokens), what
+    calculate_retrieval_scores(local_rerank=) matches against."""
     from . import gallery as G, ops
     _check_grid(extractor, image_size)
     dev = torch.device(device)
@@ -334,9 +337,20 @@ def build_gallery_from_images(extractor: DinoV2Salad, csv_path: str, image_dir: 
     names = df["filename"].tolist()
     prep = ResizeNormalize(image_size, "bilinear", HALF_MEAN, HALF_STD, torch.bfloat16)
     desc = torch.empty((len(names), 8448), dtype=torch.float32, device=dev)
-    fwd = GraphedForward(extractor) if graph and dev.type == "cuda" else extractor
+    local = None
+    if keep_local:
+        features = lambda x: extractor.features(x, want_local=True)
+        local = torch.empty((len(names), extractor.backbone.num_patches, extractor.aggregator.cluster_dim), dtype=torch.bfloat16,
+                            device=dev)
+        fwd = GraphedForward(features, module=extractor) if graph and dev.type == "cuda" else features
+    else:
+        fwd = GraphedForward(extractor) if graph and dev.type == "cuda" else extractor
     for idxs, u8 in _batches(image_dir, names, batch_size, dev):
-        desc[torch.tensor(idxs, device=dev)] = fwd(prep(u8))
+        sel = torch.tensor(idxs, device=dev)
+        if keep_local:
+            desc[sel], local[sel] = fwd(prep(u8))
+        else:
+            desc[sel] = fwd(prep(u8))
     labels = df[list(G.LABEL_COLUMNS)].to_numpy(dtype=np.float64)
     fine = desc.to(torch.bfloat16) if keep_fine and (fp8 or projection is not None) else None
     if projection is not None:
@@ -345,12 +359,12 @@ def build_gallery_from_images(extractor: DinoV2Salad, csv_path: str, image_dir: 
         if isinstance(projection, int):
             projection = fit_projection(d16, projection, whiten=whiten)
         rows, scales = G.project_gallery(d16, projection, fp8=fp8)
-        G.save_gallery(out_dir, rows, labels, scales=scales, filenames=names, projection=projection, fine=fine)
+        G.save_gallery(out_dir, rows, labels, scales=scales, filenames=names, projection=projection, fine=fine, local=local)
     elif fp8:
         rows, scales = ops.quantize_fp8_rows(desc)
-        G.save_gallery(out_dir, rows, labels, scales=scales, filenames=names, fine=fine)
+        G.save_gallery(out_dir, rows, labels, scales=scales, filenames=names, fine=fine, local=local)
     else:
-        G.save_gallery(out_dir, desc.to(torch.bfloat16), labels, filenames=names)
+        G.save_gallery(out_dir, desc.to(torch.bfloat16), labels, filenames=names, local=local)
     return len(names)
 
 
@@ -392,7 +406,8 @@ def retrieval_metrics(vals: torch.Tensor, idx: torch.Tensor, labels: np.ndarray,
 def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv_path: str, image_dir: str, *, k: int = 10,
                                tau: float = 25.0, mode: str = "top1", batch_size: int = 64, device: str = "cuda", graph: bool = True,
                                image_size: int = 224, rank: int = 0, world: int = 1, group=None, verbose: bool = True,
-                               on_device: bool = False, query_expansion=None, rerank: Optional[int] = None) -> dict:
+                               on_device: bool = False, query_expansion=None, rerank: Optional[int] = None,
+                               local_rerank: Optional[int] = None, min_sim: float = 0.0) -> dict:
     """Validation split through descriptor -> sharded cosine top-k -> label transfer:
       pose      (lat, lon, angle) of the best match, or the softmax-weighted mean of the k matches (gallery.label_transfer);
       final_loss on lat/lon with the validation scripts' formula (dinov2salad_validation.py:101), MAAE on the angle
@@ -408,14 +423,23 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
     A gallery saved with a projection (projection.npz) has every query batch projected on the device before its search.
     rerank (kc): two-tier retrieval — every (last) search yields kc coarse candidates, re-ranked to k on the gallery's fine
     descriptors (fine_descriptors.npy, build_gallery_from_images(keep_fine=True); a plain bf16 gallery is its own fine tier)
-    with the batch's bf16 descriptors as fine queries (ShardedGallery.search_reranked); topk_scores are then fine scores."""
+    with the batch's bf16 descriptors as fine queries (ShardedGallery.search_reranked); topk_scores are then fine scores.
+    local_rerank (kc): local-feature re-ranking — every search yields kc coarse candidates, re-ranked to k by the mutual-
+    nearest-neighbour matches (similarity >= min_sim) between the query's and the candidates' patch features
+    (local_features.npy, build_gallery_from_images(keep_local=True); ShardedGallery.search_local_reranked); topk_scores are
+    then local scores.  Not together with rerank or query_expansion."""
     from . import gallery as G
     from .retrieval import ShardedGallery
     _check_grid(extractor, image_size)
     dev = torch.device(device)
     extractor = extractor.to(dev).to(torch.bfloat16).eval()
+    if local_rerank is not None and (rerank is not None or query_expansion is not None):
+        raise ValueError("calculate_retrieval_scores: local_rerank combines neither with rerank nor with query_expansion")
+    if local_rerank is not None and not os.path.exists(os.path.join(gallery_dir, G.LOCAL_FILE)):
+        raise ValueError(f"local_rerank: {gallery_dir} has no {G.LOCAL_FILE} (build_gallery_from_images(keep_local=True))")
     has_fine = os.path.exists(os.path.join(gallery_dir, G.FINE_FILE))
-    shard = G.load_gallery_shard(gallery_dir, dev, rank, world, load_fine=rerank is not None and has_fine)
+    shard = G.load_gallery_shard(gallery_dir, dev, rank, world, load_fine=rerank is not None and has_fine,
+                                 load_local=local_rerank is not None)
     fine = shard.fine
     if rerank is not None and fine is None:
         if shard.dtype != "bf16" or shard.projection is not None:
@@ -423,18 +447,20 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
         fine = shard.rows
     # offline evaluation: unconditionally exact neighbours (queries the device certificate flags are re-run on f64 scores)
     sg = ShardedGallery(shard.rows, shard.n_total, rank, world, group=group, scales=shard.scales, exact_fallback=True,
-                        projection=shard.projection, fine_rows=fine)
+                        projection=shard.projection, fine_rows=fine, local_feats=shard.local)
     df = _existing_rows(val_csv_path, image_dir)
     names = df["filename"].tolist()
     prep = ResizeNormalize(image_size, "bilinear", HALF_MEAN, HALF_STD, torch.bfloat16)
     kk = min(k, shard.n_total)
     vals = torch.empty((len(names), kk), dtype=torch.float32, device=dev)
     idx = torch.empty((len(names), kk), dtype=torch.int32, device=dev)
-    features = lambda x: extractor.features(x, want_bf16=True)
+    features = lambda x: extractor.features(x, want_bf16=True, want_local=local_rerank is not None)
     fwd = GraphedForward(features, module=extractor) if graph and dev.type == "cuda" else features
     two_tier = {} if rerank is None else {"rerank": int(rerank)}     # named only when asked for
     for idxs, u8 in _batches(image_dir, names, batch_size, dev):
-        _, d16 = fwd(prep(u8))
+        _, d16, *feats = fwd(prep(u8))
+        if local_rerank is not None:
+            two_tier = {"local_rerank": int(local_rerank), "q_local_feats": feats[0], "min_sim": float(min_sim)}
         v, i = sg.search_local_queries(d16, kk, query_expansion, **two_tier)
         sel = torch.tensor(idxs, device=dev)
         vals[sel], idx[sel] = v, i

@@ -12,6 +12,9 @@ On-disk format (a directory; every array is a plain .npy so shards can be memory
                        projected width.  A directory without it loads as ever.
   fine_descriptors.npy (optional) [N, D_fine] uint16 (bf16 bit patterns): the full-precision descriptors the rows were made
                        from, the second tier of ShardedGallery.search_reranked.  A directory without it loads as ever.
+  local_features.npy   (optional) [N, n, l] uint16 (bf16 bit patterns): every image's n L2-normalised patch descriptors of
+                       width l (SaladAggregator.local_features), what ShardedGallery.search_local_reranked matches the
+                       queries' patches against.  A directory without it loads as ever.
 Rank r of R loads rows [N*r/R, N*(r+1)/R) only.
 """
 from __future__ import annotations
@@ -31,6 +34,7 @@ from .retrieval import ShardedGallery, shard_bounds
 LABEL_COLUMNS = ("latitude", "longitude", "angle", "Region_ID")
 PROJECTION_FILE = "projection.npz"
 FINE_FILE = "fine_descriptors.npy"
+LOCAL_FILE = "local_features.npy"
 
 
 @dataclass
@@ -43,16 +47,20 @@ class GalleryShard:
     dtype: str
     labels_dev: Optional[torch.Tensor] = None   # [N, 4] float64 on the GPU: the same table for ops.retrieval_pose (device_labels)
     projection: Optional["DescriptorProjection"] = None   # what the rows went through (projection.npz), or None
+    local: Optional[torch.Tensor] = None  # [n_local, n, l] bf16 on the GPU (local_features.npy; load_local), or None
     fine: Optional[torch.Tensor] = None   # [n_local, D_fine] bf16 on the GPU (fine_descriptors.npy; load_fine), or None
 
 
 def save_gallery(path: str, descriptors: torch.Tensor, labels: np.ndarray, scales: Optional[torch.Tensor] = None,
                  filenames: Optional[Sequence[str]] = None, projection: Optional[DescriptorProjection] = None,
-                 fine: Optional[torch.Tensor] = None) -> None:
+                 fine: Optional[torch.Tensor] = None, local: Optional[torch.Tensor] = None) -> None:
     """descriptors: [N,D] torch.bfloat16 (bf16 gallery) or torch.uint8 (+ scales: fp8 gallery).
     projection: the DescriptorProjection the rows went through (project_gallery); written as projection.npz.
-    fine: [N, D_fine] torch.bfloat16, the full-precision descriptors of the same rows; written as fine_descriptors.npy."""
+    fine: [N, D_fine] torch.bfloat16, the full-precision descriptors of the same rows; written as fine_descriptors.npy.
+    local: [N, n, l] torch.bfloat16, the local features of the same rows; written as local_features.npy."""
     os.makedirs(path, exist_ok=True)
+    if local is not None and (local.dim() != 3 or local.dtype != torch.bfloat16 or local.shape[0] != descriptors.shape[0]):
+        raise ValueError(f"local must be bfloat16 [N, n, l] with one image per descriptor ({descriptors.shape[0]})")
     if fine is not None and (fine.dim() != 2 or fine.dtype != torch.bfloat16 or fine.shape[0] != descriptors.shape[0]):
         raise ValueError(f"fine must be bfloat16 [N, D_fine] with one row per descriptor ({descriptors.shape[0]})")
     if projection is not None and projection.d != descriptors.shape[1]:
@@ -88,6 +96,11 @@ def save_gallery(path: str, descriptors: torch.Tensor, labels: np.ndarray, scale
         np.save(fine_path, fine.detach().cpu().contiguous().view(torch.uint16).numpy())
     elif os.path.exists(fine_path):            # nor do the old fine rows
         os.remove(fine_path)
+    local_path = os.path.join(path, LOCAL_FILE)
+    if local is not None:
+        np.save(local_path, local.detach().cpu().contiguous().view(torch.uint16).numpy())
+    elif os.path.exists(local_path):           # nor the old local features
+        os.remove(local_path)
 
 
 def device_labels(labels: np.ndarray, device: torch.device) -> torch.Tensor:
@@ -103,9 +116,10 @@ _device_labels = device_labels       # load_gallery_shard's flag of the same nam
 
 
 def load_gallery_shard(path: str, device: torch.device, rank: int = 0, world: int = 1,
-                       device_labels: bool = False, load_fine: bool = False) -> GalleryShard:
+                       device_labels: bool = False, load_fine: bool = False, load_local: bool = False) -> GalleryShard:
     """device_labels: also place the label table on `device` (GalleryShard.labels_dev), for the on-device retrieval pose.
-    load_fine: also read this rank's slice of fine_descriptors.npy (GalleryShard.fine); the file must then exist."""
+    load_fine: also read this rank's slice of fine_descriptors.npy (GalleryShard.fine); the file must then exist.
+    load_local: also read this rank's slice of local_features.npy (GalleryShard.local); the file must then exist."""
     with open(os.path.join(path, "meta.json")) as f:
         meta = json.load(f)
     if meta.get("version") != 1:
@@ -132,7 +146,16 @@ def load_gallery_shard(path: str, device: torch.device, rank: int = 0, world: in
         if arr.shape[0] != meta["n"]:
             raise ValueError(f"{FINE_FILE} has {arr.shape[0]} rows, the gallery {meta['n']}")
         fine = torch.from_numpy(np.array(arr[lo:hi])).to(device).view(torch.bfloat16)
-    return GalleryShard(rows, scales, labels, meta["n"], lo, meta["dtype"], labels_dev, projection, fine)
+    local = None
+    if load_local:
+        local_path = os.path.join(path, LOCAL_FILE)
+        if not os.path.exists(local_path):
+            raise ValueError(f"load_local: {path} has no {LOCAL_FILE}")
+        arr = np.load(local_path, mmap_mode="r")
+        if arr.ndim != 3 or arr.shape[0] != meta["n"]:
+            raise ValueError(f"{LOCAL_FILE} is {arr.shape}, the gallery has {meta['n']} rows")
+        local = torch.from_numpy(np.array(arr[lo:hi])).to(device).view(torch.bfloat16)
+    return GalleryShard(rows, scales, labels, meta["n"], lo, meta["dtype"], labels_dev, projection, local=local, fine=fine)
 
 
 def labels_from_csv(csv_path: str) -> Tuple[np.ndarray, List[str]]:
@@ -279,4 +302,4 @@ class GraphedLocalTopK:
 def sharded_gallery_from(shard: GalleryShard, rank: int = 0, world: int = 1, group=None) -> ShardedGallery:
     """A loaded shard (bf16 rows, or e4m3 bytes + per-row scales) as the distributed search object."""
     return ShardedGallery(shard.rows, shard.n_total, rank, world, group=group, scales=shard.scales,
-                          projection=shard.projection, fine_rows=shard.fine)
+                          projection=shard.projection, fine_rows=shard.fine, local_feats=shard.local)

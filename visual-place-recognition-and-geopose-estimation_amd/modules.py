@@ -125,6 +125,34 @@ class SaladAggregator(nn.Module):
         desc, desc16 = op(patch, cls, weights, w.dustbin, 3)
         return (desc, desc16) if want_bf16 else desc
 
+    @torch.no_grad()
+    def local_features(self, tokens: torch.Tensor) -> torch.Tensor:
+        """Per-patch local descriptors for local-feature re-ranking (include/vpr_amd_local.h): patch tokens [B, n, C] (no cls
+        row; bf16 or f32) -> [B, n, cluster_dim] bf16, the cluster_features MLP of every patch in eval arithmetic (its Dropout
+        is never applied), L2-normalised per patch in f32; an all-zero output row stays zero.  bf16 tokens on the GPU run the
+        two layers on the MFMA GEMM (bf16 operands and hidden layer, f32 accumulation); anything else runs them in f32 torch
+        with the f32 weights.  n > 256 (322 px and up) raises before any launch: the matching kernel holds one image's
+        patches in a single tile set."""
+        if tokens.dim() != 3 or tokens.shape[2] != self.num_channels:
+            raise ValueError(f"SaladAggregator.local_features: tokens must be [B, n, {self.num_channels}] patch tokens, "
+                             f"got {tuple(tokens.shape)}")
+        B, n, C = tokens.shape
+        if n > _lib.LOCAL_MAX_N:
+            raise ValueError(f"SaladAggregator.local_features: {n} patch tokens per image, but local-feature re-ranking takes at "
+                             f"most {_lib.LOCAL_MAX_N} (224 px images at patch 14)")
+        x = tokens.reshape(B * n, C)
+        if x.is_cuda and x.dtype == torch.bfloat16:
+            w = self._packed or self.pack()
+            h = ops.gemm_nt_bf16(x.contiguous(), w.w1_sc[self.hidden:], w.b1_sc[self.hidden:], relu=True, out_dtype=torch.bfloat16)
+            f = ops.gemm_nt_bf16(h, w.w2_c, w.b2_c)
+        else:
+            w = self._packed_f32 or self.pack_f32()
+            h = torch.relu(x.float() @ w.w1_sc[self.hidden:].T + w.b1_sc[self.hidden:])
+            f = h @ w.w2_c.T + w.b2_c
+        norm = f.norm(dim=1, keepdim=True)
+        f = torch.where(norm > 0, f / norm, torch.zeros_like(f))
+        return f.to(torch.bfloat16).view(B, n, self.cluster_dim)
+
     def dropout_p(self) -> float:
         """p of the two Dropout layers (score[1], cluster_features[1]); the fused kernel draws one mask rate for both."""
         ps, pc = float(self.score[1].p), float(self.cluster_features[1].p)
@@ -173,11 +201,25 @@ class DinoV2Salad(nn.Module):
         return t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16)
 
     @torch.no_grad()
-    def features(self, x: torch.Tensor, want_bf16: bool = False, events: Optional[list] = None):
+    def features(self, x: torch.Tensor, want_bf16: bool = False, events: Optional[list] = None, want_local: bool = False):
         """images -> descriptor (and its bf16 copy): backbone tokens stay in the layout the backbone
         computed them in (SplitTokens on the HIP path), no re-layout copy before SALAD.
         events: a list -> a (start, end) pair of timing events around the aggregation on the current stream is appended
-        (bench.py: the SALAD stage as the step runs it, token MLP on the backbone's cls-row stream)."""
+        (bench.py: the SALAD stage as the step runs it, token MLP on the backbone's cls-row stream).
+        want_local: the result gains a last element, the local features [B, n, 128] bf16 of the same backbone pass
+        (SaladAggregator.local_features; at most 256 patch tokens, ValueError before the backbone runs otherwise).  The
+        descriptor is the default call's, bit for bit."""
+        if want_local:
+            if self.backbone.num_patches > _lib.LOCAL_MAX_N:
+                raise ValueError(f"DinoV2Salad.features(want_local=True): {self.backbone.num_patches} patch tokens per image, but "
+                                 f"local-feature re-ranking takes at most {_lib.LOCAL_MAX_N} (224 px images at patch 14)")
+            keep: list = []
+            out = self._features(x, want_bf16, events, keep)
+            local = self.aggregator.local_features(keep[0])
+            return (*out, local) if want_bf16 else (out, local)
+        return self._features(x, want_bf16, events)
+
+    def _features(self, x: torch.Tensor, want_bf16: bool, events: Optional[list], keep_patch: Optional[list] = None):
         # the token stage on the cls-row stream exists for 256 tokens only; any other grid runs the token MLP in the aggregation
         hook = self.token_on_cls_stream and self.backbone.num_patches == 256
         self.backbone.cls_tail_hook = self.aggregator.token_stage if hook else None
@@ -187,6 +229,8 @@ class DinoV2Salad(nn.Module):
             self.backbone.cls_tail_hook = None
         if t.patch.dtype not in (torch.bfloat16, torch.float32):
             t = SplitTokens(t.patch.to(torch.bfloat16), t.cls.to(torch.bfloat16))
+        if keep_patch is not None:
+            keep_patch.append(t.patch)
         if events is None:
             return self.aggregator(t, want_bf16=want_bf16)      # f32 tokens (an f32 model) take the f32-accurate aggregation
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

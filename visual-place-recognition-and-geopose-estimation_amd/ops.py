@@ -865,6 +865,75 @@ def rerank_rows(q: torch.Tensor, idx: torch.Tensor, rows: torch.Tensor, index_ba
     return vals, out
 
 
+def _local_check(what: str, q_local, idx, g_local, k) -> int:
+    for t, name in ((q_local, "q_local"), (g_local, "g_local")):
+        _need(t, torch.bfloat16, name, 3)
+    _need(idx, torch.int32, "idx", 2)
+    if idx.shape[0] != q_local.shape[0]:
+        raise RuntimeError(f"{what}: q_local and idx disagree on B")
+    if g_local.shape[2] != q_local.shape[2]:
+        raise RuntimeError(f"{what}: q_local and g_local disagree on l")
+    if idx.device != q_local.device or g_local.device != q_local.device:
+        raise RuntimeError(f"{what}: q_local, idx and g_local must live on one device")
+    for t, name in ((q_local, "q_local"), (g_local, "g_local")):
+        if not 1 <= t.shape[1] <= _lib.LOCAL_MAX_N:
+            raise RuntimeError(f"{what}: {name} must hold 1..{_lib.LOCAL_MAX_N} patches per image, got {t.shape[1]}")
+    l = q_local.shape[2]
+    if l % 32 or not 32 <= l <= _lib.LOCAL_MAX_L:
+        raise RuntimeError(f"{what}: the feature width must be a multiple of 32 in 32..{_lib.LOCAL_MAX_L}, got {l}")
+    kc = idx.shape[1]
+    if not 1 <= kc <= _lib.LOCAL_MAX_KC:
+        raise RuntimeError(f"{what}: idx must hold 1..{_lib.LOCAL_MAX_KC} candidates per query, got {kc}")
+    k = kc if k is None else int(k)
+    if not 1 <= k <= kc:
+        raise RuntimeError(f"{what}: k must be in 1..kc (kc = {kc})")
+    return k
+
+
+class LocalRerankDebug(NamedTuple):
+    """The optional outputs of vpr_local_rerank, candidate order: pair_score f32 / pair_matches int32 [B, kc] ((-inf, 0) for a
+    candidate the shard does not own), row_nn int32 [B, kc, n_q] / col_nn int32 [B, kc, n_g] (-1: none, or not owned)."""
+    pair_score: torch.Tensor
+    pair_matches: torch.Tensor
+    row_nn: torch.Tensor
+    col_nn: torch.Tensor
+
+
+def local_rerank(q_local: torch.Tensor, idx: torch.Tensor, g_local: torch.Tensor, index_base: int = 0, k: Optional[int] = None,
+                 min_sim: float = 0.0, ws: Optional[torch.Tensor] = None, debug: bool = False):
+    """Local-feature re-ranking (include/vpr_amd_local.h): q_local bf16 [B, n_q, l], idx int32 [B, kc] (kc <= 128) the candidates
+    of a search as global rows, g_local = this shard's local features bf16 [n_local, n_g, l], owning global rows index_base ...
+    Returns (vals f32 [B, k], idx int32 [B, k], matches int32 [B, k]): the k best (None: all kc) of the candidates this shard
+    owns by the sum of the similarities of their mutual-nearest-neighbour patch pairs of similarity >= min_sim, (score desc,
+    index asc); everything else is never dereferenced and comes back as (-inf, -1, 0) at the tail.  debug=True: a fourth
+    element, LocalRerankDebug.  ws: a byte buffer of vpr_local_workspace_bytes(B, kc); None: the current stream's cached one."""
+    k = _local_check("local_rerank", q_local, idx, g_local, k)
+    min_sim = float(min_sim)
+    if min_sim != min_sim:
+        raise RuntimeError("local_rerank: min_sim must be a number")
+    B, n_q, l = q_local.shape
+    n_local, n_g = g_local.shape[:2]
+    kc = idx.shape[1]
+    dev = q_local.device
+    need = _lib.lib().vpr_local_workspace_bytes(B, kc)
+    if ws is None:
+        ws = workspace("local_rerank", need, dev)
+    else:
+        _need(ws, torch.uint8, "ws", 1)
+    vals = torch.empty((B, k), dtype=torch.float32, device=dev)
+    out = torch.empty((B, k), dtype=torch.int32, device=dev)
+    matches = torch.empty((B, k), dtype=torch.int32, device=dev)
+    dbg = None
+    if debug:
+        dbg = LocalRerankDebug(torch.empty((B, kc), dtype=torch.float32, device=dev), torch.empty((B, kc), dtype=torch.int32, device=dev),
+                               torch.empty((B, kc, n_q), dtype=torch.int32, device=dev),
+                               torch.empty((B, kc, n_g), dtype=torch.int32, device=dev))
+    if B:
+        _call("vpr_local_rerank", _ptr(q_local), n_q, _ptr(idx), B, kc, _ptr(g_local), n_g, l, n_local, int(index_base), min_sim,
+              k, _ptr(vals), _ptr(out), _ptr(matches), *[_ptr(t) for t in (dbg or (None,) * 4)], _ptr(ws), ws.numel(), _stream())
+    return (vals, out, matches, dbg) if debug else (vals, out, matches)
+
+
 PROJECT_CHUNK_ROWS = 65536      # rows per vpr_project_rows call: bounds the workspace for million-row inputs
 
 

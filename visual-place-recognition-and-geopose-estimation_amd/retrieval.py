@@ -75,6 +75,11 @@ class HipEngine:
             return torch.ops.vpr.rerank_rows(q, idx, rows, index_base, k)
         return ops.rerank_rows(q, idx, rows, index_base, k, ws)
 
+    def local_rerank(self, q_local_feats, idx, local_feats, index_base, k, min_sim=0.0):
+        """The k best of the candidates idx [B, kc] this shard owns, by mutual-nearest-neighbour patch matches
+        (vpr_local_rerank): (vals, idx, matches) [B, k]."""
+        return torch.ops.vpr.local_rerank(q_local_feats, idx, local_feats, index_base, k, min_sim)
+
 
 def pose_labels(labels, device) -> torch.Tensor:
     """The label table for torch.ops.vpr.retrieval_pose: a [N, 4] float64 tensor on `device` (gallery.device_labels /
@@ -135,7 +140,7 @@ class ShardedGallery:
     def __init__(self, local_rows: torch.Tensor, n_total: int, rank: int = 0, world: int = 1,
                  engine=None, group: Optional[dist.ProcessGroup] = None, scales: Optional[torch.Tensor] = None,
                  norm_bound: Optional[float] = None, force_collectives: bool = False, exact_fallback: bool = False,
-                 projection=None, fine_rows: Optional[torch.Tensor] = None):
+                 projection=None, fine_rows: Optional[torch.Tensor] = None, local_feats: Optional[torch.Tensor] = None):
         """local_rows: [n_local, D] bf16, or uint8 e4m3 bytes with per-row f32 `scales` (value = scale * fp8).
         norm_bound: upper bound of the (dequantised) row norms for the exactness certificate; None = L2-normalised
         descriptors (what SALAD emits); `measure_norm_bound()` computes it from the rows.
@@ -149,7 +154,9 @@ class ShardedGallery:
         (include/vpr_amd_project.h; in search_local_queries before the all-gather, so d-wide rows travel); queries of width d
         are taken as already projected; `expand` works in the projected space.
         fine_rows ([n_local, D_fine] bf16 or f32, this shard's rows of the full-precision descriptors the local rows were made
-        from): the second tier of search_reranked (include/vpr_amd_rerank.h); nothing else reads them."""
+        from): the second tier of search_reranked (include/vpr_amd_rerank.h); nothing else reads them.
+        local_feats ([n_local, n, l] bf16, this shard's images' local features, SaladAggregator.local_features): what
+        search_local_reranked matches the queries' patches against (include/vpr_amd_local.h); nothing else reads them."""
         lo, hi = shard_bounds(n_total, rank, world)
         if local_rows.shape[0] != hi - lo:
             raise ValueError(f"rank {rank}: shard has {local_rows.shape[0]} rows, expected {hi - lo}")
@@ -164,6 +171,13 @@ class ShardedGallery:
                 raise ValueError(f"rank {rank}: fine_rows must be [{hi - lo}, D_fine], one per local row; got {tuple(fine_rows.shape)}")
             if fine_rows.dtype not in (torch.bfloat16, torch.float32):
                 raise ValueError(f"fine_rows: bf16 or f32, got {fine_rows.dtype}")
+        if local_feats is not None:
+            if local_feats.dim() != 3 or local_feats.shape[0] != hi - lo:
+                raise ValueError(f"rank {rank}: local_feats must be [{hi - lo}, n, l], one image per local row; "
+                                 f"got {tuple(local_feats.shape)}")
+            if local_feats.dtype != torch.bfloat16:
+                raise ValueError(f"local_feats: bf16, got {local_feats.dtype}")
+        self.local_feats = local_feats
         self.fine_rows = fine_rows
         self.projection = projection
         self.scales = scales
@@ -205,6 +219,9 @@ class ShardedGallery:
     def gather_queries(self, q_local: torch.Tensor) -> torch.Tensor:
         if not self.collective:
             return q_local
+        if q_local.dim() > 2:           # local features [B_local, n, l]: gathered as rows of n * l
+            B = q_local.shape[0]
+            return self.gather_queries(q_local.reshape(B, -1)).view(self.world * B, *q_local.shape[1:])
         out = torch.empty((self.world * q_local.shape[0], q_local.shape[1]), dtype=q_local.dtype, device=q_local.device)
         dist.all_gather_into_tensor(out, q_local.contiguous(), group=self.group)
         return out
@@ -254,6 +271,35 @@ class ShardedGallery:
         _, i = self._local(self.project_queries(q_all), kc, ws, score_events)
         return self._merged(*self.engine.rerank(q_fine, i.contiguous(), self.fine_rows, self.index_base, k))
 
+    def search_local_reranked(self, q_all: torch.Tensor, k: int, kc: int, q_local_feats: torch.Tensor, min_sim: float = 0.0,
+                              ws=None, score_events=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Local-feature re-ranking (include/vpr_amd_local.h): the coarse local search of this shard for kc candidates
+        (k <= kc <= 64, through the projection if there is one), those candidates re-ranked to k by the summed similarity of
+        the mutual-nearest-neighbour patch pairs (similarity >= min_sim) between q_local_feats [B, n_q, l] bf16 and the shard's
+        `local_feats`, then the packed all-gather and merge of `search` — as many collectives as a plain search.
+        ws, score_events: of the coarse search, as in `search`.
+        Sharded meaning, as search_reranked: the answer is the k best by local score among the UNION of the shards' coarse
+        top-kc — each shard re-ranks its own kc candidates, so up to world * kc images are considered, a superset of the
+        global coarse top-kc.  With one shard that is the coarse top-kc itself.  Values are local scores (always finite)."""
+        if self.local_feats is None:
+            raise ValueError("search_local_reranked: this gallery has no local_feats")
+        if not 1 <= kc <= 64:
+            raise ValueError(f"search_local_reranked: one coarse search yields at most 64 candidates; kc = {kc}")
+        if not 1 <= k <= kc:
+            raise ValueError(f"search_local_reranked: k must be in 1..kc (k = {k}, kc = {kc})")
+        if q_local_feats is None or q_local_feats.dim() != 3 or q_local_feats.dtype != torch.bfloat16:
+            raise ValueError("search_local_reranked: q_local_feats must be bf16 [B, n_q, l]")
+        if q_local_feats.shape[2] != self.local_feats.shape[2]:
+            raise ValueError(f"search_local_reranked: the queries' local features are {q_local_feats.shape[2]} wide, the "
+                             f"gallery's {self.local_feats.shape[2]}")
+        if q_local_feats.shape[0] != q_all.shape[0]:
+            raise ValueError("search_local_reranked: q_all and q_local_feats disagree on B")
+        if max(q_local_feats.shape[1], self.local_feats.shape[1]) > 256:
+            raise ValueError("search_local_reranked: at most 256 patches per image")
+        _, i = self._local(self.project_queries(q_all), kc, ws, score_events)
+        v, i, _ = self.engine.local_rerank(q_local_feats.contiguous(), i.contiguous(), self.local_feats, self.index_base, k, min_sim)
+        return self._merged(v, i)
+
     def expand(self, q_all: torch.Tensor, vals: torch.Tensor, idx: torch.Tensor, n_use: int, alpha: float = 3.0,
                q_weight: float = 1.0) -> torch.Tensor:
         """Query expansion (alpha-QE, include/vpr_amd_expand.h): q_all [B, D] bf16 and its merged top-k (vals, idx) [B, k], the
@@ -292,11 +338,20 @@ class ShardedGallery:
 
     def search_gathered(self, q_all: torch.Tensor, k: int, expand=None, rerank: Optional[int] = None,
                         q_fine: Optional[torch.Tensor] = None, ws=None, ws2=None,
-                        score_events=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                        score_events=None, local_rerank: Optional[int] = None, q_local_feats: Optional[torch.Tensor] = None,
+                        min_sim: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
         """The search that (expand, rerank) name, over queries that are the same on every rank: `search`, `search_reranked`
         (rerank = kc) or `search_expanded` (expand: anything expansion_params takes; with rerank, of its last search).
-        q_fine, ws, ws2, score_events: as those take them; an expanded search has no seam for score_events."""
+        q_fine, ws, ws2, score_events: as those take them; an expanded search has no seam for score_events.
+        local_rerank = kc: `search_local_reranked` with q_local_feats and min_sim; it is a second stage of its own and combines
+        neither with rerank= nor with expand= (ValueError)."""
         expand = expansion_params(expand)
+        if local_rerank is not None:
+            if rerank is not None:
+                raise ValueError("search_gathered: local_rerank and rerank are two kinds of second stage; name one of them")
+            if expand is not None:
+                raise ValueError("search_gathered: local_rerank does not combine with expand")
+            return self.search_local_reranked(q_all, k, local_rerank, q_local_feats, min_sim, ws, score_events)
         if expand is not None:
             if score_events is not None:
                 raise ValueError("search_gathered: score_events cannot be collected around an expanded search")
@@ -306,19 +361,27 @@ class ShardedGallery:
         return self.search(q_all, k, ws, score_events)
 
     def search_local_queries(self, q_local: torch.Tensor, k: int, expand=None, rerank: Optional[int] = None, *,
-                             ws=None, ws2=None, score_events=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                             ws=None, ws2=None, score_events=None, local_rerank: Optional[int] = None,
+                             q_local_feats: Optional[torch.Tensor] = None, min_sim: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
         """Data-parallel form: each rank contributes B_local queries and gets back its own rows — project, gather, search
         (search_gathered), keep this rank's rows.  The eager callers and GraphedRetrieval all go through here.
         expand: None, or the query expansion to search with (expansion_params).
         rerank = kc: the two-tier form (search_reranked; with `expand`, of its last search).  The fine queries are q_local's
         rows: when a projection made the travelling rows d wide, the D_in-wide ones are gathered as well.
+        local_rerank = kc: the local-feature form (search_local_reranked) with this rank's q_local_feats [B_local, n_q, l] bf16,
+        gathered across the ranks like the queries when the gallery is collective; not together with rerank= or expand=.
         ws, ws2, score_events: handed to search_gathered."""
+        if local_rerank is not None and rerank is not None:
+            raise ValueError("search_local_queries: local_rerank and rerank are two kinds of second stage; name one of them")
+        if local_rerank is not None and (q_local_feats is None or q_local_feats.shape[0] != q_local.shape[0]):
+            raise ValueError("search_local_queries: local_rerank needs q_local_feats, one image per query")
         q_proj = self.project_queries(q_local)
         q_all = self.gather_queries(q_proj)
         q_fine = None
         if rerank is not None:
             q_fine = q_all if q_proj is q_local else self.gather_queries(q_local)
-        v, i = self.search_gathered(q_all, k, expand, rerank, q_fine, ws, ws2, score_events)
+        feats_all = None if local_rerank is None else self.gather_queries(q_local_feats.contiguous())
+        v, i = self.search_gathered(q_all, k, expand, rerank, q_fine, ws, ws2, score_events, local_rerank, feats_all, min_sim)
         b = q_local.shape[0]
         return v[self.rank * b:(self.rank + 1) * b], i[self.rank * b:(self.rank + 1) * b]
 
@@ -351,12 +414,24 @@ class GraphedRetrieval:
     A gallery with a projection: `self.q` has the projection's input width and the projection is captured inside the graph,
     ahead of the gather.
     rerank (kc): the graph holds the two-tier form, ShardedGallery.search_reranked (with `expand`, of its last search): the fine
-    queries are `self.q`, vals are fine scores, and the poses come from the re-ranked rows."""
+    queries are `self.q`, vals are fine scores, and the poses come from the re-ranked rows.
+    local_rerank (kc): the graph holds the local-feature form, ShardedGallery.search_local_reranked (not with `rerank` or
+    `expand`): `self.q_feats` [B_local, n, l] bf16 (n, l: the gallery's) is a second static input,
+    filled by __call__(q_local, q_local_feats); vals are local scores."""
 
     def __init__(self, gallery: ShardedGallery, batch_local: int, k: int, labels=None, mode: str = "top1",
-                 temperature: float = 0.01, scaler=None, expand=None, rerank: Optional[int] = None):
+                 temperature: float = 0.01, scaler=None, expand=None, rerank: Optional[int] = None,
+                 local_rerank: Optional[int] = None, min_sim: float = 0.0):
         self.g, self.k = gallery, k
         self.rerank = None if rerank is None else int(rerank)
+        self.local_rerank = None if local_rerank is None else int(local_rerank)
+        self.min_sim, self.q_feats = float(min_sim), None
+        if self.local_rerank is not None:
+            if rerank is not None or expand is not None:
+                raise ValueError("GraphedRetrieval: local_rerank combines neither with rerank nor with expand")
+            if gallery.local_feats is None:
+                raise ValueError("GraphedRetrieval: local_rerank needs a gallery with local_feats")
+            self.q_feats = torch.zeros((batch_local, *gallery.local_feats.shape[1:]), dtype=torch.bfloat16, device=gallery.rows.device)
         self.expand = expansion_params(expand)
         self.labels = None if labels is None else pose_labels(labels, gallery.rows.device)
         self.mode, self.temperature, self.scaler = mode, temperature, pose_scaler(scaler)
@@ -370,7 +445,7 @@ class GraphedRetrieval:
         dev, D = rows.device, rows.shape[1]
         self.q = torch.zeros((batch_local, gallery.query_width), dtype=torch.bfloat16, device=dev)
         B = batch_local * (gallery.world if gallery.collective else 1)
-        self.ws = ops.knn_workspace(B, rows.shape[0], D, k if self.rerank is None else max(k, self.rerank), dev)
+        self.ws = ops.knn_workspace(B, rows.shape[0], D, max(k, self.rerank or 0, self.local_rerank or 0), dev)
         self.ws2 = None if self.expand is None else ops.workspace("knn_expanded", self.ws.numel(), dev)
         counted = gallery.uncertified.clone() if gallery.uncertified is not None else None
         self._captured = _streams.Captured(self._run, dev)      # the warm-up also sets the communicator up
@@ -383,12 +458,15 @@ class GraphedRetrieval:
         self._captured.close()
 
     def _run(self):
-        v, i = self.g.search_local_queries(self.q, self.k, self.expand, self.rerank, ws=self.ws, ws2=self.ws2)
+        v, i = self.g.search_local_queries(self.q, self.k, self.expand, self.rerank, ws=self.ws, ws2=self.ws2,
+                                           local_rerank=self.local_rerank, q_local_feats=self.q_feats, min_sim=self.min_sim)
         if self.labels is not None:
             self.pose64, self.pose4 = transfer_pose(v, i, self.labels, self.mode, self.temperature, self.scaler)
         return v, i
 
-    def __call__(self, q_local: torch.Tensor):
+    def __call__(self, q_local: torch.Tensor, q_local_feats: Optional[torch.Tensor] = None):
         self.q.copy_(q_local)
+        if self.q_feats is not None:
+            self.q_feats.copy_(q_local_feats)
         self._captured.graph.replay()
         return self.vals, self.idx

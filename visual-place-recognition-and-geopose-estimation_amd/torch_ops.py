@@ -13,6 +13,7 @@ that seam, so the HIP hot path is visible to PyTorch's dispatcher like any other
     torch.ops.vpr.query_expand / query_expand_finish   (alpha-QE / DBA: weighted mean of a query and its best rows)
     torch.ops.vpr.project_rows                         (PCA / whitening projection of descriptors + L2 re-normalisation)
     torch.ops.vpr.rerank_rows                          (two-tier retrieval: coarse candidates re-ranked on full-precision rows)
+    torch.ops.vpr.local_rerank                         (local-feature re-ranking: mutual-nearest-neighbour patch matches)
     torch.ops.vpr.pose_head / ln_meanpool_head
     torch.ops.vpr.head_train_epoch                     (head-only fine-tuning pass; mutates parameters and AdamW moments)
     torch.ops.vpr.head_train_epoch_dropout             (the same pass with Dropout(p) after the ReLU, training mode)
@@ -271,6 +272,23 @@ def _(q, idx, rows, index_base=0, k=None):
     return q.new_empty((B, k), dtype=torch.float32), q.new_empty((B, k), dtype=torch.int32)
 
 
+@torch.library.custom_op("vpr::local_rerank", mutates_args=())
+def local_rerank(q_local: Tensor, idx: Tensor, g_local: Tensor, index_base: int = 0, k: Optional[int] = None,
+                 min_sim: float = 0.0) -> Tuple[Tensor, Tensor, Tensor]:
+    """Local-feature re-ranking: q_local bf16 [B, n_q, l], candidates idx int32 [B, kc] (global rows), this shard's local
+    features bf16 [n_local, n_g, l] -> (scores f32, indices int32, matches int32), each [B, k]: the k best (None: kc) of the
+    candidates the shard owns by the summed similarity of their mutual-nearest-neighbour patch pairs (similarity >= min_sim),
+    (score desc, index asc); the rest is (-inf, -1, 0).  vpr_local_rerank."""
+    return ops.local_rerank(q_local, idx, g_local, index_base, k, min_sim)
+
+
+@local_rerank.register_fake
+def _(q_local, idx, g_local, index_base=0, k=None, min_sim=0.0):
+    B, k = idx.shape[0], idx.shape[1] if k is None else k
+    new = lambda dtype: q_local.new_empty((B, k), dtype=dtype)
+    return new(torch.float32), new(torch.int32), new(torch.int32)
+
+
 # ------------------------------------------------------------------------------------------------------------ heads
 @torch.library.custom_op("vpr::pose_head", mutates_args=())
 def pose_head(x: Tensor, W1: Optional[Tensor], b1: Optional[Tensor], W2: Tensor, b2: Tensor, sincos_offset: int) -> Tensor:
@@ -343,4 +361,5 @@ def _(X, Y, order, batch_size, W1, b1, W2, b2, m, v, first_step, lr, beta1, beta
 
 OPS = ("head_train_epoch", "head_train_epoch_dropout", "salad_aggregate", "salad_aggregate_split", "salad_aggregate_f32", "salad_aggregate_train", "knn_topk", "knn_topk_fp8", "quantize_fp8_rows",
        "topk_merge", "pose_head", "ln_meanpool_head", "retrieval_pose", "query_expand", "query_expand_finish", "project_rows",
-       "rerank_rows", "salad_aggregate_n", "salad_aggregate_f32_n", "salad_aggregate_hires", "salad_aggregate_f32_hires")
+       "rerank_rows", "salad_aggregate_n", "salad_aggregate_f32_n", "salad_aggregate_hires", "salad_aggregate_f32_hires",
+       "local_rerank")
