@@ -12,8 +12,8 @@
 //                                 with its W2 slice -> S [2][B*n, m], F [2][B*n, l] f32 partial-sum slabs (no H in HBM)
 //   A  vpr_salad_stage_aggregate  sinkhorn_aggregate_kernel (one workgroup per image): slab sum, dustbin row, Sinkhorn in the
 //                                 exp domain (K = exp(M - rowmax) once, then alpha / beta updates: matrix-vector products),
-//                                 P as two bf16 planes, V = F^T P^T as three exact-product bf16 MFMAs on the (hi, lo) terms
-//                                 (f32 accuracy), the three L2 normalisations, 8448 outputs (f32 + bf16 copy for the kNN stage)
+//                                 then the back half all stage-A kernels share (salad_stage_a.h): P planes, V = F^T P^T at
+//                                 f32 accuracy, the three L2 normalisations, 8448 outputs (f32 + bf16 copy for the kNN stage)
 //   vpr_salad_aggregate_f32: the same at the reference's fp32 precision (three bf16 planes per operand, f32 hidden).
 //   vpr_salad_aggregate_n / _f32_n (include/vpr_amd_salad_anyres.h): any token count 65 .. 576 — stages T and the unfused M
 //   as above, stage A by sinkhorn_aggregate_n_kernel (salad_anyres.hip); everything else here stays n = 256.
@@ -22,6 +22,7 @@
 #include <math.h>
 #include "vpr_common.h"
 #include "vpr_internal.h"
+#include "salad_stage_a.h"
 #include "../../include/vpr_amd_salad_stages.h"
 #include "../../include/vpr_amd_salad_anyres.h"
 #include "../../include/vpr_amd_salad_hires.h"
@@ -35,20 +36,6 @@ constexpr int SA_PLD = SA_N + 8;  // row stride (bf16) of the P planes: 528 B, 1
 constexpr size_t SA_BIG_BYTES = ((SA_M + 1) * SA_LD * sizeof(float) > 2 * SA_M * SA_PLD * sizeof(uint16_t)
                                      ? (SA_M + 1) * SA_LD * sizeof(float) : 2 * SA_M * SA_PLD * sizeof(uint16_t));
 constexpr size_t SA_SMALL_OFF = (SA_BIG_BYTES + 15) / 16 * 16;
-
-// value of lane `i` (compile-time constant) of a wave-distributed register, as a scalar operand: v_readlane_b32
-__device__ __forceinline__ float lane_bcast(float v, int i) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), i));
-}
-
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-  // deterministic: wave butterflies, then a fixed-order sum of the 4 wave totals
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // NSLAB = 2: scores / feats arrive as two partial-sum slabs (the fused MLP kernel's K slices of the second layers,
 // gemm256_fuse2_kernel), `slab_rows` * m resp. * l elements apart; they are added here, slab 0 first.
@@ -216,8 +203,7 @@ __global__ __launch_bounds__(256, 1) void sinkhorn_aggregate_kernel(
   }
 
   SA_CLOCK(3);      // K in registers (and, NSLAB = 2, both feature slabs arrived)
-  const float inv_nm = 1.f / (float)(SA_N + SA_M);
-  const float a_reg = inv_nm, a_dust = (float)(SA_N - SA_M) * inv_nm, b_col = inv_nm;
+  const StageAMarginals mg = stage_a_marginals(SA_N);
   for (int it = 0; it < iters; ++it) {
     {                                                  // alpha_i = a_i / sum_j K_ij beta_j
       float bv[16];
@@ -230,7 +216,7 @@ __global__ __launch_bounds__(256, 1) void sinkhorn_aggregate_kernel(
         for (int c = 0; c < 16; ++c) sx = fmaf(mrow[p5][c], bv[c], sx);
         sx = row16_sum(sx);
         const int i = 16 * p5 + grp;
-        if (l16 == 0 && i <= SA_M) al[i] = (i == SA_M ? a_dust : a_reg) / sx;
+        if (l16 == 0 && i <= SA_M) al[i] = (i == SA_M ? mg.a_dust : mg.a_reg) / sx;
       }
     }
     lds_barrier();  
@@ -242,61 +228,34 @@ __global__ __launch_bounds__(256, 1) void sinkhorn_aggregate_kernel(
         s0 = fmaf(mcol[i], lane_bcast(a_lane, i), s0);
         s1 = fmaf(mcol[i + 1], lane_bcast(a_lane, i + 1), s1);
       }
-      be[tid] = b_col / (s0 + s1);
+      be[tid] = mg.b_col / (s0 + s1);
     }
     lds_barrier();
   }
 
   SA_CLOCK(4);      // iterations done
-  // ---- P = K alpha beta (n + m); dustbin row dropped.  Two bf16 planes (hi = bf16(P), lo = bf16(P - hi)) over the
-  // LDS of the score matrix (nobody reads Mx after the barrier above the iterations). ----
+  // ---- P = K alpha beta (n + m); dustbin row dropped.  The two bf16 planes go over the LDS of the score matrix (nobody
+  // reads Mx after the barrier above the iterations). ----
   {
     const int j = tid;
-    const float bj = be[j] * (float)(SA_N + SA_M);
+    const float bj = be[j] * mg.scale;
     const float a_lane = al[lane];
 #pragma unroll
-    for (int i = 0; i < SA_M; ++i) {
-      const float pv = mcol[i] * lane_bcast(a_lane, i) * bj;
-      const __bf16 h = (__bf16)pv;
-      const __bf16 l = (__bf16)(pv - (float)h);
-      Phi[i * SA_PLD + j] = __builtin_bit_cast(uint16_t, h);
-      Plo[i * SA_PLD + j] = __builtin_bit_cast(uint16_t, l);
-    }
+    for (int i = 0; i < SA_M; ++i) p_plane_entry(mcol[i], lane_bcast(a_lane, i), bj, Phi[i * SA_PLD + j], Plo[i * SA_PLD + j]);
   }
   lds_barrier();
 
   SA_CLOCK(5);      // P planes in LDS
-  // ---- V[l][m] = sum_j F[j][l] * P[m][j] on the bf16 matrix pipe at f32 accuracy ----
-  // F and P each split into two bf16 terms (2^-17 relative): three v_mfma_f32_32x32x16_bf16 (hi*hi, hi*lo, lo*hi) with exact
-  // products and f32 accumulation, error <= 2^-16 per product (~1e-8 absolute on descriptor entries of 1e-2; tolerance 1e-4).
-  // 32x32x16 operand maps: A[i = lane&31][k = 8*(lane>>5) + e], B[k = 8*(lane>>5) + e][j = lane&31].
-  // Wave w owns cluster-dim rows l0 = 32w .. 32w+31 and both 32-cluster column blocks.
+  // ---- V[l][m] = sum_j F[j][l] * P[m][j] (salad_stage_a.h): error <= 2^-16 per product, ~1e-8 absolute on descriptor
+  // entries of 1e-2 (tolerance 1e-4) ----
   f32x16 acc0, acc1;
 #pragma unroll
   for (int e = 0; e < 16; ++e) { acc0[e] = 0.f; acc1[e] = 0.f; }
 #pragma unroll
   for (int ch = 0; ch < NCH; ++ch) {
 #pragma unroll
-    for (int st = 0; st < 2; ++st) {
-      bf16x8 fh, fl;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        fh[e] = (__bf16)fa[ch][8 * st + e];
-        fl[e] = (__bf16)(fa[ch][8 * st + e] - (float)fh[e]);
-      }
-      const int j0 = tok0 + 32 * ch + 16 * st + 8 * kh;
-      const bf16x8 p0h = *reinterpret_cast<const bf16x8*>(Phi + li * SA_PLD + j0);
-      const bf16x8 p0l = *reinterpret_cast<const bf16x8*>(Plo + li * SA_PLD + j0);
-      const bf16x8 p1h = *reinterpret_cast<const bf16x8*>(Phi + (32 + li) * SA_PLD + j0);
-      const bf16x8 p1l = *reinterpret_cast<const bf16x8*>(Plo + (32 + li) * SA_PLD + j0);
-      // (the lo x lo term is 2^-34 of the product: below f32 resolution, dropped)
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl, p0h, acc0, 0, 0, 0);     // smallest terms first
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl, p1h, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh, p0l, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh, p1l, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh, p0h, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh, p1h, acc1, 0, 0, 0);
-    }
+    for (int st = 0; st < 2; ++st)
+      aggregate_step16(fa[ch], 8 * st, Phi, Plo, SA_PLD, tok0 + 32 * ch + 16 * st + 8 * kh, li, acc0, acc1);
   }
 
   SA_CLOCK(6);      // aggregation MFMAs issued (features arrived)
@@ -338,16 +297,13 @@ __global__ __launch_bounds__(256, 1) void sinkhorn_aggregate_kernel(
     if (tid == 0) __hip_atomic_store(counters + b, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     SA_CLOCK(7);
     // ---- finisher: per-cluster norm over all 128 cluster dims (quarter order), the whole row normalised in place ----
-    const float den = fmaxf(sqrtf((ob[m] + ob[SA_M + m]) + (ob[2 * SA_M + m] + ob[3 * SA_M + m])), 1e-12f);
+    const float den = l2_den((ob[m] + ob[SA_M + m]) + (ob[2 * SA_M + m] + ob[3 * SA_M + m]));
     float w[32], part = 0.f;
 #pragma unroll
     for (int i = 0; i < 32; ++i) w[i] = ob[SA_T + (lq + 4 * i) * SA_M + m];
 #pragma unroll
     for (int i = 0; i < 32; ++i) { w[i] = w[i] / den; part = fmaf(w[i], w[i], part); }
-    const float gn = fmaxf(sqrtf(block_sum_256(g * g, red)), 1e-12f);      // (its barriers also fence the reads of the scratch slots)
-    g = g / gn;
-    const float tot = block_sum_256(part + g * g, red);
-    const float gden = fmaxf(sqrtf(tot), 1e-12f);
+    const float gden = token_and_global_norm(g, part, red);                // (its barriers also fence the reads of the scratch slots)
     uint16_t* obh = out_bf16 ? out_bf16 + (long long)b * D_OUT : nullptr;
     {
       const float o = g / gden;
@@ -364,52 +320,10 @@ __global__ __launch_bounds__(256, 1) void sinkhorn_aggregate_kernel(
     SA_CLOCK(8);
     return;
   }
-  // ---- per-cluster L2 norm over l (F.normalize dim=1, eps 1e-12) ----
-  {
-    float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { s0 += acc0[e] * acc0[e]; s1 += acc1[e] * acc1[e]; }
-    s0 += __shfl_xor(s0, 32, 64);
-    s1 += __shfl_xor(s1, 32, 64);
-    if (lane < 32) { ssq[wave * SA_M + lane] = s0; ssq[wave * SA_M + 32 + lane] = s1; }
-  }
-  __syncthreads();
-  const float den0 = fmaxf(sqrtf((ssq[li] + ssq[SA_M + li]) + (ssq[2 * SA_M + li] + ssq[3 * SA_M + li])), 1e-12f);
-  const float den1 = fmaxf(sqrtf((ssq[32 + li] + ssq[SA_M + 32 + li]) + (ssq[2 * SA_M + 32 + li] + ssq[3 * SA_M + 32 + li])), 1e-12f);
-  float part = 0.f;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    acc0[e] = acc0[e] / den0;
-    acc1[e] = acc1[e] / den1;
-    part += acc0[e] * acc0[e] + acc1[e] * acc1[e];
-  }
-
-  // ---- token vector: F.normalize(g) ----
-  const float gn = fmaxf(sqrtf(block_sum_256(g * g, red)), 1e-12f);
-  g = g / gn;
-
-  // ---- global L2 over the concatenation [g | V.flatten] ----
-  const float tot = block_sum_256(part + g * g, red);
-  const float gden = fmaxf(sqrtf(tot), 1e-12f);
-
+  // ---- the three L2 normalisations and the 8448 outputs (salad_stage_a.h) ----
+  const float gden = stage_a_norms(acc0, acc1, g, ssq, red);
   SA_CLOCK(7);      // norms done
-  float* ob = out_f32 + (long long)b * D_OUT;
-  uint16_t* obh = out_bf16 ? out_bf16 + (long long)b * D_OUT : nullptr;
-  {
-    const float o = g / gden;
-    ob[tid] = o;
-    if (obh) obh[tid] = f32_to_bf16_bits(o);
-  }
-  // C/D map of 32x32: col (cluster) = lane&31, row (l) = (e&3) + 8*(e>>2) + 4*(lane>>5)
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const int l = l0 + (e & 3) + 8 * (e >> 2) + 4 * kh;
-    const float o0 = acc0[e] / gden, o1 = acc1[e] / gden;
-    const int base = SA_T + l * SA_M;
-    ob[base + li] = o0;
-    ob[base + 32 + li] = o1;
-    if (obh) { obh[base + li] = f32_to_bf16_bits(o0); obh[base + 32 + li] = f32_to_bf16_bits(o1); }
-  }
+  stage_a_store(acc0, acc1, g, gden, b, out_f32, out_bf16);
   SA_CLOCK(8);
 }
 

@@ -3,7 +3,7 @@
 //
 // sinkhorn_aggregate_kernel (salad.hip) is written around n = 256: one score column per thread, the whole K matrix and all
 // cluster features of a wave in registers.  This kernel keeps its arithmetic — exp-domain iterations on K = exp(M - rowmax),
-// P as (hi, lo) bf16 planes over the dead score matrix, three exact-product v_mfma_f32_32x32x16_bf16 per 16-token step,
+// the shared back half of salad_stage_a.h (P planes over the dead score matrix, aggregation, normalisations, stores),
 // lds_barrier() so that feature loads keep flying across the score-dependent phases — and changes where the operands live:
 //   * K stays in LDS as f32 [65][ld], ld = (n + 1) | 1 (odd: the transposing stores of the staging loop and the column pass
 //     are conflict-free); dynamic LDS sized from n, 153,664 B at n = 576 of the 163,840 B a workgroup may declare;
@@ -25,12 +25,12 @@
 #include <math.h>
 #include "vpr_common.h"
 #include "vpr_internal.h"
+#include "salad_stage_a.h"
 #include "../../include/vpr_amd_salad_anyres.h"
 
 namespace vpr {
 namespace {
 
-constexpr int AN_M = SA_M, AN_L = SA_L, AN_T = SA_T;   // the kernel's names for clusters, cluster dim, token dim (= threads per workgroup)
 constexpr int AN_QMAX = 18;  // score float4 per thread and staging batch: n <= 288 in one round trip, n <= 576 in two
 constexpr int AN_RC = VPR_SALAD_MAX_N / 32;   // 18: row entries per lane of a half-wave
 constexpr int AN_CQ = (VPR_SALAD_MAX_N + 255) / 256;   // 3: columns per thread
@@ -42,27 +42,16 @@ __host__ __device__ inline AnyresLds anyres_lds(int n) {
   g.ld = (n + 1) | 1;
   g.npad = (n + 15) & ~15;
   g.pld = g.npad + 8;                    // rows of 16-byte chunks, 4 banks apart (as SA_PLD)
-  const unsigned kbytes = (unsigned)(AN_M + 1) * g.ld * sizeof(float);
-  const unsigned pbytes = 2u * AN_M * g.pld * sizeof(uint16_t);        // larger than K for small n
+  const unsigned kbytes = (unsigned)(SA_M + 1) * g.ld * sizeof(float);
+  const unsigned pbytes = 2u * SA_M * g.pld * sizeof(uint16_t);        // larger than K for small n
   g.small_off = ((kbytes > pbytes ? kbytes : pbytes) + 15u) / 16u * 16u;
-  g.total = g.small_off + (68 + 4 * AN_M + 8 + g.npad) * (unsigned)sizeof(float);
+  g.total = g.small_off + (68 + 4 * SA_M + 8 + g.npad) * (unsigned)sizeof(float);
   return g;
 }
 
-__device__ __forceinline__ float an_lane_bcast(float v, int i) {      // lane i (constant) of v as a scalar operand
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), i));
-}
 // all-reduce over the 32 lanes of a half-wave; never leaves the half
 __device__ __forceinline__ float half32_sum(float v) { v = row16_sum(v); return v + __shfl_xor(v, 16, 64); }
 __device__ __forceinline__ float half32_max(float v) { v = row16_max(v); return fmaxf(v, __shfl_xor(v, 16, 64)); }
-
-__device__ __forceinline__ float an_block_sum_256(float v, float* red) {   // wave butterflies, then the 4 wave totals in fixed order
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 __global__ __launch_bounds__(256, 1) void sinkhorn_aggregate_n_kernel(
     const float* __restrict__ scores,   // [B, n, m]
@@ -74,21 +63,20 @@ __global__ __launch_bounds__(256, 1) void sinkhorn_aggregate_n_kernel(
   const int ld = geo.ld, npad = geo.npad, pld = geo.pld;
   float* Kx = reinterpret_cast<float*>(smem);               // [65][ld] raw scores, then K; later the two P planes
   uint16_t* Phi = reinterpret_cast<uint16_t*>(smem);        // [64][pld] bf16: hi plane of P (16-byte aligned rows)
-  uint16_t* Plo = Phi + AN_M * pld;                         // lo plane: P = hi + lo to 2^-17
+  uint16_t* Plo = Phi + SA_M * pld;                         // lo plane: P = hi + lo to 2^-17
   float* al = reinterpret_cast<float*>(smem + geo.small_off);   // [65] (+3 pad): alpha
   float* ssq = al + 68;                                     // [4][64]
-  float* red = ssq + 4 * AN_M;                              // [4] (+4 pad)
+  float* red = ssq + 4 * SA_M;                              // [4] (+4 pad)
   float* be = red + 8;                                      // [npad] beta
   const int b = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  constexpr int D_OUT = AN_T + AN_L * AN_M;
 
-  float g = tokfeat[(long long)b * AN_T + tid];
+  float g = tokfeat[(long long)b * SA_T + tid];
 
   // ---- scores transposed into LDS: Kx[i][j] = scores[b][j][i]; up to AN_QMAX float4 per thread in flight ----
   {
-    const float4* sb4 = reinterpret_cast<const float4*>(scores + (long long)b * n * AN_M);
-    const int n16 = n * (AN_M / 4);
+    const float4* sb4 = reinterpret_cast<const float4*>(scores + (long long)b * n * SA_M);
+    const int n16 = n * (SA_M / 4);
     for (int base = 0; base < n16; base += 256 * AN_QMAX) {
       float4 q[AN_QMAX];
 #pragma unroll
@@ -110,30 +98,18 @@ __global__ __launch_bounds__(256, 1) void sinkhorn_aggregate_n_kernel(
     }
   }
   for (int j = tid; j < n; j += 256) {       // dustbin row i = m; beta = 1
-    Kx[AN_M * ld + j] = dustbin;
+    Kx[SA_M * ld + j] = dustbin;
     be[j] = 1.f;
   }
 
-  // ---- cluster features: this wave's 32 cluster dims, 64 tokens per chunk (32x32x16 A-operand map: A[i = lane & 31]
-  // [k = 8 * (lane >> 5) + e]); f[8 * st + e] = F[64 c + 16 st + 8 kh + e][l0 + li].  The loads go through a buffer
-  // descriptor whose range is feats[b] and nothing else: for a token >= n the hardware's bounds check returns 0 and fetches
-  // nothing, without a branch per element (32 predicated flat loads per chunk made the compiler spill ~2 KB per lane). ----
-  const int l0 = 32 * wave, kh = lane >> 5, li = lane & 31;
-  const auto frsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(feats + (long long)b * n * AN_L), 0,
-                                                       n * AN_L * (int)sizeof(float), 0x00020000);      // wave-uniform operands only
-  const int foff = (l0 + li) * (int)sizeof(float);
-  auto load_chunk = [&](float (&f)[32], int c) {
-    const int t0 = 64 * c + 8 * kh;
-#pragma unroll
-    for (int i = 0; i < 32; ++i)
-      f[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                 frsrc, (t0 + 16 * (i >> 3) + (i & 7)) * (AN_L * (int)sizeof(float)) + foff, 0, 0));
-  };
+  // ---- cluster features: this wave's 32 cluster dims, 64 tokens per chunk, three chunk buffers ----
+  const int kh = lane >> 5, li = lane & 31;
+  const FeatureStream fs(feats + (long long)b * n * SA_L, n, lane, wave);
   float f0[32], f1[32], f2[32];
   const int nch = (npad + 63) >> 6;          // >= 2: n > 64
-  load_chunk(f0, 0);
-  load_chunk(f1, 1);
-  if (2 < nch) load_chunk(f2, 2);
+  fs.load_chunk(f0, 0);
+  fs.load_chunk(f1, 1);
+  if (2 < nch) fs.load_chunk(f2, 2);
   lds_barrier();
 
   // ---- row maxima, K = exp(M - rowmax) in place: half-wave `half` owns rows half, half + 8, ... ----
@@ -141,7 +117,7 @@ __global__ __launch_bounds__(256, 1) void sinkhorn_aggregate_n_kernel(
 #pragma unroll 1
   for (int p = 0; p < 9; ++p) {
     const int i = half + 8 * p;
-    if (i <= AN_M) {                                                   // per half-wave; nothing below leaves the half
+    if (i <= SA_M) {                                                   // per half-wave; nothing below leaves the half
       float* row = Kx + i * ld;
       float kv[AN_RC];
 #pragma unroll
@@ -163,8 +139,7 @@ __global__ __launch_bounds__(256, 1) void sinkhorn_aggregate_n_kernel(
   lds_barrier();
 
   // ---- Sinkhorn in the exp domain: alpha_i = a_i / sum_j K_ij beta_j, beta_j = b_j / sum_i K_ij alpha_i ----
-  const float inv_nm = 1.f / (float)(n + AN_M);
-  const float a_reg = inv_nm, a_dust = (float)(n - AN_M) * inv_nm, b_col = inv_nm;
+  const StageAMarginals mg = stage_a_marginals(n);
   for (int it = 0; it < iters; ++it) {
     {
       float bv[AN_RC];
@@ -176,7 +151,7 @@ __global__ __launch_bounds__(256, 1) void sinkhorn_aggregate_n_kernel(
 #pragma unroll 1
       for (int p = 0; p < 9; ++p) {
         const int i = half + 8 * p;
-        if (i <= AN_M) {
+        if (i <= SA_M) {
           const float* row = Kx + i * ld;
           float kv[AN_RC];
 #pragma unroll
@@ -188,50 +163,49 @@ __global__ __launch_bounds__(256, 1) void sinkhorn_aggregate_n_kernel(
 #pragma unroll
           for (int c = 0; c < AN_RC; ++c) sx = fmaf(kv[c], bv[c], sx);
           sx = half32_sum(sx);
-          if (l32 == 0) al[i] = (i == AN_M ? a_dust : a_reg) / sx;
+          if (l32 == 0) al[i] = (i == SA_M ? mg.a_dust : mg.a_reg) / sx;
         }
       }
     }
     lds_barrier();
     {
-      const float a_lane = al[lane], a_d = al[AN_M];
+      const float a_lane = al[lane], a_d = al[SA_M];
 #pragma unroll
       for (int q = 0; q < AN_CQ; ++q) {
         const int j = tid + 256 * q;
         if (j < n) {
           const float* col = Kx + j;
-          float s0 = col[AN_M * ld] * a_d, s1 = 0.f;                  // two chains: half the dependent-FMA latency
+          float s0 = col[SA_M * ld] * a_d, s1 = 0.f;                  // two chains: half the dependent-FMA latency
 #pragma unroll
-          for (int i = 0; i < AN_M; i += 2) {
-            s0 = fmaf(col[i * ld], an_lane_bcast(a_lane, i), s0);
-            s1 = fmaf(col[(i + 1) * ld], an_lane_bcast(a_lane, i + 1), s1);
+          for (int i = 0; i < SA_M; i += 2) {
+            s0 = fmaf(col[i * ld], lane_bcast(a_lane, i), s0);
+            s1 = fmaf(col[(i + 1) * ld], lane_bcast(a_lane, i + 1), s1);
           }
-          be[j] = b_col / (s0 + s1);
+          be[j] = mg.b_col / (s0 + s1);
         }
       }
     }
     lds_barrier();
   }
 
-  // ---- P = K alpha beta (n + m); dustbin row dropped.  Packed (hi = bf16(P), lo = bf16(P - hi)) pairs of this thread's
-  // columns in registers first: the planes overwrite K, which other threads' columns still live in. ----
+  // ---- P = K alpha beta (n + m); dustbin row dropped.  Packed (hi, lo) pairs of this thread's columns in registers first:
+  // the planes overwrite K, which other threads' columns still live in. ----
   {
-    uint32_t pk[AN_CQ][AN_M];
+    uint32_t pk[AN_CQ][SA_M];
     const float a_lane = al[lane];
 #pragma unroll
     for (int q = 0; q < AN_CQ; ++q) {
       const int j = tid + 256 * q;
 #pragma unroll
-      for (int i = 0; i < AN_M; ++i) pk[q][i] = 0u;                   // pad columns: +0 in both planes
+      for (int i = 0; i < SA_M; ++i) pk[q][i] = 0u;                   // pad columns: +0 in both planes
       if (j < n) {
         const float* col = Kx + j;
-        const float bj = be[j] * (float)(n + AN_M);
+        const float bj = be[j] * mg.scale;
 #pragma unroll
-        for (int i = 0; i < AN_M; ++i) {
-          const float pv = col[i * ld] * an_lane_bcast(a_lane, i) * bj;
-          const __bf16 h = (__bf16)pv;
-          const __bf16 l = (__bf16)(pv - (float)h);
-          pk[q][i] = (uint32_t)__builtin_bit_cast(uint16_t, h) | ((uint32_t)__builtin_bit_cast(uint16_t, l) << 16);
+        for (int i = 0; i < SA_M; ++i) {
+          uint16_t h, l;
+          p_plane_entry(col[i * ld], lane_bcast(a_lane, i), bj, h, l);
+          pk[q][i] = (uint32_t)h | ((uint32_t)l << 16);
         }
       }
     }
@@ -241,7 +215,7 @@ __global__ __launch_bounds__(256, 1) void sinkhorn_aggregate_n_kernel(
       const int j = tid + 256 * q;
       if (j < npad) {
 #pragma unroll
-        for (int i = 0; i < AN_M; ++i) {
+        for (int i = 0; i < SA_M; ++i) {
           Phi[i * pld + j] = (uint16_t)(pk[q][i] & 0xffffu);
           Plo[i * pld + j] = (uint16_t)(pk[q][i] >> 16);
         }
@@ -250,9 +224,7 @@ __global__ __launch_bounds__(256, 1) void sinkhorn_aggregate_n_kernel(
   }
   lds_barrier();
 
-  // ---- V[l][m] = sum_j F[j][l] * P[m][j] on the bf16 matrix pipe at f32 accuracy: F and P each as two bf16 terms, three
-  // MFMAs (lo*hi, hi*lo, hi*hi; smallest terms first) with exact products and f32 accumulation, as in salad.hip.
-  // 32x32x16 operand maps: A[i = lane&31][k = 8*(lane>>5) + e], B[k = 8*(lane>>5) + e][j = lane&31]. ----
+  // ---- V[l][m] = sum_j F[j][l] * P[m][j], the normalisations and the outputs (salad_stage_a.h) ----
   f32x16 acc0, acc1;
 #pragma unroll
   for (int e = 0; e < 16; ++e) { acc0[e] = 0.f; acc1[e] = 0.f; }
@@ -260,79 +232,20 @@ __global__ __launch_bounds__(256, 1) void sinkhorn_aggregate_n_kernel(
 #pragma unroll
     for (int st = 0; st < 4; ++st) {
       const int j0 = 64 * c + 16 * st;
-      if (j0 < npad) {                                                 // uniform; the planes end at column npad
-        bf16x8 fh, fl;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          fh[e] = (__bf16)f[8 * st + e];
-          fl[e] = (__bf16)(f[8 * st + e] - (float)fh[e]);
-        }
-        const int jj = j0 + 8 * kh;
-        const bf16x8 p0h = *reinterpret_cast<const bf16x8*>(Phi + li * pld + jj);
-        const bf16x8 p0l = *reinterpret_cast<const bf16x8*>(Plo + li * pld + jj);
-        const bf16x8 p1h = *reinterpret_cast<const bf16x8*>(Phi + (32 + li) * pld + jj);
-        const bf16x8 p1l = *reinterpret_cast<const bf16x8*>(Plo + (32 + li) * pld + jj);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl, p0h, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fl, p1h, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh, p0l, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh, p1l, acc1, 0, 0, 0);
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh, p0h, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fh, p1h, acc1, 0, 0, 0);
-      }
+      if (j0 < npad) aggregate_step16(f, 8 * st, Phi, Plo, pld, j0 + 8 * kh, li, acc0, acc1);   // uniform; the planes end at column npad
     }
   };
 #pragma unroll 1
   for (int c = 0; c < nch; c += 3) {       // three chunk buffers in fixed registers; nothing is requested at or behind nch
     mma_chunk(f0, c);
-    if (c + 3 < nch) load_chunk(f0, c + 3);
+    if (c + 3 < nch) fs.load_chunk(f0, c + 3);
     mma_chunk(f1, c + 1);
-    if (c + 4 < nch) load_chunk(f1, c + 4);
+    if (c + 4 < nch) fs.load_chunk(f1, c + 4);
     mma_chunk(f2, c + 2);
-    if (c + 5 < nch) load_chunk(f2, c + 5);
+    if (c + 5 < nch) fs.load_chunk(f2, c + 5);
   }
-
-  // ---- per-cluster L2 norm over l (F.normalize dim=1, eps 1e-12) ----
-  {
-    float s0 = 0.f, s1 = 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { s0 += acc0[e] * acc0[e]; s1 += acc1[e] * acc1[e]; }
-    s0 += __shfl_xor(s0, 32, 64);
-    s1 += __shfl_xor(s1, 32, 64);
-    if (lane < 32) { ssq[wave * AN_M + lane] = s0; ssq[wave * AN_M + 32 + lane] = s1; }
-  }
-  __syncthreads();
-  const float den0 = fmaxf(sqrtf((ssq[li] + ssq[AN_M + li]) + (ssq[2 * AN_M + li] + ssq[3 * AN_M + li])), 1e-12f);
-  const float den1 = fmaxf(sqrtf((ssq[32 + li] + ssq[AN_M + 32 + li]) + (ssq[2 * AN_M + 32 + li] + ssq[3 * AN_M + 32 + li])), 1e-12f);
-  float part = 0.f;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    acc0[e] = acc0[e] / den0;
-    acc1[e] = acc1[e] / den1;
-    part += acc0[e] * acc0[e] + acc1[e] * acc1[e];
-  }
-  // ---- token vector: F.normalize(g); then the global L2 over the concatenation [g | V.flatten] ----
-  const float gn = fmaxf(sqrtf(an_block_sum_256(g * g, red)), 1e-12f);
-  g = g / gn;
-  const float tot = an_block_sum_256(part + g * g, red);
-  const float gden = fmaxf(sqrtf(tot), 1e-12f);
-
-  float* ob = out_f32 + (long long)b * D_OUT;
-  uint16_t* obh = out_bf16 ? out_bf16 + (long long)b * D_OUT : nullptr;
-  {
-    const float o = g / gden;
-    ob[tid] = o;
-    if (obh) obh[tid] = f32_to_bf16_bits(o);
-  }
-  // C/D map of 32x32: col (cluster) = lane&31, row (l) = (e&3) + 8*(e>>2) + 4*(lane>>5)
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const int l = l0 + (e & 3) + 8 * (e >> 2) + 4 * kh;
-    const float o0 = acc0[e] / gden, o1 = acc1[e] / gden;
-    const int base = AN_T + l * AN_M;
-    ob[base + li] = o0;
-    ob[base + 32 + li] = o1;
-    if (obh) { obh[base + li] = f32_to_bf16_bits(o0); obh[base + 32 + li] = f32_to_bf16_bits(o1); }
-  }
+  const float gden = stage_a_norms(acc0, acc1, g, ssq, red);
+  stage_a_store(acc0, acc1, g, gden, b, out_f32, out_bf16);
 }
 
 }  // namespace
@@ -340,10 +253,7 @@ __global__ __launch_bounds__(256, 1) void sinkhorn_aggregate_n_kernel(
 int launch_sinkhorn_aggregate_n(const float* scores, const float* feats, const float* tokfeat,
                                 int B, int n, int m, int l, int t, float dustbin, int iters,
                                 float* out_f32, uint16_t* out_bf16, hipStream_t stream) {
-  if (!scores || !feats || !tokfeat || !out_f32 || B <= 0 || n < 1 || iters < 1) return VPR_ERR_INVALID_ARG;
-  if (!salad_in_domain(SaladDomain::AnyN, n, m, l, t)) return VPR_ERR_UNSUPPORTED;
-  if (!aligned16(scores) || !aligned16(feats) || !aligned4(tokfeat) || !aligned4(out_f32) || (reinterpret_cast<uintptr_t>(out_bf16) & 1))
-    return VPR_ERR_UNSUPPORTED;
+  VPR_TRY_LAUNCH(stage_a_check(SaladDomain::AnyN, scores, feats, tokfeat, B, n, m, l, t, iters, out_f32, out_bf16));
   // the opt-in once per device, for the largest n (smaller n then needs no second call)
   VPR_TRY_LAUNCH(optin_dynamic_lds<sinkhorn_aggregate_n_kernel>(anyres_lds(VPR_SALAD_MAX_N).total));
   return launch_kernel(sinkhorn_aggregate_n_kernel, dim3(B), dim3(256), anyres_lds(n).total, stream, scores, feats, tokfeat, n,

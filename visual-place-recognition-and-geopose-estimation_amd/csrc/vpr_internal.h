@@ -162,4 +162,15 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
+// The argument check of the two run-time-n stage-A launchers (salad_anyres.hip, salad_hires.hip): INVALID_ARG (null operand,
+// sizes, iterations), then UNSUPPORTED (outside `d`; scores / feats are read as 16-byte chunks, the rest as elements).
+inline int stage_a_check(SaladDomain d, const float* scores, const float* feats, const float* tokfeat, int B, int n, int m, int l,
+                         int t, int iters, const float* out_f32, const uint16_t* out_bf16) {
+  if (!scores || !feats || !tokfeat || !out_f32 || B <= 0 || n < 1 || iters < 1) return VPR_ERR_INVALID_ARG;
+  if (!salad_in_domain(d, n, m, l, t)) return VPR_ERR_UNSUPPORTED;
+  if (!aligned16(scores) || !aligned16(feats) || !aligned4(tokfeat) || !aligned4(out_f32) || (reinterpret_cast<uintptr_t>(out_bf16) & 1))
+    return VPR_ERR_UNSUPPORTED;
+  return VPR_OK;
+}
+
 }  // namespace vpr
