@@ -114,6 +114,25 @@ def test_layernorm_two_rows_per_wave_bit_identical(dev, tune, C):
             assert torch.equal(a, b), f"C={C} M={M}"
 
 
+@pytest.mark.parametrize("C", (8, 520, 1544, 2048))
+def test_layernorm_forms_share_one_row_pass(dev, C):
+    """The three entries and both parameter types are one row pass behind different front ends: a zero pre-bias, a zero
+    residual and f32 copies of bf16 gamma / beta each give the bits of the plain bf16-parameter call (the rows hold no
+    negative zero, so adding +0.0 changes no value)."""
+    from vpr_amd import ops
+    g = torch.Generator().manual_seed(7000 + C)
+    for M in (1, 5):
+        x = torch.cat([_rows(k, M, C, g) for k in KINDS]).to(torch.bfloat16).to(dev)
+        gamma, beta = (t.to(dev) for t in _params(C, torch.bfloat16, g))
+        y = ops.layernorm_bf16(x, gamma, beta, EPS)
+        what = f"C={C} M={M}"
+        assert torch.equal(ops.bias_layernorm_bf16(x, torch.zeros(C, device=dev), gamma, beta, EPS), y), "bias " + what
+        s, y_add = ops.add_layernorm_bf16(x, torch.zeros_like(x), gamma, beta, EPS)
+        assert torch.equal(s, x), "add " + what
+        assert torch.equal(y_add, y), "add " + what
+        assert torch.equal(ops.layernorm_bf16(x, gamma.float(), beta.float(), EPS), y), "f32 parameters " + what
+
+
 def test_layernorm_refusals(dev):
     """C % 8, C > 2048 and misaligned pointers are refused; M = 0 is a no-op."""
     from vpr_amd import ops

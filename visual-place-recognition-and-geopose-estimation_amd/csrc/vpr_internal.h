@@ -61,7 +61,9 @@ int launch_salad_mlps_fused(const uint16_t* X, int ldx, int group_rows, long lon
                             float* S, float* F, int M, int C, int hidden, int m, int l, hipStream_t stream,
                             const uint16_t* W2s_frag = nullptr, const uint16_t* W2c_frag = nullptr,
                             const Fuse2Drop* drop = nullptr);
-// skinny.hip: a few rows x [N, K]^T; mode 0 bias, 1 bias+tanh-GELU, 2 accumulate into out, 3 bias+ReLU, 4 bias+erf-GELU
+// skinny.hip: out = epilogue(in W^T) for a few rows x [N, K]^T; `mode` is one of
+enum { SK_BIAS = 0, SK_BIAS_GELU = 1 /* tanh form */, SK_ACCUMULATE = 2 /* out += in W^T, no bias */, SK_BIAS_RELU = 3,
+       SK_BIAS_GELU_ERF = 4, SK_BIAS_F32 = 5 /* out is float*, ldo in floats: SALAD token features */ };
 int launch_skinny_linear(const uint16_t* in, int ldi, const uint16_t* W, int ldw, const void* bias, int bias_is_bf16,
                          int mode, uint16_t* out, int ldo, int M, int N, int K, const float* stats_bias,
                          float* row_stats, void* stream);
