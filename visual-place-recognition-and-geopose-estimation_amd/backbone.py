@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _streams
+from . import _streams, ops
 from ._cache import tensor_key
 
 def gemm_autotune(enable: bool = True, tuning: bool = True, max_ms_per_gemm: int = 30) -> None:
@@ -43,10 +43,19 @@ CONFIGS = {
 }
 
 
+def _ln_width_ok(C: int) -> bool:
+    """The row widths the HIP LayerNorm kernels take."""
+    return C % 8 == 0 and C <= 2048
+
+
+def _hip_attention_ok(head_dim: int, T: int) -> bool:
+    """The domain of the short-sequence HIP attention kernel (K, V of one (image, head) resident in LDS)."""
+    return head_dim == 64 and T <= 288
+
+
 def _ln(norm: nn.LayerNorm, x: torch.Tensor) -> torch.Tensor:
     """LayerNorm: the hand-written HIP kernel for GPU bf16 activations, PyTorch's otherwise (CPU)."""
-    if x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048:
-        from . import ops
+    if x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous() and _ln_width_ok(x.shape[-1]):
         return ops.layernorm_bf16(x, norm.weight, norm.bias, norm.eps)
     return norm(x)
 
@@ -113,6 +122,70 @@ class Block(nn.Module):
         return x
 
 
+PATCH, CLS = 0, 1       # the two row ranges of the split row layout [B*n patch rows | B cls rows]
+ATT, MLP = 0, 1         # the two halves of a block: proj -> LayerNorm 2, and fc2 -> the LayerNorm before the next qkv
+
+
+class _BlockStages:
+    """One block of the HIP path as its launches: qkv, [attention,] x += att Wproj^T, LayerNorm 2, fc1 + GELU, x += hh Wfc2^T,
+    and the LayerNorm before the next qkv (the next block's norm1, or the final norm).  Each GEMM stage has a PATCH form (a
+    library GEMM) and a CLS form (vpr_skinny_linear_bf16: a library GEMM spends 9-14 us on 64 rows); a LayerNorm is the
+    same launch on any rows.  A method takes the row views it reads and writes and issues one launch on the current
+    stream: the drivers (DinoV2._blocks_side_chain, _blocks_in_stream, _forward_hip) decide only order, stream and buffers.
+    The residual add lives in the proj / fc2 GEMM (beta = 1, in place: the f32 accumulator is added to the stream before
+    the single bf16 rounding) and their biases never enter the bf16 stream: the running sum of the biases is a static [C]
+    f32 vector per LayerNorm (DinoV2._cumulative_bias), added inside the kernel (vpr_bias_layernorm_bf16)."""
+    def __init__(self, m: "DinoV2", blk: Block, nxt: nn.LayerNorm, bias_att: torch.Tensor, bias_mlp: torch.Tensor):
+        self.m, self.blk = m, blk
+        self.lin, self.norm, self.bias = (blk.proj, blk.fc2), (blk.norm2, nxt), (bias_att, bias_mlp)     # by half
+
+    def qkv(self, part: int, h: torch.Tensor, out: torch.Tensor) -> None:
+        lin = self.blk.qkv
+        if part == CLS:
+            ops.skinny_linear_bf16(h, lin.weight, lin.bias, out, 0)
+        else:
+            torch.addmm(lin.bias, h, lin.weight.t(), out=out)
+
+    def add(self, half: int, part: int, a: torch.Tensor, x: torch.Tensor, row_stats: Optional[torch.Tensor] = None) -> None:
+        """x += a W^T (proj / fc2).  row_stats (CLS): the launch also leaves these rows' statistics partials for ln(half)."""
+        w = self.lin[half].weight
+        if part == CLS:
+            ops.skinny_linear_bf16(a, w, None, x, 2, None if row_stats is None else self.bias[half], row_stats)
+        else:
+            x.addmm_(a, w.t())
+
+    def ln(self, half: int, x: torch.Tensor, cls_linear: Optional[tuple] = None) -> torch.Tensor:
+        """The LayerNorm that ends a half, on rows x.  cls_linear = (first cls row, row_stats, ClsLinearConsts, out): the CLS
+        form of the stage that follows (fc1 + GELU / the next qkv) rides in the launch (vpr_bias_layernorm_cls_linear_bf16)."""
+        n = self.norm[half]
+        if cls_linear is None:
+            return ops.bias_layernorm_bf16(x, self.bias[half], n.weight, n.bias, n.eps)
+        return ops.bias_layernorm_cls_linear_bf16(x, self.bias[half], n.weight, n.bias, n.eps, *cls_linear, gelu=half == ATT)
+
+    def fc1(self, part: int, h: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """GELU(h Wfc1^T + b) in the form DinoV2.gelu names, into `out` or a new tensor of the current stream's allocator pool."""
+        lin, gelu = self.blk.fc1, self.m.gelu
+        if gelu not in ("tanh", "erf"):
+            raise ValueError("DinoV2.gelu must be 'tanh' or 'erf'")
+        if part == CLS:
+            out = h.new_empty((h.shape[0], lin.weight.shape[0])) if out is None else out
+            return ops.skinny_linear_bf16(h, lin.weight, lin.bias, out, 1 if gelu == "tanh" else 4)
+        if gelu == "tanh":
+            return torch._addmm_activation(lin.bias, h, lin.weight.t(), use_gelu=True, out=out)
+        return torch._C._nn.gelu_(torch.addmm(lin.bias, h, lin.weight.t(), out=out))
+
+    def rows(self, part: int, att: torch.Tensor, x: torch.Tensor, nst: Optional["_BlockStages"] = None, qkv_next=None) -> torch.Tensor:
+        """Everything between this block's attention and the next one on ONE row range (att, x, qkv_next: its rows), in
+        order; nst: the next block's stages, None after the last block.  -> the normalised rows."""
+        self.add(ATT, part, att, x)
+        hh = self.fc1(part, self.ln(ATT, x))
+        self.add(MLP, part, hh, x)
+        h = self.ln(MLP, x)
+        if nst is not None:
+            nst.qkv(part, h, qkv_next)
+        return h
+
+
 class DinoV2(nn.Module):
     def __init__(self, arch: str = "vit_large", img_size: int = 224, patch: int = 14):
         super().__init__()
@@ -173,25 +246,16 @@ class DinoV2(nn.Module):
     # loop is always erf.  evaluate.py (reference checkpoints) selects "erf"; bench.py keeps the default.
     gelu = "tanh"
 
-    def _fc1_gelu(self, blk: "Block", h: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if self.gelu == "tanh":
-            if out is None:
-                return torch._addmm_activation(blk.fc1.bias, h, blk.fc1.weight.t(), use_gelu=True)
-            return torch._addmm_activation(blk.fc1.bias, h, blk.fc1.weight.t(), use_gelu=True, out=out)
-        if self.gelu != "erf":
-            raise ValueError("DinoV2.gelu must be 'tanh' or 'erf'")
-        hh = torch.addmm(blk.fc1.bias, h, blk.fc1.weight.t()) if out is None else torch.addmm(blk.fc1.bias, h, blk.fc1.weight.t(), out=out)
-        return torch._C._nn.gelu_(hh)
-
-    @property
-    def _skinny_gelu_mode(self) -> int:
-        return 1 if self.gelu == "tanh" else 4
-
     auto_fold = True        # fold LayerScale at the first bf16 GPU forward after a load, so a freshly loaded checkpoint never
                             # lands on the slow PyTorch block loop by accident (bench.py --no-fold turns it off for the A/B)
     hip_split = True
+    # Two switches of the in-stream schedule (cls_side_chain = False).  cls_after_gemm: each cls-row launch comes right AFTER
+    # the library GEMM that used the same weight matrix (the 2-8 MB it streams could then be cache-resident); measured equal
+    # to "before": 11.20 / 11.16 vs 11.12 / 11.17 ms per step — the launches are latency-, not bandwidth-bound.  fuse_ln_cls:
+    # the two cls-row linears that directly follow a LayerNorm (qkv, fc1) ride in its launch (vpr_bias_layernorm_cls_linear_bf16):
+    # 0.03-0.05 ms per step, 11.17/11.23 vs 11.22/11.26 — within noise, so the simpler path is the default
     cls_after_gemm = True
-    fuse_ln_cls = False     # measured: 11.17/11.23 vs 11.22/11.26 ms per step — within noise, so the simpler path is the default
+    fuse_ln_cls = False
 
     def _hip_split_ok(self, img: torch.Tensor) -> bool:
         P, C = self.patch, self.embed_dim
@@ -199,7 +263,7 @@ class DinoV2(nn.Module):
                 and img.shape[2] % P == 0 and img.shape[3] % P == 0 and img.shape[3] % 8 == 0
                 and (img.shape[2] // P) * (img.shape[3] // P) == self.num_patches
                 and img.shape[1] * P * img.shape[3] * 2 <= 48 * 1024
-                and C % 8 == 0 and C <= 2048 and C // self.blocks[0].heads == 64 and 1 + self.num_patches <= 288
+                and _ln_width_ok(C) and _hip_attention_ok(C // self.blocks[0].heads, 1 + self.num_patches)
                 and all(b.folded for b in self.blocks))
 
     def _embed_consts(self, img: torch.Tensor):
@@ -227,7 +291,6 @@ class DinoV2(nn.Module):
         """This module's graph-safe cache `name` (_cache.Cache), made on first use; kept out of the module's attributes proper."""
         c = self.__dict__.get(name)
         if c is None:
-            from . import ops
             c = self.__dict__[name] = ops.cache(capacity)
         return c
 
@@ -235,20 +298,23 @@ class DinoV2(nn.Module):
     side_sync = "events"        # fork / join of the cls side chain (_streams): "events" (torch.cuda.Event), "light" (HIP events without the
                                 # system-scope fence), "signals" (stream memory operations: measured SLOWER in the step).  bench.py --side-sync
 
-    def _blocks_side_chain(self, x: torch.Tensor, h: torch.Tensor, cum: torch.Tensor, B: int, n: int, C: int) -> "SplitTokens":
-        """The 24 blocks with the cls rows on their own stream.  Between two attentions the B cls rows need six
-        small kernels (proj, LayerNorm, fc1, fc2, LayerNorm, next qkv: ~40 us) that depend on nothing but the cls
-        rows of the attention output; in-stream they cost 0.8 ms per step, almost all of it launch latency.  Here
-        the side stream is forked right after each attention and joined right before the next one, ~375 us of
-        patch-row GEMMs later, so the join never waits (an earlier attempt forked and joined around every single
-        cls-row launch and lost 0.6 ms to cross-queue waits).  The main stream touches only patch rows
-        (x[:Mp], LayerNorm on the patch slice), the side stream only cls rows: no shared writes.
-        Lifetimes: `att` (read by the side stream) and `qkv_next` (written by it) stay referenced until after
-        the join; side-stream temporaries come from that stream's allocator pool."""
-        from . import ops
-        Mp, M = B * n, B * n + B
-        dev, bf = x.device, torch.bfloat16
-        blocks = self.blocks
+    def _stages(self, device: torch.device, deferred_biases: bool = True) -> list:
+        """The blocks as _BlockStages, each with the LayerNorm that follows it and its two cumulative-bias rows."""
+        cum = self._cumulative_bias(device).unbind(0) if deferred_biases else [None] * (2 * len(self.blocks))
+        norms = [b.norm1 for b in self.blocks][1:] + [self.norm]
+        return [_BlockStages(self, blk, nxt, cum[2 * i], cum[2 * i + 1]) for i, (blk, nxt) in enumerate(zip(self.blocks, norms))]
+
+    def _blocks_side_chain(self, stages: list, x: torch.Tensor, h: torch.Tensor, B: int, n: int) -> "SplitTokens":
+        """The blocks with the cls rows on their own stream.  Between two attentions the B cls rows need six small kernels
+        (_BlockStages.rows: ~40 us) that depend on nothing but the cls rows of the attention output; in-stream they cost
+        0.8 ms per step, almost all of it launch latency.  Here the side stream is forked right after each attention and
+        joined right before the next one, ~375 us of patch-row GEMMs later, so the join never waits (an earlier attempt forked
+        and joined around every single cls-row launch and lost 0.6 ms to cross-queue waits: 12.8 vs 12.2 ms per step).  The
+        main stream touches only patch rows, the side stream only cls rows: no shared writes.  Lifetimes: what the main
+        stream allocated and the side stream reads (`att`) or writes (`qkv_next`) stays referenced until after the join; the
+        side stream's temporaries (rows(CLS), inside the stream context) come from that stream's allocator pool, the patch
+        rows' (rows(PATCH), outside it, `hh` among them) from the main stream's.  Under graph capture fork / join are "events"."""
+        Mp, C, dev = B * n, self.embed_dim, x.device
         main = torch.cuda.current_stream(dev)
         # high priority: the cls-row workgroups take the first CU slots a retiring GEMM workgroup frees (the
         # library GEMMs fill every CU, so at equal priority the small kernels sit in the queue: 40-95 us each)
@@ -257,45 +323,24 @@ class DinoV2(nn.Module):
         if mode not in ("events", "light", "signals"):
             raise RuntimeError(f"DinoV2.side_sync: unknown mode {mode!r}")
         sync = _streams.fork_join(dev, main.cuda_stream, mode)      # "events": a fresh object; else kept per main stream
-        C3, C4 = blocks[0].qkv.weight.shape[0], blocks[0].fc1.weight.shape[0]
         xp, xc = x[:Mp], x[Mp:]
-        hp = h[:Mp]
-        qkv = torch.empty((M, C3), dtype=bf, device=dev)
-        torch.addmm(blocks[0].qkv.bias, hp, blocks[0].qkv.weight.t(), out=qkv[:Mp])
-        ops.skinny_linear_bf16(h[Mp:], blocks[0].qkv.weight, blocks[0].qkv.bias, qkv[Mp:], 0)
-        cls_out, hooked = None, False
-        for i, blk in enumerate(blocks):
-            last = i + 1 == len(blocks)
-            nb = blocks[i + 1] if not last else None
-            nxt = nb.norm1 if not last else self.norm
-            att = ops.attention_qkv_split_bf16(qkv, B, 1 + n, n, blk.heads)
-            qkv_next = torch.empty((M, C3), dtype=bf, device=dev) if not last else None
+        qkv = torch.empty((Mp + B, 3 * C), dtype=torch.bfloat16, device=dev)
+        stages[0].qkv(PATCH, h[:Mp], qkv[:Mp])
+        stages[0].qkv(CLS, h[Mp:], qkv[Mp:])
+        for st, nst in zip(stages, stages[1:] + [None]):
+            att = ops.attention_qkv_split_bf16(qkv, B, 1 + n, n, st.blk.heads)
+            qkv_next = torch.empty_like(qkv) if nst is not None else None
             sync.fork(main, side)
             with torch.cuda.stream(side):
-                ops.skinny_linear_bf16(att[Mp:], blk.proj.weight, None, xc, 2)
-                hc = ops.bias_layernorm_bf16(xc, cum[2 * i], blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
-                hhc = torch.empty((B, C4), dtype=bf, device=dev)
-                ops.skinny_linear_bf16(hc, blk.fc1.weight, blk.fc1.bias, hhc, self._skinny_gelu_mode)
-                ops.skinny_linear_bf16(hhc, blk.fc2.weight, None, xc, 2)
-                hc2 = ops.bias_layernorm_bf16(xc, cum[2 * i + 1], nxt.weight, nxt.bias, nxt.eps)
-                if not last:
-                    ops.skinny_linear_bf16(hc2, nb.qkv.weight, nb.qkv.bias, qkv_next[Mp:], 0)
-                else:
-                    cls_out = hc2
-                    if self.cls_tail_hook is not None:     # e.g. SALAD's token MLP: needs the cls rows only, rides on this stream
-                        self.cls_tail_hook(cls_out, main.cuda_stream, n)
-                        hooked = True
+                hc = st.rows(CLS, att[Mp:], xc, nst, qkv_next[Mp:] if nst is not None else None)
+                hooked = nst is None and self.cls_tail_hook is not None
+                if hooked:                  # e.g. SALAD's token MLP: needs the final cls rows only, rides on this stream
+                    self.cls_tail_hook(hc, main.cuda_stream, n)
                 joined = sync.mark(side)
-            xp.addmm_(att[:Mp], blk.proj.weight.t())
-            hp = ops.bias_layernorm_bf16(xp, cum[2 * i], blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
-            hh = self._fc1_gelu(blk, hp)
-            xp.addmm_(hh, blk.fc2.weight.t())
-            hp = ops.bias_layernorm_bf16(xp, cum[2 * i + 1], nxt.weight, nxt.bias, nxt.eps)
-            if not last:
-                torch.addmm(nb.qkv.bias, hp, nb.qkv.weight.t(), out=qkv_next[:Mp])
+            hp = st.rows(PATCH, att[:Mp], xp, nst, qkv_next[:Mp] if nst is not None else None)
             sync.join(main, joined)        # the side chain finished ~0.3 ms ago: satisfied on arrival
             qkv = qkv_next                 # (att stayed referenced up to here)
-        return SplitTokens(hp.view(B, n, C), cls_out, hooked)
+        return SplitTokens(hp.view(B, n, C), hc, hooked)
 
     # optional callable(cls_rows [B, C] bf16, raw handle of the main stream, patch tokens per image n): run on the cls-row side
     # stream right after the final LayerNorm of the cls rows, before that stream is joined (modules.DinoV2Salad installs SALAD's token MLP here)
@@ -310,134 +355,84 @@ class DinoV2(nn.Module):
         * patch embedding = HIP patchify + one GEMM (instead of MIOpen's implicit-GEMM conv +
           transposes + cat + add); cls / position / conv-bias terms are a static additive matrix
           consumed by the first LayerNorm kernel, which writes the residual stream anyway;
-        * the residual add lives in the proj / fc2 GEMM (`x.addmm_`, beta = 1, in place) and their
-          biases never enter the bf16 stream: their running sum is a static [C] f32 vector per
-          LayerNorm, added inside the kernel (vpr_bias_layernorm_bf16);
-        * bias + GELU in the fc1 GEMM epilogue (hipBLASLt's tanh form; vs an f32 reference the max
-          error equals erf-GELU's 0.016: bf16 rounding dominates);
+        * the blocks: _BlockStages, driven by _blocks_side_chain (default) or _blocks_in_stream; bias + GELU in the fc1 GEMM
+          epilogue (hipBLASLt's tanh form; vs an f32 reference the max error equals erf-GELU's 0.016: bf16 rounding dominates);
         * attention: vpr_attention_qkv_split_bf16 (token -> row mapping inside the kernel)."""
-        from . import ops
         B, n, C, P = img.shape[0], self.num_patches, self.embed_dim, self.patch
-        Mp, M = B * n, B * n + B
-        dev, bf = img.device, torch.bfloat16
+        Mp, M, dev = B * n, B * n + B, img.device
         w, off = self._embed_consts(img)
         a = ops.patchify_bf16(img.contiguous(), P, w.shape[1], 0)               # [Mp, kpad]
         raw = ops.zero_rows_bf16(M, C, dev)         # persistent per (device, stream, shape): its cls rows are zero and nothing ever writes them
         torch.mm(a, w.t(), out=raw[:Mp])
-        blocks = self.blocks
-        n0 = blocks[0].norm1
+        n0 = self.blocks[0].norm1
         x, h = ops.add_layernorm_bf16(raw, off, n0.weight, n0.bias, n0.eps)
-        cum = self._cumulative_bias(dev)
+        run = self._blocks_side_chain if self.cls_side_chain else self._blocks_in_stream
+        return run(self._stages(dev), x, h, B, n)
 
-        if self.cls_side_chain:
-            return self._blocks_side_chain(x, h, cum, B, n, C)
-
-        # patch rows: library GEMMs; cls rows: vpr_skinny_linear_bf16 (a library GEMM spends 9-14 us on 64 rows).
-        # cls_after_gemm: each cls-row launch comes right AFTER the library GEMM that used the same weight
-        # matrix (the 2-8 MB it streams could then be cache-resident).  Measured equal to "before":
-        # 11.20 / 11.16 vs 11.12 / 11.17 ms per step — the launches are latency-, not bandwidth-bound.
-        # Tried and dropped: proj over all B*n + B rows in one GEMM (50 us vs 38 + 8); the cls-row kernels on
-        # a side stream (cross-queue waits: 12.8 vs 12.2 ms/step).
-        # fuse_ln_cls (option): the two cls-row linears that directly follow a LayerNorm (qkv, fc1) ride in
-        # the LayerNorm's launch (vpr_bias_layernorm_cls_linear_bf16): 0.03-0.05 ms per step, default off.
+    def _blocks_in_stream(self, stages: list, x: torch.Tensor, h: torch.Tensor, B: int, n: int) -> "SplitTokens":
+        """The blocks on one stream: every LayerNorm is one launch over all rows, every GEMM stage its PATCH and its CLS
+        launch in the order `cls_after_gemm` says.  With `fuse_ln_cls` the CLS launches of fc1 and qkv ride in the
+        LayerNorm before them, and the CLS launches of proj and fc2 leave that LayerNorm's statistics partials in `rs`.
+        Tried and dropped: proj over all B*n + B rows in one GEMM (50 us vs 38 + 8)."""
+        Mp, M, C = B * n, B * n + B, self.embed_dim
         fuse = self.fuse_ln_cls and C % 32 == 0 and self.gelu == "tanh"     # the fused launch has the tanh form only
-        after = self.cls_after_gemm
-        rs = torch.empty((C // 16, B, 2), dtype=torch.float32, device=dev) if fuse else None   # stream-ordered reuse
-        fc = self._cls_fused_consts(dev) if fuse else None
-        C3, C4 = blocks[0].qkv.weight.shape[0], blocks[0].fc1.weight.shape[0]
-
-        def pair(big, small, do_small=True):     # the library GEMM on the patch rows and the cls-row launch, in either order
-            if do_small and not after:
-                small()
-            big()
-            if do_small and after:
-                small()
-
-        qkv = torch.empty((M, C3), dtype=bf, device=dev)
-        cls_qkv_pending = True                   # False once a fused LayerNorm launch has produced qkv[Mp:]
-        for i, blk in enumerate(blocks):
-            last = i + 1 == len(blocks)
-            pair(lambda: torch.addmm(blk.qkv.bias, h[:Mp], blk.qkv.weight.t(), out=qkv[:Mp]),
-                 lambda: ops.skinny_linear_bf16(h[Mp:], blk.qkv.weight, blk.qkv.bias, qkv[Mp:], 0), cls_qkv_pending)
-            att = ops.attention_qkv_split_bf16(qkv, B, 1 + n, n, blk.heads)
-            pair(lambda: x[:Mp].addmm_(att[:Mp], blk.proj.weight.t()),
-                 lambda: ops.skinny_linear_bf16(att[Mp:], blk.proj.weight, None, x[Mp:], 2, cum[2 * i] if fuse else None, rs))
-            hh = torch.empty((M, C4), dtype=bf, device=dev)
-            n2 = blk.norm2
-            if fuse:
-                h = ops.bias_layernorm_cls_linear_bf16(x, cum[2 * i], n2.weight, n2.bias, n2.eps, Mp, rs,
-                                                       fc[2 * i + 1], hh[Mp:], gelu=True)
-            else:
-                h = ops.bias_layernorm_bf16(x, cum[2 * i], n2.weight, n2.bias, n2.eps)
-            pair(lambda: self._fc1_gelu(blk, h[:Mp], out=hh[:Mp]),
-                 lambda: ops.skinny_linear_bf16(h[Mp:], blk.fc1.weight, blk.fc1.bias, hh[Mp:], self._skinny_gelu_mode), not fuse)
-            pair(lambda: x[:Mp].addmm_(hh[:Mp], blk.fc2.weight.t()),
-                 lambda: ops.skinny_linear_bf16(hh[Mp:], blk.fc2.weight, None, x[Mp:], 2,
-                                                cum[2 * i + 1] if fuse and not last else None, rs if not last else None))
-            if not last:
-                nb = blocks[i + 1]
-                qkv = torch.empty((M, C3), dtype=bf, device=dev)
-                if fuse:
-                    h = ops.bias_layernorm_cls_linear_bf16(x, cum[2 * i + 1], nb.norm1.weight, nb.norm1.bias, nb.norm1.eps,
-                                                           Mp, rs, fc[2 * i + 2], qkv[Mp:])
-                else:
-                    h = ops.bias_layernorm_bf16(x, cum[2 * i + 1], nb.norm1.weight, nb.norm1.bias, nb.norm1.eps)
-                cls_qkv_pending = not fuse
-            else:
-                h = ops.bias_layernorm_bf16(x, cum[2 * i + 1], self.norm.weight, self.norm.bias, self.norm.eps)
+        order = (PATCH, CLS) if self.cls_after_gemm else (CLS, PATCH)
+        rs = torch.empty((C // 16, B, 2), dtype=torch.float32, device=x.device) if fuse else None   # stream-ordered reuse
+        fc = self._cls_fused_consts(x.device) if fuse else None
+        parts = lambda t: (t[:Mp], t[Mp:])       # a tensor's (PATCH rows, CLS rows)
+        xs = parts(x)
+        qkv = x.new_empty((M, 3 * C))
+        cls_qkv_done = False                     # True once a fused LayerNorm launch has produced qkv[Mp:]
+        for i, (st, nst) in enumerate(zip(stages, stages[1:] + [None])):
+            hs, qs = parts(h), parts(qkv)
+            for part in order if not cls_qkv_done else (PATCH,):
+                st.qkv(part, hs[part], qs[part])
+            atts = parts(ops.attention_qkv_split_bf16(qkv, B, 1 + n, n, st.blk.heads))
+            for part in order:
+                st.add(ATT, part, atts[part], xs[part], rs)
+            hhs = parts(x.new_empty((M, st.blk.fc1.weight.shape[0])))
+            hs = parts(st.ln(ATT, x, (Mp, rs, fc[2 * i + 1], hhs[CLS]) if fuse else None))
+            for part in order if not fuse else (PATCH,):
+                st.fc1(part, hs[part], hhs[part])
+            for part in order:
+                st.add(MLP, part, hhs[part], xs[part], rs if nst is not None else None)
+            if nst is not None:
+                qkv = x.new_empty((M, 3 * C))
+            cls_qkv_done = fuse and nst is not None
+            h = st.ln(MLP, x, (Mp, rs, fc[2 * i + 2], qkv[Mp:]) if cls_qkv_done else None)
         return SplitTokens(h[:Mp].view(B, n, C), h[Mp:])
 
-    gelu_in_epilogue = True
-
     def _hip_ok(self, x: torch.Tensor) -> bool:
-        return (x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048
-                and all(b.folded for b in self.blocks))
+        return x.is_cuda and x.dtype == torch.bfloat16 and _ln_width_ok(x.shape[-1]) and all(b.folded for b in self.blocks)
 
     residual_in_gemm = True
 
     def _forward_hip(self, x: torch.Tensor) -> torch.Tensor:
-        """Same math as the block loop, with x carrying the residual stream and h the normalised copy.
-        residual_in_gemm: the residual add lives in the proj / fc2 GEMM (`x.addmm_(a, W^T)`, beta = 1,
-        in place: the f32 accumulator is added to the stream before the single bf16 rounding) and
-        their biases are not written into the stream at all: the running sum of the biases is a
-        static [C] f32 vector per LayerNorm, added inside the kernel (vpr_bias_layernorm_bf16).
-        Per block that is LN r1 w1 twice (67 MB each) instead of add+LN r2 w2 (135 MB each), for
-        ~8 us of extra C reads in the two GEMMs.  Otherwise: every residual add fused into the
-        LayerNorm that follows it (vpr_add_layernorm_bf16)."""
-        from . import ops
+        """The cls-first layout [B, T, C]: same math as the block loop, with x carrying the residual stream and h the normalised
+        copy.  residual_in_gemm: _BlockStages.rows on one row range, all B*T rows in their PATCH forms: per block LN r1 w1 twice
+        (67 MB each) instead of add+LN r2 w2 (135 MB each), for ~8 us of extra C reads in the two GEMMs.  Otherwise: biased proj /
+        fc2, every residual add fused into the LayerNorm that follows it (vpr_add_layernorm_bf16).  qkv stays blk.qkv(h) either way."""
         B, T, C = x.shape
         x = x.contiguous()
-        blocks = self.blocks
-        n0 = blocks[0].norm1
+        n0 = self.blocks[0].norm1
         h = ops.layernorm_bf16(x, n0.weight, n0.bias, n0.eps)
-        hip_attn = (C // blocks[0].heads == 64) and T <= 288      # the short-sequence HIP kernel's domain
+
+        def attention(blk, h):
+            if _hip_attention_ok(C // blk.heads, T):
+                return ops.attention_qkv_bf16(blk.qkv(h), blk.heads)
+            qkv = blk.qkv(h).view(B, T, 3, blk.heads, C // blk.heads).permute(2, 0, 3, 1, 4)
+            return F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2]).transpose(1, 2).reshape(B, T, C)
+
+        stages = self._stages(x.device, self.residual_in_gemm)
         if self.residual_in_gemm:
-            cum = self._cumulative_bias(x.device)
             x2 = x.view(B * T, C)          # fresh tensor from forward(): safe to update in place
-        for i, blk in enumerate(blocks):
-            if hip_attn:
-                a = ops.attention_qkv_bf16(blk.qkv(h), blk.heads)
-            else:
-                qkv = blk.qkv(h).view(B, T, 3, blk.heads, C // blk.heads).permute(2, 0, 3, 1, 4)
-                a = F.scaled_dot_product_attention(qkv[0], qkv[1], qkv[2]).transpose(1, 2).reshape(B, T, C)
-            nxt = blocks[i + 1].norm1 if i + 1 < len(blocks) else self.norm
-            if self.residual_in_gemm:
-                x2.addmm_(a.view(B * T, C), blk.proj.weight.t())
-                h = ops.bias_layernorm_bf16(x2, cum[2 * i], blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
-                hh = self._fc1_gelu(blk, h)
-                x2.addmm_(hh, blk.fc2.weight.t())
-                h = ops.bias_layernorm_bf16(x2, cum[2 * i + 1], nxt.weight, nxt.bias, nxt.eps).view(B, T, C)
-                continue
-            y = blk.proj(a)
-            x, h = ops.add_layernorm_bf16(x, y, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
-            if self.gelu_in_epilogue:
-                # bias + GELU inside the fc1 GEMM epilogue (hipBLASLt's tanh form): removes a 270 MB
-                # elementwise pass per block.  Its deviation from erf-GELU (<= 3e-4) is below bf16
-                # resolution: against an f32 reference both forms measure the same max error (0.016).
-                hh = self._fc1_gelu(blk, h.view(B * T, C))
-                y = blk.fc2(hh).view(B, T, C)
-            else:
-                y = blk.fc2(F.gelu(blk.fc1(h)))
+            for st in stages:
+                h = st.rows(PATCH, attention(st.blk, h).view(B * T, C), x2).view(B, T, C)
+            return h
+        for st in stages:
+            blk, (n2, nxt) = st.blk, st.norm
+            x, h = ops.add_layernorm_bf16(x, blk.proj(attention(blk, h)), n2.weight, n2.bias, n2.eps)
+            y = blk.fc2(st.fc1(PATCH, h.view(B * T, C))).view(B, T, C)
             x, h = ops.add_layernorm_bf16(x, y, nxt.weight, nxt.bias, nxt.eps)
         return h.view(B, T, C)
 
@@ -450,7 +445,6 @@ class DinoV2(nn.Module):
         return self._cache("_clsf", 2).get((device, tensor_key(*ps)), self._build_cls_fused_consts, (device,), ps)
 
     def _build_cls_fused_consts(self, device: torch.device) -> list:
-        from . import ops
         cum = self._cumulative_bias(device)
         out = []
         for i, b in enumerate(self.blocks):
