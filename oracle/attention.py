@@ -44,3 +44,37 @@ def to_split_rows(x: torch.Tensor, body_tokens: int) -> torch.Tensor:
 def from_split_rows(rows: torch.Tensor, B: int, T: int, body_tokens: int) -> torch.Tensor:
     """Split-layout rows [B*T, F] -> token-ordered [B, T, F]."""
     return rows[split_row_index(B, T, body_tokens).to(rows.device)]
+
+
+# ---- per-element error bound of the HIP attention kernel (tests/test_attention_edges_gpu.py states the model) ----
+U_BF16 = 2.0 ** -8                    # bf16 unit roundoff
+SCALE = 0.125
+GATE = 2e-2                           # the project's absolute gate on attention outputs (randn-scale V)
+
+
+def half_ulp(x: torch.Tensor) -> torch.Tensor:
+    """Half the bf16 spacing at |x| (the most one RNE rounding to bf16 can move x), at least at the smallest normal."""
+    return torch.ldexp(torch.ones_like(x), torch.frexp(x.clamp_min(2.0 ** -126)).exponent - 9)
+
+
+def bound(qkv: torch.Tensor, H: int, scale: float = SCALE, terms: int = 288, gate: float = GATE):
+    """(bound, exact output), both [B, T, H*64] f64, of attention on qkv [B, T, 3*H*64]: p_k rounded once to bf16
+    (u / (1 - u) · Σ_k w_k |v_kd - o_d|), f32 logits ((e^2ε - 1) · the same sum), `terms` f32 additions in the row sum
+    and P·V (the kernel pads every sequence to 288 keys), one bf16 rounding of the output; never above `gate`."""
+    B, T, _ = qkv.shape
+    q, k, v = qkv.double().reshape(B, T, 3, H, HEAD_DIM).permute(2, 0, 3, 1, 4)   # [B, H, T, 64]
+    s = q @ k.transpose(-1, -2) * scale
+    w = torch.softmax(s, dim=-1)                                                  # stable in f64
+    o = w @ v
+    mad = torch.empty_like(o)                                                     # Σ_k w_k |v_kd - o_d|
+    for i in range(0, T, 32):
+        mad[:, :, i:i + 32] = (w[:, :, i:i + 32, :, None] * (v[:, :, None] - o[:, :, i:i + 32, None]).abs()).sum(3)
+    dot_abs = (q.abs() @ k.abs().transpose(-1, -2)).amax(dim=-1, keepdim=True)  # max_k Σ_d |q_d k_d|
+    eps = 2 * 64 * 2.0 ** -24 * scale * dot_abs + 2.0 ** -22
+    vmax = v.abs().amax(dim=2, keepdim=True)                                      # [B, H, 1, 64]
+    pre = (U_BF16 / (1 - U_BF16) + torch.expm1(2 * eps)) * mad + 2 * terms * 2.0 ** -24 * vmax
+    bnd = pre + half_ulp(o.abs() + pre)
+    if gate is not None:
+        bnd = bnd.clamp_max(gate)
+    to_tok = lambda t: t.transpose(1, 2).reshape(B, T, H * HEAD_DIM)
+    return to_tok(bnd), to_tok(o)

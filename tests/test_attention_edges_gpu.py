@@ -26,9 +26,8 @@ from oracle import attention as oattn
 
 pytestmark = pytest.mark.gpu
 
-U = 2.0 ** -8                         # bf16 unit roundoff
-SCALE = 0.125
-GATE = 2e-2                           # the absolute gate of the existing randn attention test
+SCALE, GATE = oattn.SCALE, oattn.GATE  # GATE: the absolute gate of the existing randn attention test
+_bound = oattn.bound                  # the error model above, shared with the backbone stage tests
 C_SWEEP = (-200.0, -96.0, -40.0, -24.0, -16.0, -12.0, -8.0, 0.0, 8.0, 40.0, 200.0)   # all exact in bf16
 T_SWEEP = (1, 2, 15, 16, 17, 31, 33, 100, 255, 256, 257, 287, 288)
 
@@ -47,30 +46,6 @@ def _forced_qkv(B, T, H, c, seed, v_scale=1.0):
 def _mixed_offsets(B, T, H, seed):
     g = torch.Generator().manual_seed(seed)
     return torch.tensor(C_SWEEP)[torch.randint(0, len(C_SWEEP), (B, T, H), generator=g)]
-
-
-def _half_ulp(x):
-    """Half the bf16 spacing at |x| (the most one RNE rounding to bf16 can move x), at least at the smallest normal."""
-    return torch.ldexp(torch.ones_like(x), torch.frexp(x.clamp_min(2.0 ** -126)).exponent - 9)
-
-
-def _bound(qkv, H, scale=SCALE):
-    """The error bound of the module docstring, [B, T, H*64] f64, and the exact output."""
-    B, T, _ = qkv.shape
-    q, k, v = qkv.double().reshape(B, T, 3, H, 64).permute(2, 0, 3, 1, 4)        # [B, H, T, 64]
-    s = q @ k.transpose(-1, -2) * scale
-    w = torch.softmax(s, dim=-1)                                                  # stable in f64
-    o = w @ v
-    mad = torch.empty_like(o)                                                     # Σ_k w_k |v_kd - o_d|
-    for i in range(0, T, 32):
-        mad[:, :, i:i + 32] = (w[:, :, i:i + 32, :, None] * (v[:, :, None] - o[:, :, i:i + 32, None]).abs()).sum(3)
-    dot_abs = (q.abs() @ k.abs().transpose(-1, -2)).amax(dim=-1, keepdim=True)  # max_k Σ_d |q_d k_d|
-    eps = 2 * 64 * 2.0 ** -24 * scale * dot_abs + 2.0 ** -22
-    vmax = v.abs().amax(dim=2, keepdim=True)                                      # [B, H, 1, 64]
-    pre = (U / (1 - U) + torch.expm1(2 * eps)) * mad + 2 * 288 * 2.0 ** -24 * vmax
-    bound = (pre + _half_ulp(o.abs() + pre)).clamp_max(GATE)
-    to_tok = lambda t: t.transpose(1, 2).reshape(B, T, H * 64)
-    return to_tok(bound), to_tok(o)
 
 
 def _check(out, qkv, H, what):

@@ -4,82 +4,19 @@ sequence below, which doubles as the documentation of the schedule: what is laun
 on which stream.  vit_small cut to its first 3 blocks (a first, an inner and a last block), B = 2 (the smallest batch at
 which the cls-row kernels see more than one row); 224 px for the split row layout [B*256 patch rows | B cls rows], 196 px
 (W % 8 != 0) for the cls-first layout [B, 197, C].  Recorded: the `ops` entry points the backbone calls, the library GEMM
-calls (torch.mm / addmm / _addmm_activation, Tensor.addmm_, F.linear), fork / join of the side chain and the cls tail hook.
+calls (torch.mm / addmm / _addmm_activation, Tensor.addmm_, F.linear), fork / join of the side chain and the cls tail hook
+(the recorder: tests/backbone_trace.py).
 A cls-row linear carries its mode (0 bias, 1 bias + tanh-GELU, 2 accumulate into the residual stream) and "+stats" where
 it also leaves LayerNorm statistics partials."""
 import pytest
-import torch
-import torch.nn.functional as F
+
+from backbone_trace import MAIN, SIDE, _on, _record
 
 pytestmark = pytest.mark.gpu
 
 B, L = 2, 3
 MP, M = B * 256, B * 257            # split row layout at 224 px: patch rows, all rows
 BT = B * 197                        # cls-first layout at 196 px
-MAIN, SIDE = "main", "side"
-
-
-class _Recorder:
-    OPS = ("patchify_bf16", "layernorm_bf16", "add_layernorm_bf16", "bias_layernorm_bf16", "bias_layernorm_cls_linear_bf16",
-           "skinny_linear_bf16", "attention_qkv_split_bf16", "attention_qkv_bf16")
-    LIBRARY = ((torch, "mm", 0), (torch, "addmm", 1), (torch, "_addmm_activation", 1), (torch.Tensor, "addmm_", 1), (F, "linear", 0))
-
-    def __init__(self, monkeypatch, dev):
-        from vpr_amd import _streams, ops
-        self.dev, self.main, self.calls = dev, torch.cuda.current_stream(dev), []
-        for name in self.OPS:
-            monkeypatch.setattr(ops, name, self._wrap(name, getattr(ops, name), 0))
-        for owner, name, operand in self.LIBRARY:
-            monkeypatch.setattr(owner, name, self._wrap(name, getattr(owner, name), operand))
-        for name in ("fork", "join"):                   # side_sync = "events": _TorchEvents does both
-            monkeypatch.setattr(_streams._TorchEvents, name, self._wrap(name, getattr(_streams._TorchEvents, name), None))
-
-    def note(self, name, rows):
-        self.calls.append((name, rows, MAIN if torch.cuda.current_stream(self.dev) == self.main else SIDE))
-
-    def _wrap(self, name, fn, operand):
-        def recorded(*args, **kwargs):
-            out = fn(*args, **kwargs)                   # the call still runs; nothing below launches anything
-            label, rows = name, None
-            if name == "patchify_bf16":
-                rows = out.shape[0]                     # the rows it makes (its input is the image batch)
-            elif operand is not None:
-                rows = args[operand].numel() // args[operand].shape[-1]
-            if name == "skinny_linear_bf16":
-                mode = args[4] if len(args) > 4 else kwargs.get("mode", 0)
-                stats = args[6] if len(args) > 6 else kwargs.get("row_stats")
-                label = f"skinny:{mode}" + ("+stats" if stats is not None else "")
-            self.note(label, rows)
-            return out
-        return recorded
-
-    def hook(self, cls_rows, main_raw, n):
-        self.note("cls_tail_hook", cls_rows.shape[0])
-
-
-def _record(dev, monkeypatch, img_size, **switches):
-    """-> (calls of one forward(split=True) after a warm-up forward, its SplitTokens)."""
-    from vpr_amd.backbone import DinoV2
-    torch.manual_seed(0)
-    m = DinoV2("vit_small", img_size=img_size).to(dev).to(torch.bfloat16).eval()
-    m.blocks = torch.nn.ModuleList(list(m.blocks)[:L])
-    m.fold_layerscale()
-    for name, value in switches.items():
-        assert hasattr(m, name)
-        setattr(m, name, value)
-    x = torch.randn(B, 3, img_size, img_size, device=dev, dtype=torch.bfloat16)
-    assert m._hip_split_ok(x) == (img_size == 224)
-    rec = _Recorder(monkeypatch, dev)
-    m.cls_tail_hook = rec.hook
-    m(x, split=True)                                    # builds the cached constants
-    rec.calls.clear()
-    out = m(x, split=True)
-    torch.cuda.synchronize()
-    return rec.calls, out
-
-
-def _on(stream, *calls):
-    return [(name, rows, stream) for name, rows in calls]
 
 
 # patch embedding: patchify, one GEMM into the patch rows of the zero-row buffer, add + LayerNorm (block 0's norm1) on all rows
