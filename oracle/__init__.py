@@ -18,6 +18,9 @@ Pinning status:
   * salad_stages.py         — the same MLPs stage by stage (hidden activations, partial-sum slabs, token features), inputs
     on which f32 arithmetic is exact in any order, and the per-element error bound of an f32-accumulating kernel; every
     property the GPU tests rely on is asserted on the oracle alone in tests/test_oracle_selfchecks.py.
+  * salad_f32_stages.py     — the f32-accurate path's stages: the three bf16 planes of an operand, the six-product plane
+    GEMM of both layers, its true-f64 statement, the outputs a wrong kernel would leave, and three input families on which
+    f32 accumulation is exact in any order; asserted on the oracle alone in tests/test_oracle_selfchecks.py as well.
   * knn.py                  — PARITY UNPINNED by the reference: it has no retrieval code at all
     (SURVEY.md fact 3).  Brute-force definition of the stage's contract.
 """

@@ -211,6 +211,12 @@ LOCAL_PROTOTYPES = {
                                  _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 
+# include/vpr_amd_salad_f32_stages.h, the ninth table: where the f32-accurate aggregation leaves planes, hidden values, S / F / g
+SALAD_F32_STAGES_PROTOTYPES = {
+    # workspace workspace_bytes | B n C m l t hidden | H Ht S F g | A1 cls3 W1 H2 | W1t W2s W2c W2t Ht2 (optional)
+    "vpr_salad_f32_stage_outputs": (c_int, [_P, c_size_t] + [c_int] * 7 + [_PP] * 14),
+}
+
 
 def rerank_roundings(D: int, rows_are_f32: bool) -> int:
     """VPR_RERANK_ROUNDINGS: L of the fine score, the roundings on the longest path from a product to the result."""
@@ -237,7 +243,7 @@ def lib() -> ctypes.CDLL:
                                           + list(EXPAND_PROTOTYPES.items()) + list(PROJECT_PROTOTYPES.items())
                                           + list(RERANK_PROTOTYPES.items()) + list(SALAD_STAGES_PROTOTYPES.items())
                                           + list(SALAD_ANYRES_PROTOTYPES.items()) + list(SALAD_HIRES_PROTOTYPES.items())
-                                          + list(LOCAL_PROTOTYPES.items())):
+                                          + list(LOCAL_PROTOTYPES.items()) + list(SALAD_F32_STAGES_PROTOTYPES.items())):
             fn = getattr(handle, name)   # AttributeError if a declared symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

@@ -737,6 +737,19 @@ static bool salad_f32_plan(int B, int n, int C, int m, int l, int t, int hidden,
   return true;
 }
 
+// The buffers of a plan inside a workspace: what salad_f32_run() writes and vpr_salad_f32_stage_outputs() names.
+struct SaladF32Buffers {
+  uint16_t *A1, *W1, *H2, *W2s, *W2c, *cls3, *W1t, *Ht2, *W2t;
+  float *H, *Ht, *S, *F, *g;
+};
+static SaladF32Buffers salad_f32_buffers(void* workspace, const SaladF32Plan& p) {
+  char* ws = static_cast<char*>(workspace);
+  auto u16 = [&](size_t off) { return reinterpret_cast<uint16_t*>(ws + off); };
+  auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+  return {u16(p.off_A1), u16(p.off_W1), u16(p.off_H2), u16(p.off_W2s), u16(p.off_W2c), u16(p.off_cls), u16(p.off_W1t),
+          u16(p.off_Ht2), u16(p.off_W2t), f32(p.off_H), f32(p.off_Ht), f32(p.off_S), f32(p.off_F), f32(p.off_g)};
+}
+
 }  // namespace vpr
 
 extern "C" size_t vpr_salad_f32_workspace_bytes(int B, int n, int C, int m, int l, int t, int hidden) {
@@ -763,12 +776,9 @@ static int salad_f32_run(SaladDomain domain, const float* patch, long long patch
   if (sinkhorn_iters < 1) return VPR_ERR_INVALID_ARG;
   if (n != SA_N && (!aligned4(out_f32) || (reinterpret_cast<uintptr_t>(out_bf16) & 1))) return VPR_ERR_UNSUPPORTED;   // the run-time-n kernels'
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  char* ws = static_cast<char*>(workspace);
-  auto u16 = [&](size_t off) { return reinterpret_cast<uint16_t*>(ws + off); };
-  auto f32 = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-  uint16_t *A1 = u16(p.off_A1), *W1 = u16(p.off_W1), *H2 = u16(p.off_H2), *W2s = u16(p.off_W2s), *W2c = u16(p.off_W2c);
-  uint16_t *cls3 = u16(p.off_cls), *W1t = u16(p.off_W1t), *Ht2 = u16(p.off_Ht2), *W2t = u16(p.off_W2t);
-  float *H = f32(p.off_H), *Ht = f32(p.off_Ht), *S = f32(p.off_S), *F = f32(p.off_F), *g = f32(p.off_g);
+  const SaladF32Buffers b = salad_f32_buffers(workspace, p);
+  uint16_t *A1 = b.A1, *W1 = b.W1, *H2 = b.H2, *W2s = b.W2s, *W2c = b.W2c, *cls3 = b.cls3, *W1t = b.W1t, *Ht2 = b.Ht2, *W2t = b.W2t;
+  float *H = b.H, *Ht = b.Ht, *S = b.S, *F = b.F, *g = b.g;
   const long long rows = (long long)B * n;
   const int K1 = 6 * C, K2 = 6 * hidden;
   // operand planes: tokens (row-group addressing resolved here, A1 is dense), cls rows, all five weight matrices
@@ -823,4 +833,29 @@ extern "C" int vpr_salad_aggregate_f32_hires(const float* patch, long long patch
                                              void* workspace, size_t workspace_bytes, void* stream) {
   return salad_f32_run(SaladDomain::HiRes, patch, patch_img_stride, cls, cls_stride, B, n, C, w, dustbin, m, l, t, hidden,
                        sinkhorn_iters, out_f32, out_bf16, workspace, workspace_bytes, stream);
+}
+
+// include/vpr_amd_salad_f32_stages.h: where salad_f32_run() leaves its planes, hidden values and stage-A operands — the
+// plan it runs on, nothing else; no launch, no device access.  The refusals salad_f32_run() makes on these arguments, in its
+// order, in the widest of its three domains (n == 256 and the any-n range lie inside the high-resolution one).
+extern "C" int vpr_salad_f32_stage_outputs(void* workspace, size_t workspace_bytes, int B, int n, int C, int m, int l, int t,
+                                           int hidden, float** H, float** Ht, float** S, float** F, float** g,
+                                           uint16_t** A1, uint16_t** cls3, uint16_t** W1, uint16_t** H2,
+                                           uint16_t** W1t, uint16_t** W2s, uint16_t** W2c, uint16_t** W2t, uint16_t** Ht2) {
+  if (!H || !Ht || !S || !F || !g || !A1 || !cls3 || !W1 || !H2) return VPR_ERR_INVALID_ARG;
+  if (!workspace || B <= 0 || n < 1 || C <= 0) return VPR_ERR_INVALID_ARG;
+  if (!salad_in_domain(SaladDomain::HiRes, n, m, l, t, C, hidden)) return VPR_ERR_UNSUPPORTED;
+  if (!aligned16(workspace)) return VPR_ERR_UNSUPPORTED;
+  SaladF32Plan p;
+  if (!salad_f32_plan(B, n, C, m, l, t, hidden, &p)) return VPR_ERR_INVALID_ARG;
+  if (workspace_bytes < p.total) return VPR_ERR_WORKSPACE;
+  const SaladF32Buffers b = salad_f32_buffers(workspace, p);
+  *H = b.H, *Ht = b.Ht, *S = b.S, *F = b.F, *g = b.g;
+  *A1 = b.A1, *cls3 = b.cls3, *W1 = b.W1, *H2 = b.H2;
+  if (W1t) *W1t = b.W1t;
+  if (W2s) *W2s = b.W2s;
+  if (W2c) *W2c = b.W2c;
+  if (W2t) *W2t = b.W2t;
+  if (Ht2) *Ht2 = b.Ht2;
+  return VPR_OK;
 }

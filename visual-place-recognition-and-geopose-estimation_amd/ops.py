@@ -363,6 +363,46 @@ def salad_aggregate_f32(tokens, w: SaladWeightsF32, sinkhorn_iters: int = 3,
     return _salad_whole("vpr_salad_aggregate_f32", torch.float32, tokens, w, sinkhorn_iters, want_bf16)
 
 
+class SaladF32StageViews(NamedTuple):
+    H: torch.Tensor                  # [B*n, 2*hidden] f32 hidden activations: score head, then cluster head
+    Ht: torch.Tensor                 # [B, hidden] f32 hidden activations of the token MLP
+    S: torch.Tensor                  # [B*n, m] f32 cluster scores (b2_s included)
+    F: torch.Tensor                  # [B*n, l] f32 cluster features
+    g: torch.Tensor                  # [B, t] f32 token features
+    A1: torch.Tensor                 # [B*n, 6, C] bf16 planes of the patch tokens, activation order (q h m m h h)
+    cls3: torch.Tensor               # [B, 6, C] bf16 planes of the cls rows, activation order
+    W1: torch.Tensor                 # [2*hidden, 6, C] bf16 planes of w1_sc, weight order (h q m h m h)
+    H2: torch.Tensor                 # [B*n, 2, 6, hidden] bf16 planes of H: head (score, cluster), segment, column
+    W1t: torch.Tensor                # [hidden, 6, C], weight order
+    W2s: torch.Tensor                # [m, 6, hidden]
+    W2c: torch.Tensor                # [l, 6, hidden]
+    W2t: torch.Tensor                # [t, 6, hidden]
+    Ht2: torch.Tensor                # [B, 6, hidden] bf16 planes of Ht, activation order
+
+
+def salad_f32_stage_views(ws: torch.Tensor, B: int, n: int, w: "SaladWeightsF32") -> SaladF32StageViews:
+    """Views of what the f32-accurate aggregation (salad_aggregate_f32, _f32_n, _f32_hires) left in its workspace `ws`
+    (ops.workspace("salad_f32", ...) of the stream that ran it) for a batch of B images x n patch tokens (tests).  The layout
+    comes from vpr_salad_f32_stage_outputs (include/vpr_amd_salad_f32_stages.h), which asks the library's own plan: nothing
+    about it is restated here but the shapes the header states."""
+    C, hidden, m, l, t = w.validate()
+    names = SaladF32StageViews._fields
+    ptrs = {k: ctypes.c_void_p(0) for k in names}
+    _call("vpr_salad_f32_stage_outputs", _ptr(ws), ws.numel(), B, n, C, m, l, t, hidden, *[ctypes.byref(ptrs[k]) for k in names])
+
+    def view(p: ctypes.c_void_p, dtype: torch.dtype, *shape: int) -> torch.Tensor:
+        off, count = p.value - ws.data_ptr(), 1
+        for s in shape:
+            count *= s
+        return ws[off: off + count * dtype.itemsize].view(dtype).view(*shape)
+
+    r, f, b = B * n, torch.float32, torch.bfloat16
+    shapes = dict(H=(f, r, 2 * hidden), Ht=(f, B, hidden), S=(f, r, m), F=(f, r, l), g=(f, B, t), A1=(b, r, 6, C), cls3=(b, B, 6, C),
+                  W1=(b, 2 * hidden, 6, C), H2=(b, r, 2, 6, hidden), W1t=(b, hidden, 6, C), W2s=(b, m, 6, hidden),
+                  W2c=(b, l, 6, hidden), W2t=(b, t, 6, hidden), Ht2=(b, B, 6, hidden))
+    return SaladF32StageViews(*[view(ptrs[k], *shapes[k]) for k in names])
+
+
 def _salad_stage_a(entry: str, scores: torch.Tensor, feats: torch.Tensor, tokfeat: torch.Tensor, dustbin: float, iters: int,
                    want_bf16: bool) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Stage A alone through `entry` (vpr_salad_sinkhorn_aggregate or its run-time-n form: the same parameter list)."""
