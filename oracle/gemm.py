@@ -12,6 +12,7 @@ Exact operands: small integers times powers of two such that every partial sum o
 multiple of the scale below 2^24 of it — f32 then sums exactly, the result does not depend on the summation order,
 and every kernel, tile form, K split and K walk must return f(s + b) rounded once: the f32 value itself, or its
 round-to-nearest-even bf16 (ties included: the integer sums above 256 land on bf16 ties often).
+exact_e4m3_operands is the same idea for the e4m3 score kernels (integer elements, power-of-two row scales).
 """
 import torch
 
@@ -78,6 +79,23 @@ def exact_operands(M, N, K, seed, with_bias=True):
     w = (torch.randint(-8, 9, (N, K), generator=g).double() / 4).to(torch.bfloat16)
     b = (torch.randint(-2048, 2049, (N,), generator=g).double() / 32).float() if with_bias else None
     return a, w, b
+
+
+def exact_e4m3_operands(B, N, D, seed):
+    """(q, q_scale, g, g_scale, want): e4m3 rows q [B, D], g [N, D] as uint8 with per-row f32 scales, and the f64 score
+    matrix want[b, n] = q_scale[b] g_scale[n] Σ_d q[b, d] g[n, d] that every e4m3 score kernel must return bit for bit.
+    Elements are integers in [-8, 8] (3 mantissa bits hold them all), so a product is an integer of magnitude <= 64 and
+    every partial sum of every order an integer below 64 D <= 2^15 for D <= 512: f32 accumulates exactly.  The scales are
+    powers of two that vary per row (2^-3 .. 2^-9 and 2^-2 .. 2^-6): acc * q_scale * g_scale only moves the exponent."""
+    assert D <= 512
+    gen = torch.Generator().manual_seed(seed)
+    qv = torch.randint(-8, 9, (B, D), generator=gen).float()
+    gv = torch.randint(-8, 9, (N, D), generator=gen).float()
+    q, g = qv.to(torch.float8_e4m3fn).view(torch.uint8), gv.to(torch.float8_e4m3fn).view(torch.uint8)
+    q_scale = torch.ldexp(torch.ones(B), -3 - torch.arange(B) % 7).float()
+    g_scale = torch.ldexp(torch.ones(N), -2 - torch.arange(N) % 5).float()
+    want = (qv.double() @ gv.double().T) * q_scale.double()[:, None] * g_scale.double()[None, :]
+    return q, q_scale, g, g_scale, want
 
 
 def random_operands(M, N, K, seed, with_bias=True):

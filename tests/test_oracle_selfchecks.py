@@ -328,6 +328,29 @@ def test_gemm_ref_resolves_row_groups():
     assert torch.equal(y, a.double() @ w.double().T)
 
 
+@pytest.mark.parametrize("B,N,D", [(150, 130, 128), (65, 3, 256), (512, 257, 512)])
+def test_exact_e4m3_operands_are_exact_in_any_order(B, N, D):
+    """The preconditions of the bit-for-bit e4m3 score test: the bytes decode to the integers they were cast from, the sum
+    of |products| of every score is below 2^24, both scale vectors are powers of two that vary per row, and the expected
+    value is an f32 number that f32 arithmetic reproduces in another summation order."""
+    q, qs, g, gs, want = ogemm.exact_e4m3_operands(B, N, D, seed=B + N + D)
+    qv, gv = q.view(torch.float8_e4m3fn).float(), g.view(torch.float8_e4m3fn).float()
+    for v in (qv, gv):
+        assert torch.equal(v, v.round()) and v.abs().max() == 8 and v.min() == -8
+        assert torch.equal(v.to(torch.float8_e4m3fn).float(), v)                      # the cast round-trips
+    assert (qv.double().abs() @ gv.double().abs().T).max() < 2 ** 24
+    for s in (qs, gs):
+        mant, _ = torch.frexp(s)
+        assert s.dtype == torch.float32 and torch.equal(mant, torch.full_like(s, 0.5)) and s.unique().numel() >= min(3, s.numel())
+    assert torch.equal(want, (qv.double() @ gv.double().T) * qs.double()[:, None] * gs.double()[None, :])
+    assert torch.equal(want.float().double(), want)
+    got = (torch.flip(qv, [1]) @ torch.flip(gv, [1]).T) * qs[:, None] * gs[None, :]    # f32, another order
+    assert torch.equal(got.double(), want)
+    one_off = want.clone()
+    one_off[B - 1, N - 1] += qs[B - 1].double() * gs[N - 1].double()                    # one unit of one product
+    assert not torch.equal(one_off.float().double(), want)
+
+
 # ------------------------------------------------------------------------- head bounds (oracle/heads.py)
 def _head_ratio(out, x, W1, b1, W2, b2, split, slices):
     from oracle import heads as oheads

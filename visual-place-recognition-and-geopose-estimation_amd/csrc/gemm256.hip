@@ -32,7 +32,7 @@ __device__ __forceinline__ int g2_w_row(int ge, bool late) { return (ge >> 2) * 
 
 // One operand fragment of a K-tile: the two 16-byte chunks (fch, fch + 4) of a tile row.  bf16: the operands of the two
 // 32-deep MFMAs of a 64-deep K-tile; fp8 (FP8 = true: e4m3 bytes, a 128-byte tile row = 128 K values): together the
-// 32-byte operand of ONE block-scaled v_mfma_scale_f32_16x16x128_f8f6f4 (unit scales) — same LDS image, same reads,
+// 32-byte operand of ONE block-scaled v_mfma_scale_f32_16x16x128_f8f6f4 (mfma_e4m3_16x16x128) — same LDS image, same reads,
 // the same 256 matrix-pipe cycles per phase for twice the K: the fp8 form of this kernel runs at twice the FLOP rate
 // on the same byte stream.
 struct G2Frag { bf16x8 lo, hi; };
@@ -42,13 +42,7 @@ __device__ __forceinline__ G2Frag g2_frag(const char* tile, int row, int fch) {
 template <bool FP8>
 __device__ __forceinline__ f32x4 g2_mma(const G2Frag& w, const G2Frag& a, f32x4 c) {
   if constexpr (FP8) {
-    typedef __attribute__((ext_vector_type(8))) int i32x8;
-    typedef __attribute__((ext_vector_type(4))) int i32x4;
-    const i32x4 w0 = __builtin_bit_cast(i32x4, w.lo), w1 = __builtin_bit_cast(i32x4, w.hi);
-    const i32x4 a0 = __builtin_bit_cast(i32x4, a.lo), a1 = __builtin_bit_cast(i32x4, a.hi);
-    const i32x8 wv = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
-    const i32x8 av = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wv, av, c, 0, 0, 0, 127, 0, 127);
+    return mfma_e4m3_16x16x128(e4m3_operand(w.lo, w.hi), e4m3_operand(a.lo, a.hi), c);
   } else {
     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.lo, a.lo, c, 0, 0, 0);
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(w.hi, a.hi, c, 0, 0, 0);
@@ -60,24 +54,22 @@ __device__ __forceinline__ f32x4 g2_mma(const G2Frag& w, const G2Frag& a, f32x4 
 // gathered batch against an e4m3 shard (BASELINE config 5 on 8 GPUs).
 typedef f32x4 G2Acc[2][2][4][2];   // [qi][qj][rb][cb]: rows n = wc*64 + qj*32 + cb*16 + 4g+e, cols m = wr*128 + qi*64 + rb*16 + lane&15
 
-// Tile mapping, staging set-up and the K loop of one 256 x 256 output tile; returns with every wave past the last MFMA
-// (the two wave groups re-aligned), the accumulators in `acc`, the LDS-DMA tail possibly still in flight.
 // VM = the counted wait of the pipeline: 10 LDS-DMA instructions (five 16 KB half-tiles) stay in flight behind every wait.
 // 6 / 2 (timing-only build, VPR_GEMM256_DEPTH): the same requests, waited for two / four half-tiles earlier than needed —
-// an ablation of the prefetch distance (gathered-batch score GEMM).
-template <int VM> __device__ __forceinline__ void g2_wait_vm() {
-  if constexpr (VM == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-  else if constexpr (VM == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-}
-template <int VM> __device__ __forceinline__ void g2_wait_vm_lgkm() {
-  if constexpr (VM == 10) asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory");
-  else if constexpr (VM == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
+// an ablation of the prefetch distance (gathered-batch score GEMM).  LGKM: this wave's LDS reads too.
+template <int VM, bool LGKM> __device__ __forceinline__ void g2_wait() {
+  if constexpr (LGKM) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" :: "n"(VM) : "memory");
+  else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(VM) : "memory");
 }
 
+// Where the workgroup's tile is (tn = its tile column) and who the thread is in it: what g2_mainloop worked out and an
+// epilogue goes on with.
+struct G2Tile { int m0, n0, tn, lane, wave, wr, wc; };
+
+// Tile mapping, staging set-up and the K loop of one 256 x 256 output tile; returns with every wave past the last MFMA
+// (the two wave groups re-aligned), the accumulators in `acc`, the LDS-DMA tail possibly still in flight.
 template <bool FP8, int VM = 10>
-__device__ __forceinline__ void g2_mainloop(const GemmProblem& pr, char* smem, G2Acc& acc, int& m0_out, int& n0_out, int& tn_out) {
+__device__ __forceinline__ G2Tile g2_mainloop(const GemmProblem& pr, char* smem, G2Acc& acc) {
   constexpr int ES = FP8 ? 1 : 2;                       // operand element size in bytes
   const char* __restrict__ A = reinterpret_cast<const char*>(pr.A);
   const char* __restrict__ W = reinterpret_cast<const char*>(pr.W);
@@ -114,7 +106,7 @@ __device__ __forceinline__ void g2_mainloop(const GemmProblem& pr, char* smem, G
       const bool isA = (h == 0 || h == 3), late = (h >= 2);
       const int row0 = isA ? g2_a_row(ge, late) : g2_w_row(ge, late);
       const int tr = row0 + (lane >> 3);
-      const int sw = ((lane & 7) ^ ((tr >> 1) & 7)) << 4;      // bytes
+      const int sw = stage_src_off(tr, lane);
       if (isA) {
         int r = m0 + tr;
         r = r < M ? r : M - 1;
@@ -182,7 +174,7 @@ __device__ __forceinline__ void g2_mainloop(const GemmProblem& pr, char* smem, G
   //        previous L segment, which precedes a barrier both groups pass before either reads it;
   //   WAR  a slot is refilled in the L segment after the one that read it, and every L segment
   //        ends with lgkmcnt(0), so both groups' reads are complete two barriers earlier.
-  g2_wait_vm<VM>();                                    // A-early / W-early of K-tile 0 (before ANY barrier)
+  g2_wait<VM, false>();                                    // A-early / W-early of K-tile 0 (before ANY barrier)
   if (wr == 1) __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_s_barrier();
   for (int kt = 0; kt < nk; ++kt) {
@@ -196,7 +188,7 @@ __device__ __forceinline__ void g2_mainloop(const GemmProblem& pr, char* smem, G
 #pragma unroll
     for (int rb = 0; rb < 4; ++rb) a[rb] = g2_frag(ta, wr * 128 + rb * 16 + frow, fch);
     issue(3, kt + 1);
-    g2_wait_vm_lgkm<VM>();                                          // retires W-late(kt) for phase 2
+    g2_wait<VM, true>();                                           // retires W-late(kt) for phase 2
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -210,7 +202,7 @@ __device__ __forceinline__ void g2_mainloop(const GemmProblem& pr, char* smem, G
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) b1[cb] = g2_frag(tw, wc * 64 + 32 + cb * 16 + frow, fch);
     issue(0, kt + 2);          // A-early slot: both groups' phase-1 reads completed two barriers ago
-    g2_wait_vm_lgkm<VM>();                                          // retires A-late(kt) for phase 3
+    g2_wait<VM, true>();                                           // retires A-late(kt) for phase 3
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -236,7 +228,7 @@ __device__ __forceinline__ void g2_mainloop(const GemmProblem& pr, char* smem, G
 
     // ---- phase 4: no new operands (W quadrant-col 0 is still in registers) ----
     issue(2, kt + 2);          // W-late slot (read in phase 2)
-    g2_wait_vm<VM>();                                               // retires A-early / W-early of K-tile kt+1
+    g2_wait<VM, false>();                                               // retires A-early / W-early of K-tile kt+1
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -247,42 +239,41 @@ __device__ __forceinline__ void g2_mainloop(const GemmProblem& pr, char* smem, G
     __builtin_amdgcn_s_barrier();
   }
   if (wr == 0) __builtin_amdgcn_s_barrier();          // group 0 makes up the barrier group 1 spent at the start
-  m0_out = m0; n0_out = n0; tn_out = tn;
+  return G2Tile{m0, n0, tn, lane, wave, wr, wc};
+}
+
+// A lane's four consecutive output columns n .. n + 3 of a per-column vector (16-byte aligned; may be null): one float4
+// load where all four exist, 0 for a column at or past N and for a null vector.
+__device__ __forceinline__ float4 g2_col4(const float* colv, int n, int N) {
+  float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (colv != nullptr) {
+    if (n + 3 < N) b = *reinterpret_cast<const float4*>(colv + n);
+    else {
+      if (n < N) b.x = colv[n];
+      if (n + 1 < N) b.y = colv[n + 1];
+      if (n + 2 < N) b.z = colv[n + 2];
+    }
+  }
+  return b;
 }
 
 template <bool FP8, int VM = 10>
 __global__ __launch_bounds__(512, 2) void gemm256_kernel(GemmProblem pr) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   G2Acc acc;
-  int m0, n0, tn_unused;
-  g2_mainloop<FP8, VM>(pr, smem, acc, m0, n0, tn_unused);
-  const int M = pr.M, N = pr.N;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wr = wave >> 2, wc = wave & 3;
+  const G2Tile t = g2_mainloop<FP8, VM>(pr, smem, acc);
+  const int M = pr.M, N = pr.N, m0 = t.m0, n0 = t.n0, lane = t.lane, wave = t.wave, wr = t.wr, wc = t.wc;
   // ---- epilogue ----
   // C/D of (W-operand-as-A): a lane holds n = 4g+e (4 consecutive output columns) at row m = lane&15.
   // Written straight to global that is 32-byte pieces scattered over 16 rows per store; instead the
   // tile goes through the (now free) LDS in two 128-row passes and leaves as whole 512 B / 1 KB rows.
   const int g = lane >> 4;
+  const float* colv = FP8 ? pr.w_scale : pr.bias;            // bf16: additive bias; fp8: the W rows' scales (multiplicative)
   float4 bias4[2][2];
 #pragma unroll
   for (int qj = 0; qj < 2; ++qj)
 #pragma unroll
-    for (int cb = 0; cb < 2; ++cb) {
-      const int n = n0 + wc * 64 + qj * 32 + cb * 16 + 4 * g;
-      float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-      const float* colv = FP8 ? pr.w_scale : pr.bias;        // bf16: additive bias; fp8: the W rows' scales (multiplicative)
-      if (colv != nullptr) {
-        if (n + 3 < N) b = *reinterpret_cast<const float4*>(colv + n);
-        else {
-          if (n < N) b.x = colv[n];
-          if (n + 1 < N) b.y = colv[n + 1];
-          if (n + 2 < N) b.z = colv[n + 2];
-        }
-      }
-      bias4[qj][cb] = b;
-    }
+    for (int cb = 0; cb < 2; ++cb) bias4[qj][cb] = g2_col4(colv, n0 + wc * 64 + qj * 32 + cb * 16 + 4 * g, N);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // bias + the dummy tail of the LDS-DMA stream
   __builtin_amdgcn_s_barrier();                      // nobody stages before every wave's DMA has landed
   const int es = pr.out_is_bf16 ? 2 : 4;
@@ -388,13 +379,15 @@ struct Fuse2 {
 // hidden columns a lane holds in one f32x4 (4g .. 4g+3 of a 16-column block) are the four words of one Philox call.
 template <int NOB, bool DROP>
 __device__ __forceinline__ void g2_fuse2_epilogue(const GemmProblem& pr, const Fuse2& f, const Fuse2Drop& d, G2Acc& acc,
-                                                  char* smem, int head, int slab, int m0, int n0, int lane, int wave) {
+                                                  char* smem, int head, int slab, const G2Tile& t) {
   const int n_out = f.n_out[head];
-  const int wr = wave >> 2, wc = wave & 3;
+  const int m0 = t.m0, n0 = t.n0, lane = t.lane, wr = t.wr, wc = t.wc;
   const int frow = lane & 15, g = lane >> 4;
-  const int mh = wave >> 2, oq = wave & 3;              // second GEMM: row half (128 rows), output quarter (16 * NOB outputs)
+  const int mh = wr, oq = wc;                           // second GEMM: row half (128 rows), output quarter (16 * NOB outputs)
   // layer-1 bias first, then the W2 fragments: vmcnt retires in order, so the staging code below can wait for the bias
-  // (needed at once) with the NOB * 8 younger fragment loads still in flight behind it
+  // (needed at once) with the NOB * 8 younger fragment loads still in flight behind it.  Exactly four unguarded loads (the
+  // tile is whole: N = 2 * hidden is a multiple of 256), not g2_col4's guarded ones: their number and order is what the
+  // counted wait below counts
   float4 bias4[2][2];
 #pragma unroll
   for (int qj = 0; qj < 2; ++qj)
@@ -506,24 +499,21 @@ __global__ __launch_bounds__(512, 2) void gemm256_fuse2_kernel(GemmProblem pr, F
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const Fuse2Drop d = fuse2_drop(drop...);
   G2Acc acc;
-  int m0, n0, tn;
   G2_CLOCK(0);
-  g2_mainloop<false>(pr, smem, acc, m0, n0, tn);
+  const G2Tile t = g2_mainloop<false>(pr, smem, acc);
   G2_CLOCK(1);
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int tiles_per_head = f.hidden >> 8;
-  const int head = tn >= tiles_per_head ? 1 : 0;
-  const int slab = tn - head * tiles_per_head;
-  if (f.n_out[head] == 128) g2_fuse2_epilogue<2, DROP>(pr, f, d, acc, smem, head, slab, m0, n0, lane, wave);
-  else g2_fuse2_epilogue<1, DROP>(pr, f, d, acc, smem, head, slab, m0, n0, lane, wave);
+  const int head = t.tn >= tiles_per_head ? 1 : 0;
+  const int slab = t.tn - head * tiles_per_head;
+  if (f.n_out[head] == 128) g2_fuse2_epilogue<2, DROP>(pr, f, d, acc, smem, head, slab, t);
+  else g2_fuse2_epilogue<1, DROP>(pr, f, d, acc, smem, head, slab, t);
   G2_CLOCK(5);
 }
 
 constexpr size_t G2_LDS = 128 * (G2_BN * 4 + 16);   // >= the two K-tile buffers (128 KB); sized by the f32 epilogue staging
 
 // What runs a problem: the name a kernel trace prints and the launch.  VPR_GEMM256_DEPTH (timing-only build, bf16): the
-// shallower prefetch distances of g2_wait_vm (same results).
+// shallower prefetch distances of g2_wait (same results).
 struct Gemm256Kernel { const char* name; int (*launch)(const GemmProblem& g, dim3 grid, hipStream_t stream); };
 
 template <auto Kernel>

@@ -1,4 +1,5 @@
-// gemm_nt.hip — C[M,N] = act(A[M,K] * W[N,K]^T + bias), bf16 operands, f32 accumulate (MFMA).
+// gemm_nt.hip — C[M,N] = act(A[M,K] * W[N,K]^T + bias), bf16 operands, f32 accumulate (MFMA); and, as a template flag of
+// the same tile body, the e4m3 form C[m][n] = a_scale[m] * w_scale[n] * sum_k A[m][k] W[n][k] (gemm_nt_fp8_kernel).
 //
 // Used for the SALAD token MLPs (score / cluster_features / token_features
 // 1x1-conv + Linear layers of the aggregator called at
@@ -6,8 +7,8 @@
 //
 // Structure (cdna guide §5, "minimum 2-phase"): 128 x BN output tile per 256-thread workgroup,
 // BK = 64, both operand tiles brought in by LDS-DMA (global_load_lds_dwordx4) into a 2-deep LDS
-// ring with the XOR swizzle of vpr_common.h on the source address, fragments read with
-// ds_read_b128, v_mfma_f32_32x32x16_bf16, one barrier per K-step.  Workgroup ids are remapped
+// ring with the XOR swizzle of vpr_common.h on the source address (stage_src_off), fragments read with
+// ds_read_b128, v_mfma_f32_32x32x16_bf16 (e4m3: v_mfma_scale_f32_32x32x64_f8f6f4), one barrier per K-step.  Workgroup ids are remapped
 // so that the workgroups of one XCD (blockIdx % 8) own a contiguous run of tiles and re-use the
 // same A panel out of that XCD's L2.
 #include "vpr_common.h"
@@ -17,14 +18,23 @@ namespace vpr {
 
 struct GemmGroup { GemmProblem p[GEMM_MAX_GROUP]; int count; };
 
-template <int BN, int WM, int WN, int STAGES = 2>
+// FP8 = true: the e4m3 form (OCP e4m3 bytes, per-row f32 scales): C[m][n] = a_scale[m] * w_scale[n] * sum_k A[m][k] W[n][k],
+// the kNN score tile for more than 64 gathered queries against an e4m3 shard (BASELINE config 5 on several GPUs).  Same
+// tile, LDS image, staging groups, ring, fragment rows and C/D map — a 128-byte tile row is now 128 K values — with four
+// differences: the operand element (Elem, ES bytes: a K-step is 128 / ES of them); the raster; the MFMA step (two
+// block-scaled 32x32x64 steps per tile row, mfma_e4m3_32x32x64 of vpr_common.h, against four bf16 32x32x16 steps); the
+// epilogue.  The source pointers stay typed by element: as byte pointers the compiler turns the bf16 K-step offset from
+// one scalar add into eight 64-bit vector pointer increments per step (+2 VGPRs, +1.5 % on the grouped 128 x 128 launch).
+template <int BN, int WM, int WN, int STAGES = 2, bool FP8 = false>
 __device__ __forceinline__ void gemm_nt_tile(const GemmProblem& pr, int orig, char* smem) {
   constexpr int BM = 128;
+  using Elem = std::conditional_t<FP8, uint8_t, uint16_t>;   // operand element: e4m3 byte or bf16
+  constexpr int ES = sizeof(Elem);
   constexpr int TM = BM / WM / 32;  // 32x32 tiles per wave along M
   constexpr int TN = BN / WN / 32;
   constexpr int STAGE_BYTES = (BM + BN) * TILE_ROW_BYTES;
-  const uint16_t* __restrict__ A = pr.A;
-  const uint16_t* __restrict__ W = pr.W;
+  const Elem* __restrict__ A = reinterpret_cast<const Elem*>(pr.A);
+  const Elem* __restrict__ W = reinterpret_cast<const Elem*>(pr.W);
   const float* __restrict__ bias = pr.bias;
   void* __restrict__ Cout = pr.C;
   const int lda = pr.lda, a_group_rows = pr.a_group_rows, ldw = pr.ldw, relu = pr.relu, ldc = pr.ldc;
@@ -36,31 +46,32 @@ __device__ __forceinline__ void gemm_nt_tile(const GemmProblem& pr, int orig, ch
   const int wm = wave / WN, wn = wave % WN;
 
   const int tile = xcd_tile(orig, tiles_m * tiles_n);
-  const int tm = tile / tiles_n, tn = tile % tiles_n;
+  // FP8: tile_m fastest: the (few) query tiles that share a gallery panel run back to back on one XCD
+  const int tm = FP8 ? tile % tiles_m : tile / tiles_n, tn = FP8 ? tile / tiles_m : tile % tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
 
   // Per-lane source row pointers for the staging groups this wave owns (group g = 8 tile rows;
   // wave w stages groups w, w+4, ...).
   constexpr int AG = BM / 8 / 4;  // A groups per wave
   constexpr int BG = BN / 8 / 4;  // W groups per wave
-  const uint16_t* a_src[AG];
-  const uint16_t* w_src[BG];
+  const Elem* a_src[AG];
+  const Elem* w_src[BG];
 #pragma unroll
   for (int i = 0; i < AG; ++i) {
-    int r = m0 + (wave + 4 * i) * 8 + (lane >> 3);
+    const int tr = (wave + 4 * i) * 8 + (lane >> 3);
+    int r = m0 + tr;
     r = r < M ? r : M - 1;
-    const uint16_t* p = a_group_rows > 0
+    const Elem* p = a_group_rows > 0
         ? A + (long long)(r / a_group_rows) * a_group_stride + (long long)(r % a_group_rows) * lda
         : A + (long long)r * lda;
-    const int tr = (wave + 4 * i) * 8 + (lane >> 3);
-    a_src[i] = p + (((lane & 7) ^ ((tr >> 1) & 7)) << 3);
+    a_src[i] = p + stage_src_off(tr, lane) / ES;
   }
 #pragma unroll
   for (int i = 0; i < BG; ++i) {
-    int r = n0 + (wave + 4 * i) * 8 + (lane >> 3);
-    r = r < N ? r : N - 1;
     const int tr = (wave + 4 * i) * 8 + (lane >> 3);
-    w_src[i] = W + (long long)r * ldw + (((lane & 7) ^ ((tr >> 1) & 7)) << 3);
+    int r = n0 + tr;
+    r = r < N ? r : N - 1;
+    w_src[i] = W + (long long)r * ldw + stage_src_off(tr, lane) / ES;
   }
 
   f32x16 acc[TM][TN];
@@ -71,14 +82,15 @@ __device__ __forceinline__ void gemm_nt_tile(const GemmProblem& pr, int orig, ch
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
-  const int nk = K >> 6;
+  constexpr int KSTEP = TILE_ROW_BYTES / ES;   // elements of every row per K-step: one 128-byte tile row
+  const int nk = (K * ES) >> 7;
   auto stage = [&](int buf, int ks) {
     char* ta = smem + buf * STAGE_BYTES;
     char* tw = ta + BM * TILE_ROW_BYTES;
 #pragma unroll
-    for (int i = 0; i < AG; ++i) glds16(a_src[i] + ks * 64, ta + (wave + 4 * i) * 8 * TILE_ROW_BYTES);
+    for (int i = 0; i < AG; ++i) glds16(a_src[i] + ks * KSTEP, ta + (wave + 4 * i) * 8 * TILE_ROW_BYTES);
 #pragma unroll
-    for (int i = 0; i < BG; ++i) glds16(w_src[i] + ks * 64, tw + (wave + 4 * i) * 8 * TILE_ROW_BYTES);
+    for (int i = 0; i < BG; ++i) glds16(w_src[i] + ks * KSTEP, tw + (wave + 4 * i) * 8 * TILE_ROW_BYTES);
   };
 
   // STAGES-deep ring, STAGES-1 K-tiles in flight.  Before the barrier of step ks, tile ks must have landed:
@@ -108,19 +120,41 @@ __device__ __forceinline__ void gemm_nt_tile(const GemmProblem& pr, int orig, ch
     if (ks + STAGES - 1 < nk) stage((ks + STAGES - 1) % STAGES, ks + STAGES - 1);
     const char* ta = smem + (ks % STAGES) * STAGE_BYTES;
     const char* tw = ta + BM * TILE_ROW_BYTES;
+    if constexpr (FP8) {
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      bf16x8 af[TM], bfr[TN];
-      const int chunk = (lane >> 5) + 2 * s;
+      for (int s = 0; s < 2; ++s) {               // two 64-deep MFMA steps per 128-byte row
+        i32x8 af[TM], bfr[TN];
+        const int ch = 4 * s + 2 * (lane >> 5);   // a lane's 32 contiguous K bytes: chunks ch, ch + 1
 #pragma unroll
-      for (int i = 0; i < TM; ++i) af[i] = lds_frag(ta, (wm * TM + i) * 32 + (lane & 31), chunk);
+        for (int i = 0; i < TM; ++i) {
+          const int row = (wm * TM + i) * 32 + (lane & 31);
+          af[i] = e4m3_operand(lds_frag(ta, row, ch), lds_frag(ta, row, ch + 1));
+        }
 #pragma unroll
-      for (int j = 0; j < TN; ++j) bfr[j] = lds_frag(tw, (wn * TN + j) * 32 + (lane & 31), chunk);
+        for (int j = 0; j < TN; ++j) {
+          const int row = (wn * TN + j) * 32 + (lane & 31);
+          bfr[j] = e4m3_operand(lds_frag(tw, row, ch), lds_frag(tw, row, ch + 1));
+        }
 #pragma unroll
-      for (int i = 0; i < TM; ++i)
+        for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+          for (int j = 0; j < TN; ++j) acc[i][j] = mfma_e4m3_32x32x64(af[i], bfr[j], acc[i][j]);
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        bf16x8 af[TM], bfr[TN];
+        const int chunk = (lane >> 5) + 2 * s;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) af[i] = lds_frag(ta, (wm * TM + i) * 32 + (lane & 31), chunk);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) bfr[j] = lds_frag(tw, (wn * TN + j) * 32 + (lane & 31), chunk);
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
+      }
     }
   }
 
@@ -130,17 +164,22 @@ __device__ __forceinline__ void gemm_nt_tile(const GemmProblem& pr, int orig, ch
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       const int n = n0 + (wn * TN + j) * 32 + (lane & 31);
-      const float bv = (bias != nullptr && n < N) ? bias[n] : 0.f;
+      // the column's term: the additive bias (may be null), or (FP8) the W row's scale
+      const float cv = FP8 ? (n < N ? pr.w_scale[n] : 0.f) : ((bias != nullptr && n < N) ? bias[n] : 0.f);
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int m = m0 + (wm * TM + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        float v = acc[i][j][e] + bv;
-        if (relu) v = fmaxf(v, 0.f);
-        if (m < M && n < N) {
-          if (out_is_bf16)
-            reinterpret_cast<uint16_t*>(Cout)[(long long)m * ldc + n] = f32_to_bf16_bits(v);
-          else
-            reinterpret_cast<float*>(Cout)[(long long)m * ldc + n] = v;
+        if constexpr (FP8) {                      // (acc * a_scale) * w_scale: the order of every fp8 score path
+          if (m < M && n < N) reinterpret_cast<float*>(Cout)[(long long)m * ldc + n] = acc[i][j][e] * pr.a_scale[m] * cv;
+        } else {
+          float v = acc[i][j][e] + cv;
+          if (relu) v = fmaxf(v, 0.f);
+          if (m < M && n < N) {
+            if (out_is_bf16)
+              reinterpret_cast<uint16_t*>(Cout)[(long long)m * ldc + n] = f32_to_bf16_bits(v);
+            else
+              reinterpret_cast<float*>(Cout)[(long long)m * ldc + n] = v;
+          }
         }
       }
     }
@@ -169,107 +208,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_group_kernel(GemmGroup grp) {
   }
 }
 
-// ---- fp8 (OCP e4m3, per-row f32 scales) variant: C[m][n] = a_scale[m] * w_scale[n] * sum_k A[m][k] W[n][k] ----
-// The kNN score tile for more than 64 gathered queries against an e4m3 shard (BASELINE config 5 on several GPUs).
-// Same 128 x 128 tile, LDS image and 2-deep LDS-DMA ring as gemm_nt_tile — a 128-byte tile row is now 128 K
-// values — but the products run on the block-scaled matrix instruction v_mfma_scale_f32_32x32x64_f8f6f4 with
-// unit (E8M0 = 127) scales: twice the bf16 rate, where the plain fp8 MFMA runs at the bf16 rate.  A lane's
-// operand is 32 contiguous K bytes (two swizzled 16-byte chunks); A and B use the same lane -> K assignment,
-// which is all a dot product needs.
-struct GemmFp8Problem {
-  const uint8_t* A; int lda; const uint8_t* W; int ldw; const float* a_scale; const float* w_scale;
-  float* C; int ldc; int M, N, K, tiles_m, tiles_n;
-};
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-
-__global__ __launch_bounds__(256, 2) void gemm_nt_fp8_kernel(GemmFp8Problem pr) {
+// The e4m3 form of the 128 x 128 tile (gemm_nt_tile, FP8 = true) under the name kernel traces and gemm_nt_kernel_name know.
+__global__ __launch_bounds__(256, 2) void gemm_nt_fp8_kernel(GemmProblem pr) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int BM = 128, BN = 128, WN = 2, TM = 2, TN = 2;      // 2 x 2 waves, 64 x 64 per wave
-  constexpr int STAGE_BYTES = (BM + BN) * TILE_ROW_BYTES;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave / WN, wn = wave % WN;
-  const int tile = xcd_tile(blockIdx.x, pr.tiles_m * pr.tiles_n);
-  // tile_m fastest: the (few) query tiles that share a gallery panel run back to back on one XCD
-  const int tm = tile % pr.tiles_m, tn = tile / pr.tiles_m;
-  const int m0 = tm * BM, n0 = tn * BN;
-  constexpr int AG = BM / 8 / 4, BG = BN / 8 / 4;
-  const uint8_t* a_src[AG];
-  const uint8_t* w_src[BG];
-#pragma unroll
-  for (int i = 0; i < AG; ++i) {
-    const int tr = (wave + 4 * i) * 8 + (lane >> 3);
-    const int r = min(m0 + tr, pr.M - 1);
-    a_src[i] = pr.A + (long long)r * pr.lda + (((lane & 7) ^ ((tr >> 1) & 7)) << 4);
-  }
-#pragma unroll
-  for (int i = 0; i < BG; ++i) {
-    const int tr = (wave + 4 * i) * 8 + (lane >> 3);
-    const int r = min(n0 + tr, pr.N - 1);
-    w_src[i] = pr.W + (long long)r * pr.ldw + (((lane & 7) ^ ((tr >> 1) & 7)) << 4);
-  }
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  const int nk = pr.K >> 7;                       // 128 K bytes per step
-  auto stage = [&](int buf, int ks) {
-    char* ta = smem + buf * STAGE_BYTES;
-    char* tw = ta + BM * TILE_ROW_BYTES;
-#pragma unroll
-    for (int i = 0; i < AG; ++i) glds16(a_src[i] + ks * 128, ta + (wave + 4 * i) * 8 * TILE_ROW_BYTES);
-#pragma unroll
-    for (int i = 0; i < BG; ++i) glds16(w_src[i] + ks * 128, tw + (wave + 4 * i) * 8 * TILE_ROW_BYTES);
-  };
-  stage(0, 0);
-  for (int ks = 0; ks < nk; ++ks) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (ks + 1 < nk) stage((ks + 1) & 1, ks + 1);
-    const char* ta = smem + (ks & 1) * STAGE_BYTES;
-    const char* tw = ta + BM * TILE_ROW_BYTES;
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {              // two 64-deep MFMA steps per 128-byte row
-      const int ch = 4 * s2 + 2 * (lane >> 5);
-      i32x8 af[TM], bfr[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int row = (wm * TM + i) * 32 + (lane & 31);
-        const i32x4 lo = *reinterpret_cast<const i32x4*>(ta + tile_off(row, ch));
-        const i32x4 hi = *reinterpret_cast<const i32x4*>(ta + tile_off(row, ch + 1));
-        af[i] = i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int row = (wn * TN + j) * 32 + (lane & 31);
-        const i32x4 lo = *reinterpret_cast<const i32x4*>(tw + tile_off(row, ch));
-        const i32x4 hi = *reinterpret_cast<const i32x4*>(tw + tile_off(row, ch + 1));
-        bfr[j] = i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(af[i], bfr[j], acc[i][j], 0, 0, 0, 127, 0, 127);
-    }
-  }
-  // C/D map of 32x32: col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5)
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int n = n0 + (wn * TN + j) * 32 + (lane & 31);
-      const float ws = n < pr.N ? pr.w_scale[n] : 0.f;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int m = m0 + (wm * TM + i) * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        if (m < pr.M && n < pr.N) pr.C[(long long)m * pr.ldc + n] = acc[i][j][e] * pr.a_scale[m] * ws;
-      }
-    }
+  gemm_nt_tile<128, 2, 2, 2, true>(pr, blockIdx.x, smem);
 }
 
 // ---- host side: one rule set, one kernel choice, two launchers ---------------------------------------------------------
@@ -301,17 +243,12 @@ template <auto Kernel, int BN, int STAGES>
 static int gemm_nt_run(const GemmProblem& g, hipStream_t stream) {
   return launch_kernel_lds<Kernel>(dim3(g.tiles_m * g.tiles_n), dim3(256), (size_t)STAGES * (128 + BN) * TILE_ROW_BYTES, stream, g);
 }
-static int gemm_nt_run_fp8(const GemmProblem& g, hipStream_t stream) {
-  const GemmFp8Problem f{reinterpret_cast<const uint8_t*>(g.A), g.lda, reinterpret_cast<const uint8_t*>(g.W), g.ldw, g.a_scale,
-                         g.w_scale, static_cast<float*>(g.C), g.ldc, g.M, g.N, g.K, g.tiles_m, g.tiles_n};
-  return launch_kernel_lds<gemm_nt_fp8_kernel>(dim3(g.tiles_m * g.tiles_n), dim3(256), (size_t)2 * (128 + 128) * TILE_ROW_BYTES, stream, f);
-}
 
 // bf16: 128-column tiles, or one 64-column tile for N <= 64; and the A/B switch VPR_GEMM_NT_STAGES, 3 = three-deep ring
 // (96 KB: one workgroup per CU).  Measured on the kNN score tile, 2 vs 3 stages: 128 x 50k 217 / 291 us, 512 x 12.5k
 // 141 / 205 us — two workgroups per CU beat the deeper ring.
 static GemmNtKernel gemm_nt_choose(bool e4m3, int N) {
-  if (e4m3) return {"vpr::gemm_nt_fp8_kernel", 128, gemm_nt_run_fp8};
+  if (e4m3) return {"vpr::gemm_nt_fp8_kernel", 128, gemm_nt_run<gemm_nt_fp8_kernel, 128, 2>};
   if (N > 64 && tune_or(TUNE_GEMM_NT_STAGES, 2) == 3)
     return {"vpr::gemm_nt_kernel<128, 2, 2, 3>", 128, gemm_nt_run<gemm_nt_kernel<128, 2, 2, 3>, 128, 3>};
   if (N > 64) return {"vpr::gemm_nt_kernel<128, 2, 2, 2>", 128, gemm_nt_run<gemm_nt_kernel<128, 2, 2>, 128, 2>};

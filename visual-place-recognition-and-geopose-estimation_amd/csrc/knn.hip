@@ -40,10 +40,11 @@ __host__ __device__ inline int knn_kp(int k) {
 // 2-deep ring, one barrier per K-step.  Wave w multiplies queries 16w..16w+15 (MFMA A operand)
 // with every 16-row gallery block (B operand): C[q][n], lane = gallery row n -> coalesced 64-B
 // score stores.
-// FP8 (OCP e4m3, per-row f32 scale): same LDS image and the same 16-B fragment reads; each 16-B
-// chunk now holds 16 elements and feeds two v_mfma_f32_16x16x32_fp8_fp8 (low / high 8 bytes) —
-// A and B use the same (permuted) k order, so the permutation cancels in the dot product — and
-// the epilogue multiplies by the two row scales.
+// FP8 (OCP e4m3, per-row f32 scale): same LDS image and the same 16-B fragment reads; a lane's two
+// 16-B chunks are the 32-byte operand of ONE block-scaled MFMA over the whole 128-byte K-step
+// (mfma_e4m3_16x16x128 of vpr_common.h: twice the rate of the four v_mfma_f32_16x16x32_fp8_fp8 it
+// replaced) — A and B use the same lane -> K assignment, so the permutation cancels in the dot
+// product — and the epilogue multiplies by the two row scales.
 // ---------------------------------------------------------------------------------------------
 template <bool FP8, int KNN_TR, int WGPC, int ABL>
 __global__ __launch_bounds__(256, WGPC) void knn_scores_kernel(
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(256, WGPC) void knn_scores_kernel(
     for (int i = 0; i < GPW; ++i) {
       const int g = wave + 4 * i;
       const int tr = (g < GG ? g : g - GG) * 8 + (lane >> 3);   // row inside its tile
-      const int sw = ((lane & 7) ^ ((tr >> 1) & 7)) << 4;
+      const int sw = stage_src_off(tr, lane);
       if (g < GG) {
         const int r = row0 + min(tr, th - 1);
         src[i] = G + (long long)r * row_bytes + sw;
@@ -136,16 +137,7 @@ __global__ __launch_bounds__(256, WGPC) void knn_scores_kernel(
           const bf16x8 b0 = lds_frag(tg, 16 * nb + (lane & 15), (lane >> 4));
           const bf16x8 b1 = lds_frag(tg, 16 * nb + (lane & 15), 4 + (lane >> 4));
           if constexpr (FP8) {
-            // one block-scaled MFMA (unit E8M0 scales) over the whole 128-byte K-step: a lane's 32 operand bytes
-            // are its two 16-byte chunks (same lane -> K assignment for both operands); twice the rate of the
-            // four v_mfma_f32_16x16x32_fp8_fp8 this replaces
-            typedef __attribute__((ext_vector_type(8))) int i32x8;
-            typedef __attribute__((ext_vector_type(4))) int i32x4;
-            const i32x4 A0 = __builtin_bit_cast(i32x4, a0), A1 = __builtin_bit_cast(i32x4, a1);
-            const i32x4 B0 = __builtin_bit_cast(i32x4, b0), B1 = __builtin_bit_cast(i32x4, b1);
-            const i32x8 A = {A0[0], A0[1], A0[2], A0[3], A1[0], A1[1], A1[2], A1[3]};
-            const i32x8 Bv = {B0[0], B0[1], B0[2], B0[3], B1[0], B1[1], B1[2], B1[3]};
-            acc[nb] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(A, Bv, acc[nb], 0, 0, 0, 127, 0, 127);
+            acc[nb] = mfma_e4m3_16x16x128(e4m3_operand(a0, a1), e4m3_operand(b0, b1), acc[nb]);
           } else {
             acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b0, acc[nb], 0, 0, 0);
             acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b1, acc[nb], 0, 0, 0);
@@ -509,7 +501,6 @@ __global__ __launch_bounds__(256) void knn_select_stream_kernel(
 template <bool FP8>
 __device__ __forceinline__ double dot16(const s16x8& qa, const s16x8& ga, double acc) {
   if constexpr (FP8) {
-    typedef __attribute__((ext_vector_type(4))) int i32x4;
     const i32x4 qi = __builtin_bit_cast(i32x4, qa), gi = __builtin_bit_cast(i32x4, ga);
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
@@ -531,7 +522,6 @@ template <bool FP8>
 __device__ __forceinline__ float sumsq16(const s16x8& a) {
   float t = 0.f;
   if constexpr (FP8) {
-    typedef __attribute__((ext_vector_type(4))) int i32x4;
     const i32x4 w = __builtin_bit_cast(i32x4, a);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {

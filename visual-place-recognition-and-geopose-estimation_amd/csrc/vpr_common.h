@@ -11,6 +11,8 @@ typedef __attribute__((ext_vector_type(8))) short s16x8;     // 8 bf16 = one 16-
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;   // MFMA A/B fragment type
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(4))) int i32x4;       // one 16-B chunk as loaded: 8 bf16, 16 e4m3 or 4 f32
+typedef __attribute__((ext_vector_type(8))) int i32x8;       // two chunks: the 32-byte e4m3 operand of a block-scaled MFMA
 
 constexpr int WAVE = 64;
 
@@ -126,6 +128,13 @@ constexpr int TILE_ROW_BYTES = 128;
 __device__ __forceinline__ int tile_off(int row, int chunk) {
   return row * TILE_ROW_BYTES + ((chunk ^ ((row >> 1) & 7)) << 4);
 }
+// The inverse, on the filling side.  One LDS-DMA instruction (glds16 below) fills 8 tile rows: lane i writes physical slot
+// (tr, i % 8) of tile row tr = first row of the group + i / 8, and therefore fetches logical chunk (i % 8) ^ swz(tr).  This is
+// the byte offset of that chunk in the lane's source row (bf16 or e4m3: a tile row is 128 source bytes either way); the
+// caller resolves tr -> source row pointer (clamping / grouping).  tile_off(tr, c) then finds chunk c where it landed.
+__device__ __forceinline__ int stage_src_off(int tr, int lane) {
+  return ((lane & 7) ^ ((tr >> 1) & 7)) << 4;
+}
 
 // One LDS-DMA wave-instruction: 64 lanes x 16 B land at lds_wave_base + lane*16 (the LDS side
 // is linear; the swizzle is applied to the per-lane SOURCE address, cdna guide rule 21).
@@ -138,18 +147,25 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
       (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, AUX);
 }
 
-// Fill 8 tile rows [row0, row0+8) of an LDS tile from a row-major bf16 matrix: lane i writes
-// physical slot (row0 + i/8, i%8) and therefore fetches logical chunk (i%8) ^ swz(row).
-// `src_row_ptr` is this lane's source row start (already offset to the k-step), i.e. the
-// caller resolves row -> pointer (clamping / grouping) for row0 + (lane>>3).
-__device__ __forceinline__ void stage8(const uint16_t* src_row_ptr, char* tile, int row0, int lane) {
-  const int r = row0 + (lane >> 3);
-  const int c = (lane & 7) ^ ((r >> 1) & 7);
-  glds16(src_row_ptr + c * 8, tile + row0 * TILE_ROW_BYTES);
-}
-
 __device__ __forceinline__ bf16x8 lds_frag(const char* tile, int row, int chunk) {
   return *reinterpret_cast<const bf16x8*>(tile + tile_off(row, chunk));
+}
+
+// ---- the block-scaled e4m3 MFMA step (gemm_nt.hip, gemm256.hip, knn.hip) ------------------------------------------
+// v_mfma_scale_f32_{16x16x128,32x32x64}_f8f6f4 on OCP e4m3 bytes with unit block scales: twice the bf16 rate, where the
+// plain fp8 MFMA runs at the bf16 rate.  A lane's operand is 32 K bytes = two 16-byte chunks of its tile row, read with
+// the same ds_read_b128 as a bf16 fragment; A and B use the same lane -> K assignment, which is all a dot product needs.
+template <typename Chunk>
+__device__ __forceinline__ i32x8 e4m3_operand(Chunk lo, Chunk hi) {
+  const i32x4 l = __builtin_bit_cast(i32x4, lo), h = __builtin_bit_cast(i32x4, hi);
+  return i32x8{l[0], l[1], l[2], l[3], h[0], h[1], h[2], h[3]};
+}
+constexpr int E8M0_ONE = 127;   // the E8M0 block scale 2^0, for both operands: the row scales are applied in the epilogues
+__device__ __forceinline__ f32x4 mfma_e4m3_16x16x128(i32x8 a, i32x8 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, E8M0_ONE, 0, E8M0_ONE);
+}
+__device__ __forceinline__ f32x16 mfma_e4m3_32x32x64(i32x8 a, i32x8 b, f32x16 c) {
+  return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, E8M0_ONE, 0, E8M0_ONE);
 }
 
 // XCD-aware remap of a workgroup id to a tile (cdna guide §5: "XCD swizzle must be bijective").  Workgroup `orig` of `nwg`
@@ -242,9 +258,7 @@ __device__ __forceinline__ void mfma_f32_store_rows(const SlabRowMajor& slab, in
   }
 }
 
-// ---- 16-byte row chunks (query_expand.hip, rerank.hip, project.hip) ----------------------------------------------
-typedef __attribute__((ext_vector_type(4))) int i32x4;       // one chunk as loaded: 8 bf16, 16 e4m3 or 4 f32
-
+// ---- 16-byte row chunks (i32x4; query_expand.hip, rerank.hip, project.hip) ---------------------------------------
 // The two bf16 of a 32-bit word: element 2w in the low half, 2w + 1 in the high half.
 __device__ __forceinline__ float bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf16_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
