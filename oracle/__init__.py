@@ -21,6 +21,10 @@ Pinning status:
   * salad_f32_stages.py     — the f32-accurate path's stages: the three bf16 planes of an operand, the six-product plane
     GEMM of both layers, its true-f64 statement, the outputs a wrong kernel would leave, and three input families on which
     f32 accumulation is exact in any order; asserted on the oracle alone in tests/test_oracle_selfchecks.py as well.
+  * salad_stage_a.py        — stage A (Sinkhorn, V = F^T P^T on hi/lo planes, three normalisations) per element: the f64
+    statement with its intermediates, the kernels' arithmetic in plain torch f32, one-hot feature probes that read single
+    entries of the transport plan, a per-element bound derived from a stated rounding model, and the outputs a wrong kernel
+    would leave; asserted on the oracle alone in tests/test_salad_stage_a_cpu.py.
   * knn.py                  — PARITY UNPINNED by the reference: it has no retrieval code at all
     (SURVEY.md fact 3).  Brute-force definition of the stage's contract.
 """
