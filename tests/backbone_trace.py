@@ -290,8 +290,8 @@ def stage_records(captured, want):
 
 
 # ------------------------------------------------------------------------------------------------------------ the model
-def make_model(arch, img_size, L, seed=0):
-    """DinoV2 cut to its first L blocks (CPU, bf16, eval, LayerScale folded) with every parameter away from its init value
+def make_model(arch, img_size, L, seed=0, fold=True):
+    """DinoV2 cut to its first L blocks (CPU, bf16, eval, LayerScale folded unless fold=False) with every parameter away from its init value
     and no two blocks, norms or bias rows alike: norm weights 1 + 0.3 N, norm / Linear / conv biases 0.5 N, LayerScale
     N(0, 0.3) before the fold, cls token 0.5 N, pos_embed a +-1 code plus noise, fc1 weights scaled to pre-activation
     std >= 1 (0.9 / sqrt(C) per weight on LayerNorm outputs of mean square ~ 1.3, plus the 0.5 N bias: a larger scale
@@ -318,7 +318,8 @@ def make_model(arch, img_size, L, seed=0):
         T = 1 + m.num_patches
         m.pos_embed.copy_(((torch.randint(0, 2, (T, C), generator=g) * 2 - 1).float() + 0.02 * rn(T, C)).unsqueeze(0))
     m = m.to(torch.bfloat16).eval()
-    m.fold_layerscale()
+    if fold:
+        m.fold_layerscale()
     return m
 
 

@@ -196,6 +196,151 @@ def test_cumulative_bias_follows_an_in_place_change_of_fc2_bias():
     assert torch.allclose(m._cumulative_bias(cpu), before + torch.tensor([1.0] + [2.0] * (len(before) - 1))[:, None], atol=1e-5)
 
 
+# ------------------------------------------------------------------------------- the hand-over between streams, on fakes
+class FakeStreams:
+    """Stands in for ops._PROBES: a settable current stream and a log of every device action a hand-over enqueues."""
+    def __init__(self):
+        self.cur, self.log, self.events = "A", [], 0
+
+    def probes(self):
+        from vpr_amd._cache import StreamProbes
+        return StreamProbes(lambda: self.cur, self._record, lambda e: self.log.append(("wait", e, self.cur)),
+                            lambda v: self.log.append(("keep", id(v), self.cur)))
+
+    def _record(self):
+        self.events += 1
+        self.log.append(("record", self.events, self.cur))
+        return self.events
+
+
+def test_hit_from_the_builders_stream_enqueues_nothing():
+    fs = FakeStreams()
+    c = Cache(Probe(), capacity=2, probes=fs.probes())
+    v = c.get("k", _buf)
+    assert fs.log == [("record", 1, "A")]                     # one event, recorded on the building stream after the build
+    for _ in range(3):
+        assert c.get("k", _buf) is v
+    assert fs.log == [("record", 1, "A")]
+
+
+def test_first_hit_from_another_stream_waits_once_and_later_hits_enqueue_nothing():
+    fs = FakeStreams()
+    c = Cache(Probe(), probes=fs.probes())
+    v = c.get("k", _buf)
+    fs.cur = "B"
+    assert c.get("k", _buf) is v
+    assert fs.log[1:] == [("wait", 1, "B"), ("keep", id(v), "B")]
+    for _ in range(3):
+        c.get("k", _buf)
+    fs.cur = "A"
+    c.get("k", _buf)
+    assert len(fs.log) == 3                                   # neither B again nor the builder
+    fs.cur = "C"                                              # every further stream gets its own single wait, for the same event
+    c.get("k", _buf)
+    c.get("k", _buf)
+    assert fs.log[3:] == [("wait", 1, "C"), ("keep", id(v), "C")]
+
+
+def test_nothing_is_waited_for_under_capture_and_a_value_built_under_capture_has_no_event():
+    fs, probe = FakeStreams(), Probe()
+    c = Cache(probe, probes=fs.probes())
+    v = c.get("warm", _buf)
+    fs.cur, probe.on = "G", True                              # a capturing stream hits what another stream built
+    assert c.get("warm", _buf) is v and len(fs.log) == 1      # (the device was synchronised before the capture began)
+    g = c.get("in_graph", _buf)                               # built during capture: belongs to the graph, nothing recorded
+    assert len(fs.log) == 1
+    probe.on = False
+    fs.cur = "B"
+    assert c.get("in_graph", _buf) is g and len(fs.log) == 1  # nothing to wait for
+    fs.cur = "G"                                              # the capture did not count as a hand-over to G: outside it, G waits
+    c.get("warm", _buf)
+    assert fs.log[1:] == [("wait", 1, "G"), ("keep", id(v), "G")]
+
+
+def test_drop_and_eviction_forget_the_bookkeeping_with_the_entry():
+    fs = FakeStreams()
+    c = Cache(Probe(), capacity=1, probes=fs.probes())
+    c.get((0, 7, "a"), _buf)
+    fs.cur = "B"
+    c.get((0, 7, "a"), _buf)
+    assert [e[0] for e in fs.log] == ["record", "wait", "keep"]
+    c.drop(lambda k: k[1] == 7)
+    v = c.get((0, 7, "a"), _buf)                              # rebuilt, now by B: a new event, B is the builder
+    assert fs.log[3:] == [("record", 2, "B")]
+    c.get((0, 7, "a"), _buf)
+    fs.cur = "A"                                              # and the old builder is a borrower like any other
+    c.get((0, 7, "a"), _buf)
+    assert fs.log[4:] == [("wait", 2, "A"), ("keep", id(v), "A")]
+    c.get("other", _buf)                                      # capacity 1: evicts the entry
+    assert (0, 7, "a") not in c
+    fs.cur = "B"
+    w = c.get((0, 7, "a"), _buf)
+    assert fs.log[6:] == [("record", 3, "A"), ("record", 4, "B")] and w is not v
+    fs.cur = "A"
+    c.get((0, 7, "a"), _buf)
+    assert fs.log[8:] == [("wait", 4, "A"), ("keep", id(w), "A")]
+
+
+def test_a_grown_entry_is_a_new_build_with_a_new_event():
+    fs = FakeStreams()
+    c = Cache(Probe(), probes=fs.probes())
+    c.get("ws", _buf, (16,), need=16)
+    fs.cur = "B"
+    c.get("ws", _buf, (16,), need=8)
+    big = c.get("ws", _buf, (64,), need=64)                   # B rebuilds: B's event; A has to wait for it
+    fs.cur = "A"
+    c.get("ws", _buf, (64,), need=64)
+    assert fs.log[3:] == [("record", 2, "B"), ("wait", 2, "A"), ("keep", id(big), "A")]
+
+
+def test_pinned_entries_behave_as_before_with_stream_probes():
+    fs, probe = FakeStreams(), Probe()
+    c = Cache(probe, capacity=1, probes=fs.probes())
+    first = c.get("warm", _buf)
+    fs.cur, probe.on = "G", True
+    assert c.get("warm", _buf) is first                       # pinned by the captured hit
+    probe.on = False
+    c.get("x", _buf)
+    c.get("y", _buf)
+    assert c.get("warm", _buf) is first and "x" not in c and len(c) == 2
+    fs.cur = "B"
+    assert c.get("warm", _buf) is first                       # still lent in order after it was pinned
+    assert ("wait", 1, "B") in fs.log
+
+
+def test_no_stream_means_no_event_and_no_wait():
+    fs = FakeStreams()
+    fs.cur = None                                             # the process has not touched a GPU
+    c = Cache(Probe(), probes=fs.probes())
+    c.get("k", _buf)
+    fs.cur = "B"
+    c.get("k", _buf)
+    assert fs.log == []
+
+
+def test_handover_survives_a_deepcopy_as_one_that_remembers_nothing():
+    import copy
+    from vpr_amd._cache import Handover
+    fs = FakeStreams()
+    h = Handover(fs.probes(), Probe())
+    twin = copy.deepcopy({"order": h})["order"]
+    assert h.event == 1 and twin.event is None and twin.stream is None
+    fs.cur = "B"
+    twin.lend(())
+    assert len(fs.log) == 1
+    h.lend(())
+    assert fs.log[1:] == [("wait", 1, "B"), ("keep", id(()), "B")]
+
+
+def test_package_caches_and_handovers_touch_no_gpu_in_a_process_without_one():
+    if torch.cuda.is_initialized():
+        return                                                # (a GPU session that ran GPU tests first: nothing to show here)
+    c = ops.cache(1)
+    v = c.get("a", _buf)
+    assert c._entries["a"][4].stream is None and c.get("a", _buf) is v
+    assert ops.handover().event is None and not torch.cuda.is_initialized()
+
+
 # restype and argtypes of every entry point, taken from the commit before the table was built from shared prefixes
 # (P(x) = POINTER(x); c_ulong is what c_size_t names here)
 PROTOTYPES_SNAPSHOT = {

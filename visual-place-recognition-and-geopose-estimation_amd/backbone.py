@@ -227,6 +227,9 @@ class DinoV2(nn.Module):
         SplitTokens(patch [B,n,C], cls [B,C]) pair (what the HIP path computes in; no copy)."""
         if self.auto_fold and x.is_cuda and x.dtype == torch.bfloat16 and not all(b.folded for b in self.blocks):
             self.fold_layerscale()      # inference-only module: a load un-folds (Block._load_from_state_dict), the next GPU forward re-folds
+        order = self.__dict__.get("_fold_order")
+        if order is not None and x.is_cuda:
+            order.lend(())              # a stream other than the folding one waits for the fold, once (the weights are never freed)
         if self._hip_split_ok(x):
             st = self._forward_hip_split(x)
             return st if split else st.joined()
@@ -469,8 +472,13 @@ class DinoV2(nn.Module):
         return torch.stack(rows).contiguous()
 
     def fold_layerscale(self) -> "DinoV2":
+        """Fold every block.  The fold rewrites proj / fc2 in place on the current stream while `folded` flips on the host at
+        once: the hand-over to any other stream that runs a forward next is `_fold_order` (ops.handover, lent in forward)."""
+        rewrote = not all(b.folded for b in self.blocks)
         for blk in self.blocks:
             blk.fold_layerscale()
+        if rewrote and self.pos_embed.is_cuda:
+            self.__dict__["_fold_order"] = ops.handover()
         return self
 
     def flops_per_image(self) -> float:

@@ -64,8 +64,15 @@ class SaladAggregator(nn.Module):
             w1_sc=bf(torch.cat([m2(s[0].weight), m2(c[0].weight)], 0)), b1_sc=f32(torch.cat([s[0].bias, c[0].bias], 0)),
             w2_s=bf(m2(s[3].weight)), b2_s=f32(s[3].bias), w2_c=bf(m2(c[3].weight)), b2_c=f32(c[3].bias),
             w1_t=bf(m2(t[0].weight)), b1_t=f32(t[0].bias), w2_t=bf(m2(t[2].weight)), b2_t=f32(t[2].bias),
-            dustbin=float(self.dust_bin.detach().cpu()))
+            dustbin=self._dustbin_after_pack())
         return self._packed
+
+    def _dustbin_after_pack(self) -> float:
+        """dust_bin as a host number, read LAST in pack() / pack_f32(): the device-to-host copy blocks the host until the
+        current stream has run everything queued before it, the casts and concatenations of the pack among them.  That is
+        the hand-over of the packed tensors to every stream: when pack() returns they are complete, so a caller on any
+        stream may use them (tests/test_stream_handover_gpu.py holds this).  Not for use under graph capture."""
+        return float(self.dust_bin.detach().cpu())
 
     def pack_f32(self) -> ops.SaladWeightsF32:
         """f32 kernel-format weights for the f32-accurate aggregation (vpr_salad_aggregate_f32): the parameters as they
@@ -77,7 +84,7 @@ class SaladAggregator(nn.Module):
             w1_sc=torch.cat([m2(s[0].weight), m2(c[0].weight)], 0).contiguous(), b1_sc=f32(torch.cat([s[0].bias, c[0].bias], 0)),
             w2_s=m2(s[3].weight), b2_s=f32(s[3].bias), w2_c=m2(c[3].weight), b2_c=f32(c[3].bias),
             w1_t=m2(t[0].weight), b1_t=f32(t[0].bias), w2_t=m2(t[2].weight), b2_t=f32(t[2].bias),
-            dustbin=float(self.dust_bin.detach().cpu()))
+            dustbin=self._dustbin_after_pack())
         return self._packed_f32
 
     def token_stage(self, cls_rows: torch.Tensor, owner_raw_stream: int, n: int) -> None:
@@ -370,11 +377,16 @@ class FusedGeoPoseHead(nn.Module):
         W2[:2, :hp] = W2p
         W2[2:, hp:] = W2a
         self._packed = (W1, b1, W2, torch.cat([b2p, b2a], 0).contiguous())
+        self._packed_order = (self._packed, ops.handover())     # built by queued work of the current stream: lent in forward
         return self._packed
 
     @torch.no_grad()
     def forward(self, features: torch.Tensor) -> torch.Tensor:
-        W1, b1, W2, b2 = self._packed or self.pack()
+        packed = self._packed or self.pack()
+        of, order = getattr(self, "_packed_order", None) or (None, None)
+        if of is packed:                # (a caller may also set _packed itself: such matrices are ordered by whoever made them)
+            order.lend(packed)          # a stream other than the packing one waits for the pack, once
+        W1, b1, W2, b2 = packed
         return _vpr.pose_head(features, W1, b1, W2, b2, 2 if self.normalize else -1)
 
 

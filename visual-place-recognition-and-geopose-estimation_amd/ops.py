@@ -13,7 +13,7 @@ from typing import NamedTuple, Optional, Tuple
 import torch
 
 from . import _lib
-from ._cache import Cache, tensor_key
+from ._cache import Cache, Handover, StreamProbes, tensor_key
 
 
 def _raw_stream(device_index: int = -1) -> int:
@@ -49,9 +49,57 @@ def capturing() -> bool:
     return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
 
 
+def _current_stream_name() -> Optional[Tuple[int, int]]:
+    """(device index, raw handle) of the current stream; None while this process has not touched a GPU."""
+    if not torch.cuda.is_initialized():
+        return None
+    idx = torch.cuda.current_device()
+    return idx, torch._C._cuda_getCurrentRawStream(idx)
+
+
+def _current_stream_object() -> "torch.Stream":
+    """torch.cuda.current_stream() through the C entry point underneath it (like _raw_stream: none of the Python device
+    bookkeeping, and nothing a test that substitutes torch.cuda.Stream / torch.cuda.device can get in the way of)."""
+    sid, idx, kind = torch._C._cuda_getCurrentStream(torch.cuda.current_device())
+    return torch._C._CudaStreamBase(stream_id=sid, device_index=idx, device_type=kind)
+
+
+def _record_event() -> "torch.cuda.Event":
+    e = torch.cuda.Event()
+    e.record(_current_stream_object())
+    return e
+
+
+def _wait_event(event: "torch.cuda.Event") -> None:
+    event.wait(_current_stream_object())
+
+
+def _keep_for_current_stream(value) -> None:
+    """Tensor.record_stream on every GPU tensor in `value` (a tensor, or tuples / lists of them): when the last reference
+    goes, the allocator reuses the memory only after what the current stream has queued by then."""
+    if isinstance(value, torch.Tensor):
+        if value.is_cuda:
+            value.record_stream(_current_stream_object())
+    elif isinstance(value, (tuple, list)):
+        for v in value:
+            _keep_for_current_stream(v)
+
+
+# The hand-over of a cached value from the stream that built it to any other (_cache.Handover): one event wait and one
+# record_stream at the first hit from that stream, host-side comparisons ever after.
+_PROBES = StreamProbes(_current_stream_name, _record_event, _wait_event, _keep_for_current_stream)
+
+
+def handover() -> Handover:
+    """A _cache.Handover for a device value built just now on the current stream and kept outside any cache (folded
+    LayerScale weights, FusedGeoPoseHead's packed matrices): call .lend(value) wherever the value is used."""
+    return Handover(_PROBES, lambda: capturing())
+
+
 def cache(capacity: Optional[int] = None) -> Cache:
-    """A _cache.Cache that asks this module's capturing() (looked up per call: a test can substitute it)."""
-    return Cache(lambda: capturing(), capacity)
+    """A _cache.Cache that asks this module's capturing() (looked up per call: a test can substitute it) and orders
+    every value it hands to a stream other than the one that built it (_PROBES)."""
+    return Cache(lambda: capturing(), capacity, _PROBES)
 
 
 def _call(name: str, *args) -> None:
