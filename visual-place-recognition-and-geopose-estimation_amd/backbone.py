@@ -309,18 +309,23 @@ class DinoV2(nn.Module):
 
     def _blocks_side_chain(self, stages: list, x: torch.Tensor, h: torch.Tensor, B: int, n: int) -> "SplitTokens":
         """The blocks with the cls rows on their own stream.  Between two attentions the B cls rows need six small kernels
-        (_BlockStages.rows: ~40 us) that depend on nothing but the cls rows of the attention output; in-stream they cost
-        0.8 ms per step, almost all of it launch latency.  Here the side stream is forked right after each attention and
-        joined right before the next one, ~375 us of patch-row GEMMs later, so the join never waits (an earlier attempt forked
-        and joined around every single cls-row launch and lost 0.6 ms to cross-queue waits: 12.8 vs 12.2 ms per step).  The
-        main stream touches only patch rows, the side stream only cls rows: no shared writes.  Lifetimes: what the main
+        (_BlockStages.rows: 28 us of kernel time alone) that depend on nothing but the cls rows of the attention output;
+        in-stream they cost the step ~0.1 ms more (11.17 vs 11.08 ms), launch gaps mostly.  Here the side stream is forked right
+        after each attention and joined right before the next one, ~400 us of patch-row GEMMs later (an earlier attempt forked
+        and joined around every single cls-row launch and lost 0.6 ms to cross-queue waits: 12.8 vs 12.2 ms per step).
+        The chain does NOT run under the GEMMs (profiles/cls_chain_bench.txt): a library GEMM workgroup takes all 512 registers
+        per lane of every SIMD of its CU and one workgroup sits on each CU, so a cls-row kernel is dispatched while the GEMM
+        runs, stays open until the GEMM's workgroups retire (8-10x its own time) and then runs at the head of the next
+        main-stream kernel, which it delays by about its own duration.  What the chain costs the step is therefore the cls
+        kernels' own time, and the join still never waits: the chain ends ~80 us before the block's last GEMM does.
+        The main stream touches only patch rows, the side stream only cls rows: no shared writes.  Lifetimes: what the main
         stream allocated and the side stream reads (`att`) or writes (`qkv_next`) stays referenced until after the join; the
         side stream's temporaries (rows(CLS), inside the stream context) come from that stream's allocator pool, the patch
         rows' (rows(PATCH), outside it, `hh` among them) from the main stream's.  Under graph capture fork / join are "events"."""
         Mp, C, dev = B * n, self.embed_dim, x.device
         main = torch.cuda.current_stream(dev)
-        # high priority: the cls-row workgroups take the first CU slots a retiring GEMM workgroup frees (the
-        # library GEMMs fill every CU, so at equal priority the small kernels sit in the queue: 40-95 us each)
+        # high priority: the cls-row workgroups take the first CU slots a retiring GEMM workgroup frees (the library
+        # GEMMs fill every CU's register file: nothing starts beside them, whatever its size)
         side = _streams.side_stream(dev, main.cuda_stream, "cls", int(os.environ.get("VPR_SIDE_PRIORITY", "-1")))
         mode = self.side_sync if not torch.cuda.is_current_stream_capturing() else "events"     # capture: plain event nodes
         if mode not in ("events", "light", "signals"):
@@ -341,7 +346,7 @@ class DinoV2(nn.Module):
                     self.cls_tail_hook(hc, main.cuda_stream, n)
                 joined = sync.mark(side)
             hp = st.rows(PATCH, att[:Mp], xp, nst, qkv_next[:Mp] if nst is not None else None)
-            sync.join(main, joined)        # the side chain finished ~0.3 ms ago: satisfied on arrival
+            sync.join(main, joined)        # the side chain ended during the block's last GEMM (~80 us ago): satisfied on arrival
             qkv = qkv_next                 # (att stayed referenced up to here)
         return SplitTokens(hp.view(B, n, C), hc, hooked)
 

@@ -104,27 +104,47 @@ __device__ __forceinline__ void ln_store_row(const float (&v)[NCH][8], float mea
 // The scheme (16 columns x MBW row blocks per workgroup, NW waves split K) is described at the top of skinny.hip.  C/D of
 // v_mfma_f32_16x16x32_bf16 with W as the A operand: col = row m (lane & 15), rows 4 (lane >> 4) + e = 4 consecutive columns.
 
-// The lane's operand streams: W row n0 + (lane & 15) and input rows m0 + 16 mb + (lane & 15), both clamped into the matrix
-// (a clamped duplicate is loaded and its result dropped), offset by the lane's 8 elements of a 32-deep K-step.
-template <int MBW>
+// The lane's operand streams: W row n0 + row and input rows m0 + 16 mb + row, both clamped into the matrix (a clamped duplicate
+// is loaded and its result dropped), offset by the lane's 8 elements (chunk) of a 32-deep K-step.  Which (row, chunk) a lane
+// FETCHES is the form's choice:
+//   QUAD = false   the pair it feeds to the MFMA, (lane & 15, lane >> 4): neighbouring lanes read 16 different rows, which the
+//                  load path serves at a quarter of its rate (measured: the four skinny launches of a block fit 3.2 us +
+//                  0.0276 us per KB a workgroup loads, 15 B / clk per CU; by quads 0.0129: profiles/cls_chain_bench.txt);
+//   QUAD = true    (lane >> 2, lane & 3): four neighbouring lanes read 64 contiguous bytes of one row, and the fragment then
+//                  crosses to the lane that feeds it (skinny_to_mfma_lane: ds_bpermute, no LDS storage).
+template <int MBW, bool QUAD = false>
 struct SkinnyOperands {
   const uint16_t* wp;
   const uint16_t* ip[MBW];
   __device__ __forceinline__ SkinnyOperands(const uint16_t* W, int ldw, int n0, int N, const uint16_t* in, long long ldi, int m0,
                                             int M, int lane) {
-    const int r = lane & 15, g = lane >> 4;
+    const int r = QUAD ? lane >> 2 : lane & 15, g = QUAD ? lane & 3 : lane >> 4;
     wp = W + (long long)min(n0 + r, N - 1) * ldw + 8 * g;
 #pragma unroll
     for (int mb = 0; mb < MBW; ++mb) ip[mb] = in + (long long)min(m0 + mb * 16 + r, M - 1) * ldi + 8 * g;
   }
 };
 
+// The fragment (row lane & 15, chunk lane >> 4) from the lane that fetched it under QUAD: lane 4 (lane & 15) + (lane >> 4).
+__device__ __forceinline__ bf16x8 skinny_to_mfma_lane(bf16x8 f) {
+  typedef __attribute__((ext_vector_type(4))) int i32x4;
+  const int src = 4 * (4 * (int)(threadIdx.x & 15) + (int)((threadIdx.x & 63) >> 4));      // byte index of the source lane
+  i32x4 v = __builtin_bit_cast(i32x4, f);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = __builtin_amdgcn_ds_bpermute(src, v[e]);
+  return __builtin_bit_cast(bf16x8, v);
+}
+
 // K-steps [kbeg, kend) into acc: UNR steps' (1 + MBW) * UNR fragment loads are requested before their MFMAs (a slice is one or
 // two memory round trips, not a streaming loop), then the remainder step by step.  The sums are kept in locals and handed over
 // once: through the reference the compiler, which optimises this function before it inlines it, has to assume that they alias
 // the operand streams, and the loops it then leaves cost skinny_linear_kernel<*, 4, 4> 16 more AGPRs and an occupancy step.
-template <int UNR, int MBW>
-__device__ __forceinline__ void skinny_k_slice(const SkinnyOperands<MBW>& o, int kbeg, int kend, f32x4 (&acc)[MBW]) {
+template <int UNR, int MBW, bool QUAD>
+__device__ __forceinline__ void skinny_k_slice(const SkinnyOperands<MBW, QUAD>& o, int kbeg, int kend, f32x4 (&acc)[MBW]) {
+  const auto frag = [](const uint16_t* p) -> bf16x8 {
+    const bf16x8 f = *reinterpret_cast<const bf16x8*>(p);
+    if constexpr (QUAD) return skinny_to_mfma_lane(f); else return f;
+  };
   f32x4 a[MBW];
 #pragma unroll
   for (int mb = 0; mb < MBW; ++mb) a[mb] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -133,9 +153,9 @@ __device__ __forceinline__ void skinny_k_slice(const SkinnyOperands<MBW>& o, int
     bf16x8 wf[UNR], xf[UNR][MBW];
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
-      wf[u] = *reinterpret_cast<const bf16x8*>(o.wp + (ks + u) * 32);
+      wf[u] = frag(o.wp + (ks + u) * 32);
 #pragma unroll
-      for (int mb = 0; mb < MBW; ++mb) xf[u][mb] = *reinterpret_cast<const bf16x8*>(o.ip[mb] + (ks + u) * 32);
+      for (int mb = 0; mb < MBW; ++mb) xf[u][mb] = frag(o.ip[mb] + (ks + u) * 32);
     }
 #pragma unroll
     for (int u = 0; u < UNR; ++u)
@@ -143,10 +163,10 @@ __device__ __forceinline__ void skinny_k_slice(const SkinnyOperands<MBW>& o, int
       for (int mb = 0; mb < MBW; ++mb) a[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[u], xf[u][mb], a[mb], 0, 0, 0);
   }
   for (; ks < kend; ++ks) {
-    const bf16x8 wf = *reinterpret_cast<const bf16x8*>(o.wp + ks * 32);
+    const bf16x8 wf = frag(o.wp + ks * 32);
 #pragma unroll
     for (int mb = 0; mb < MBW; ++mb)
-      a[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, *reinterpret_cast<const bf16x8*>(o.ip[mb] + ks * 32), a[mb], 0, 0, 0);
+      a[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, frag(o.ip[mb] + ks * 32), a[mb], 0, 0, 0);
   }
 #pragma unroll
   for (int mb = 0; mb < MBW; ++mb) acc[mb] = a[mb];
