@@ -217,6 +217,15 @@ SALAD_F32_STAGES_PROTOTYPES = {
     "vpr_salad_f32_stage_outputs": (c_int, [_P, c_size_t] + [c_int] * 7 + [_PP] * 14),
 }
 
+# include/vpr_amd_patch_fp8.h, the tenth table: the local-feature re-ranking on e4m3 bytes of x * 2^PATCH_FP8_SHIFT
+PATCH_FP8_SHIFT = 8                                         # VPR_PATCH_FP8_SHIFT
+PATCH_FP8_MIN_L, PATCH_FP8_MAX_L = 64, 256                  # VPR_PATCH_FP8_MIN_L, VPR_PATCH_FP8_MAX_L
+PATCH_FP8_PROTOTYPES = {
+    "vpr_patch_quantize_fp8": (c_int, [_P, c_int, c_longlong, _P, _P]),     # x x_is_bf16 count out stream
+    "vpr_patch_workspace_bytes_fp8": (c_size_t, [c_int] * 2),               # B kc
+    "vpr_patch_rerank_fp8": LOCAL_PROTOTYPES["vpr_local_rerank"],           # the parameter list of the eighth table's call
+}
+
 
 def rerank_roundings(D: int, rows_are_f32: bool) -> int:
     """VPR_RERANK_ROUNDINGS: L of the fine score, the roundings on the longest path from a product to the result."""
@@ -243,7 +252,8 @@ def lib() -> ctypes.CDLL:
                                           + list(EXPAND_PROTOTYPES.items()) + list(PROJECT_PROTOTYPES.items())
                                           + list(RERANK_PROTOTYPES.items()) + list(SALAD_STAGES_PROTOTYPES.items())
                                           + list(SALAD_ANYRES_PROTOTYPES.items()) + list(SALAD_HIRES_PROTOTYPES.items())
-                                          + list(LOCAL_PROTOTYPES.items()) + list(SALAD_F32_STAGES_PROTOTYPES.items())):
+                                          + list(LOCAL_PROTOTYPES.items()) + list(SALAD_F32_STAGES_PROTOTYPES.items())
+                                          + list(PATCH_FP8_PROTOTYPES.items())):
             fn = getattr(handle, name)   # AttributeError if a declared symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

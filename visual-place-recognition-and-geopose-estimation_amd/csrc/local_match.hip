@@ -1,10 +1,14 @@
-// local_match.hip — local-feature re-ranking: mutual-nearest-neighbour patch matching (contract: include/vpr_amd_local.h).
+// local_match.hip — local-feature re-ranking: mutual-nearest-neighbour patch matching (contracts: include/vpr_amd_local.h for
+// bf16 features, include/vpr_amd_patch_fp8.h for e4m3 bytes and their quantiser).  One match kernel, a template on the element:
+// the two forms differ in the operand fetch, the MFMA step and one exact scale of the accumulator; everything after it — the
+// two argmax folds, the reductions, the match decision, the score — is the same code.
 // match: a (query, group of LM_GROUP candidates) grid of 8-wave workgroups.  Liveness comes from the index alone: a workgroup
 // without a live candidate ends before it loads or stages anything.  Wave w owns query rows 32 w .. 32 w + 31 and keeps their
-// MFMA A-fragments (l / 16 of them) in registers while the workgroup walks its candidates; each live candidate's features are
-// staged once in LDS with 16-byte loads, rows padded to a multiple of 32 with zeros, chunks XOR-swizzled so the B-fragment
-// ds_read_b128 of the 32x32x16 operand map is conflict-free.  S is never stored: a wave forms one 32 x 32 tile of it at a time
-// (column on the lane, rows in the 16 registers) and folds it into
+// MFMA A-fragments (l / 16 bf16 ones, l / 64 e4m3 ones) in registers while the workgroup walks its candidates; each live
+// candidate's features are staged once in LDS with 16-byte loads, rows padded to a multiple of 32 with zeros, chunks
+// XOR-swizzled so the B-fragment ds_read_b128 of the operand map (32x32x16 bf16: one chunk per step; 32x32x64 e4m3: two) is
+// conflict-free.  S is never stored: a wave forms one 32 x 32 tile of it at a time (column on the lane, rows in the 16
+// registers) and folds it into
 //   - a running (value, index) per register for the row argmax r(i): columns ascend per lane, so a strict > keeps the lowest
 //     index; the 32 lanes of a half are reduced once per candidate with the index in the comparison;
 //   - a per-lane (value, index) over the 16 registers for the column argmax c(j): the two halves are combined through lane
@@ -16,6 +20,7 @@
 #include "vpr_common.h"
 #include "vpr_internal.h"
 #include "../../include/vpr_amd_local.h"
+#include "../../include/vpr_amd_patch_fp8.h"
 
 namespace vpr {
 
@@ -30,29 +35,37 @@ __device__ __forceinline__ bool lm_better(float av, int ai, float bv, int bi) {
   return ai >= 0 && (bi < 0 || av > bv || (av == bv && ai < bi));
 }
 
-// Swizzle of the staged features: chunk c of row r (a row is CPR = L / 8 chunks of 16 B) sits at chunk c ^ f(r) of its row,
-// f chosen so that 16 consecutive rows at one logical chunk fall into 16 distinct 16-byte slots of the 256-byte bank row.
-// CPR is a multiple of 4, and f(r) stays below the largest power of two (<= 16) dividing CPR: the XOR stays inside the row.
-template <int L>
+// Swizzle of the staged features: chunk c of row r (a row is CPR chunks of 16 B: L / 8 for bf16, L / 16 for e4m3) sits at
+// chunk c ^ f(r) of its row, f(r) = (r >> SH) & MASK with (SH, MASK) = (0, 15) if 16 | CPR, (1, 7) if 8 | CPR, else (2, 3): the
+// 16 rows of a ds_read_b128 lane group at one logical chunk fall into 16 distinct 16-byte slots of the 256-byte bank row.  CPR
+// is a multiple of 4, and f(r) stays below the largest power of two (<= 16) dividing CPR: the XOR stays inside the row, and
+// chunks 2 m and 2 m + 1 (the two reads of an e4m3 operand) stay a pair.  Restated and checked exhaustively on the host for
+// every supported width of both elements (tests/test_local_match_fp8_cpu.py).
+template <int CPR>
 __device__ __forceinline__ int lm_off(int row, int chunk) {
-  constexpr int CPR = L / 8;
+  static_assert(CPR % 4 == 0 && CPR <= 32, "a row is a whole number of 64-byte groups");
   constexpr int SH = CPR % 16 == 0 ? 0 : CPR % 8 == 0 ? 1 : 2, MASK = CPR % 16 == 0 ? 15 : CPR % 8 == 0 ? 7 : 3;
   return (row * CPR + (chunk ^ ((row >> SH) & MASK))) << 4;
 }
 
-// LDS of one workgroup: features [ngp][L] bf16 | column best value [8][ngp] f32 | column best row [8][ngp] i32 |
+// LDS of one workgroup: features [ngp][L] elements of es bytes | column best value [8][ngp] f32 | column best row [8][ngp] i32 |
 // row_nn [256] i32 | wave sums [4] f32 + wave counts [4] i32, ngp = n_g rounded up to 32
-inline size_t lm_lds_bytes(int n_g, int l) {
+inline size_t lm_lds_bytes(int n_g, int l, int es) {
   const size_t ngp = (size_t)(n_g + 31) / 32 * 32;
-  return ngp * l * 2 + 2 * LM_WAVES * ngp * 4 + LM_MAX_N * 4 + 32;
+  return ngp * l * es + 2 * LM_WAVES * ngp * 4 + LM_MAX_N * 4 + 32;
 }
 
-template <int L>
-__global__ __launch_bounds__(LM_THREADS) void local_match_kernel(
-    const uint16_t* __restrict__ q_local, int n_q, const int32_t* __restrict__ idx, int kc, const uint16_t* __restrict__ g_local,
+// Elem = uint16_t: bf16 features, S = the accumulator.  Elem = uint8_t: e4m3 bytes of x * 2^8, S = 2^-16 * the accumulator.
+// The e4m3 form at l <= 128 asks for 4 waves per SIMD (<= 128 VGPRs): with its 49 KB of LDS two workgroups then share a CU.
+template <typename Elem, int L>
+__global__ __launch_bounds__(LM_THREADS, (sizeof(Elem) == 1 && L <= 128) ? 4 : 1) void local_match_kernel(
+    const Elem* __restrict__ q_local, int n_q, const int32_t* __restrict__ idx, int kc, const Elem* __restrict__ g_local,
     int n_g, int n_local, int index_base, float min_sim, float* __restrict__ ws_score, int32_t* __restrict__ ws_matches,
     float* __restrict__ pair_score, int32_t* __restrict__ pair_matches, int32_t* __restrict__ row_nn, int32_t* __restrict__ col_nn) {
-  constexpr int KS = L / 16, CPR = L / 8;
+  constexpr bool FP8 = sizeof(Elem) == 1;
+  constexpr int EPC = 16 / sizeof(Elem);                              // elements per 16-byte chunk
+  constexpr int CPR = L / EPC, KS = FP8 ? L / 64 : L / 16;            // chunks per row; MFMA k-steps
+  using Frag = std::conditional_t<FP8, i32x8, bf16x8>;
   extern __shared__ __attribute__((aligned(16))) char s_mem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 31, h = lane >> 5;
   const long long b = blockIdx.x;                                     // queries on x: the grid's y extent is 16 bits
@@ -60,7 +73,7 @@ __global__ __launch_bounds__(LM_THREADS) void local_match_kernel(
   const int ngp = (n_g + 31) / 32 * 32, ntile = ngp / 32;
   const int nqt = (n_q + 31) / 32;                                    // row tiles that exist
   char* s_g = s_mem;
-  float* s_colv = reinterpret_cast<float*>(s_mem + (size_t)ngp * L * 2);
+  float* s_colv = reinterpret_cast<float*>(s_mem + (size_t)ngp * L * sizeof(Elem));
   int* s_coli = reinterpret_cast<int*>(s_colv + LM_WAVES * ngp);
   int* s_rownn = s_coli + LM_WAVES * ngp;
   float* s_part = reinterpret_cast<float*>(s_rownn + LM_MAX_N);
@@ -84,16 +97,23 @@ __global__ __launch_bounds__(LM_THREADS) void local_match_kernel(
   }
   if (!any) return;                                                   // nothing of this group is local: no loads, no staging
 
-  // the query's A-fragments: lane holds Q[32 wave + li][16 ks + 8 h .. + 8]; rows past n_q are zero
-  bf16x8 a[KS];
+  // the query's A-fragments: lane holds Q[32 wave + li][16 ks + 8 h .. + 8] (bf16) or Q[32 wave + li][64 ks + 32 h .. + 32]
+  // (e4m3: chunks 4 ks + 2 h and 4 ks + 2 h + 1 of its row, as the B side reads them); rows past n_q are zero
+  Frag a[KS];
   {
     const int row = wave * 32 + li;
-    const uint16_t* qrow = q_local + (b * n_q + (row < n_q ? row : 0)) * L + 8 * h;
+    const Elem* qrow = q_local + (b * n_q + (row < n_q ? row : 0)) * L + (FP8 ? 32 : 8) * h;
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      i32x4 v = *reinterpret_cast<const i32x4*>(qrow + 16 * ks);
-      if (row >= n_q) v = i32x4{0, 0, 0, 0};
-      a[ks] = __builtin_bit_cast(bf16x8, v);
+      if constexpr (FP8) {
+        i32x4 lo = *reinterpret_cast<const i32x4*>(qrow + 64 * ks), hi = *reinterpret_cast<const i32x4*>(qrow + 64 * ks + 16);
+        if (row >= n_q) lo = hi = i32x4{0, 0, 0, 0};
+        a[ks] = e4m3_operand(lo, hi);
+      } else {
+        i32x4 v = *reinterpret_cast<const i32x4*>(qrow + 16 * ks);
+        if (row >= n_q) v = i32x4{0, 0, 0, 0};
+        a[ks] = __builtin_bit_cast(bf16x8, v);
+      }
     }
   }
 
@@ -104,12 +124,12 @@ __global__ __launch_bounds__(LM_THREADS) void local_match_kernel(
     const long long p = b * kc + j0 + g;
     __syncthreads();                                                  // the previous candidate's LDS is no longer read
     {                                                                 // stage [n_g][L] -> LDS, rows n_g .. ngp - 1 zero
-      const uint16_t* gimg = g_local + grow * n_g * L;                // 0 <= grow < n_local: inside g_local
+      const Elem* gimg = g_local + grow * n_g * L;                     // 0 <= grow < n_local: inside g_local
       for (int t = tid; t < ngp * CPR; t += LM_THREADS) {
         const int row = t / CPR, c = t - row * CPR;
         i32x4 v = i32x4{0, 0, 0, 0};
-        if (row < n_g) v = *reinterpret_cast<const i32x4*>(gimg + (long long)row * L + 8 * c);
-        *reinterpret_cast<i32x4*>(s_g + lm_off<L>(row, c)) = v;
+        if (row < n_g) v = *reinterpret_cast<const i32x4*>(gimg + (long long)row * L + EPC * c);
+        *reinterpret_cast<i32x4*>(s_g + lm_off<CPR>(row, c)) = v;
       }
     }
     __syncthreads();
@@ -125,8 +145,18 @@ __global__ __launch_bounds__(LM_THREADS) void local_match_kernel(
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-          const bf16x8 bf = *reinterpret_cast<const bf16x8*>(s_g + lm_off<L>(jt * 32 + li, 2 * ks + h));
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks], bf, acc, 0, 0, 0);
+          if constexpr (FP8) {
+            const i32x4 lo = *reinterpret_cast<const i32x4*>(s_g + lm_off<CPR>(jt * 32 + li, 4 * ks + 2 * h));
+            const i32x4 hi = *reinterpret_cast<const i32x4*>(s_g + lm_off<CPR>(jt * 32 + li, 4 * ks + 2 * h + 1));
+            acc = mfma_e4m3_32x32x64(a[ks], e4m3_operand(lo, hi), acc);
+          } else {
+            const bf16x8 bf = *reinterpret_cast<const bf16x8*>(s_g + lm_off<CPR>(jt * 32 + li, 2 * ks + h));
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks], bf, acc, 0, 0, 0);
+          }
+        }
+        if constexpr (FP8) {                                          // both operands carry 2^8: exact, see the header
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[r] *= 0x1p-16f;
         }
         // acc[r] = S[32 wave + (r & 3) + 8 (r >> 2) + 4 h][32 jt + li]
         const int col = jt * 32 + li;
@@ -219,56 +249,170 @@ __global__ __launch_bounds__(ORDER_MAX_KC) void local_order_kernel(
   }
 }
 
-template <int L>
-int launch_local_match(dim3 grid, size_t lds, hipStream_t s, const uint16_t* q_local, int n_q, const int32_t* idx, int kc,
-                       const uint16_t* g_local, int n_g, int n_local, int index_base, float min_sim, float* ws_score,
+template <typename Elem, int L>
+int launch_local_match(dim3 grid, size_t lds, hipStream_t s, const Elem* q_local, int n_q, const int32_t* idx, int kc,
+                       const Elem* g_local, int n_g, int n_local, int index_base, float min_sim, float* ws_score,
                        int32_t* ws_matches, float* pair_score, int32_t* pair_matches, int32_t* row_nn, int32_t* col_nn) {
-  VPR_TRY_LAUNCH(optin_dynamic_lds<local_match_kernel<L>>(lm_lds_bytes(LM_MAX_N, L)));      // the LDS size varies per call: the maximum
-  return launch_kernel(local_match_kernel<L>, grid, dim3(LM_THREADS), lds, s, q_local, n_q, idx, kc, g_local, n_g, n_local,
+  VPR_TRY_LAUNCH((optin_dynamic_lds<local_match_kernel<Elem, L>>(lm_lds_bytes(LM_MAX_N, L, sizeof(Elem)))));   // the LDS size varies per call: the maximum
+  return launch_kernel(local_match_kernel<Elem, L>, grid, dim3(LM_THREADS), lds, s, q_local, n_q, idx, kc, g_local, n_g, n_local,
                        index_base, min_sim, ws_score, ws_matches, pair_score, pair_matches, row_nn, col_nn);
 }
 
 inline size_t lm_ws_half(int B, int kc) { return align_up((size_t)(B > 0 ? B : 1) * kc * sizeof(float), 256); }
+inline size_t lm_ws_bytes(int B, int kc) {
+  if (B < 0 || kc < 1 || kc > VPR_LOCAL_MAX_KC) return 0;
+  return 2 * lm_ws_half(B, kc);                                       // f32 scores | i32 match counts
+}
+
+// The checks and the two launches of both element types; l_step = the width's granule (32 bf16, 64 e4m3).
+template <typename Elem>
+int local_rerank_run(const Elem* q_local, int n_q, const int32_t* idx, int B, int kc, const Elem* g_local, int n_g, int l,
+                     int n_local, int index_base, float min_sim, int k_out, float* vals_out, int32_t* idx_out, int32_t* matches_out,
+                     float* pair_score, int32_t* pair_matches, int32_t* row_nn, int32_t* col_nn, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  constexpr bool FP8 = sizeof(Elem) == 1;
+  constexpr int l_step = FP8 ? VPR_PATCH_FP8_MIN_L : 32;
+  if (!q_local || !idx || !g_local || !vals_out || !idx_out || !workspace) return VPR_ERR_INVALID_ARG;
+  if (B < 0 || n_q < 0 || n_g < 0 || l < 0 || kc < 0 || n_local < 0 || index_base < 0) return VPR_ERR_INVALID_ARG;
+  if (k_out < 1 || k_out > kc) return VPR_ERR_INVALID_ARG;
+  if (isnan(min_sim)) return VPR_ERR_INVALID_ARG;
+  if (kc > VPR_LOCAL_MAX_KC || n_q == 0 || n_q > LM_MAX_N || n_g == 0 || n_g > LM_MAX_N) return VPR_ERR_UNSUPPORTED;
+  if (l == 0 || l % l_step != 0 || l > VPR_LOCAL_MAX_L) return VPR_ERR_UNSUPPORTED;
+  if (!aligned16(q_local) || !aligned16(g_local) || !aligned16(workspace)) return VPR_ERR_UNSUPPORTED;   // read as 16-byte chunks
+  if (!aligned4(idx) || !aligned4(vals_out) || !aligned4(idx_out) || !aligned4(matches_out) || !aligned4(pair_score) ||
+      !aligned4(pair_matches) || !aligned4(row_nn) || !aligned4(col_nn)) return VPR_ERR_UNSUPPORTED;
+  if (workspace_bytes < lm_ws_bytes(B, kc)) return VPR_ERR_UNSUPPORTED;
+  if (B == 0) return VPR_OK;
+  float* ws_score = static_cast<float*>(workspace);
+  int32_t* ws_matches = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + lm_ws_half(B, kc));
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)B, (unsigned)((kc + LM_GROUP - 1) / LM_GROUP));
+  const size_t lds = lm_lds_bytes(n_g, l, sizeof(Elem));
+#define LM_CASE(LL) case LL: VPR_TRY_LAUNCH((launch_local_match<Elem, LL>(grid, lds, s, q_local, n_q, idx, kc, g_local, n_g, n_local, \
+    index_base, min_sim, ws_score, ws_matches, pair_score, pair_matches, row_nn, col_nn))); break;
+  if constexpr (FP8) {
+    switch (l) {
+      LM_CASE(64) LM_CASE(128) LM_CASE(192) LM_CASE(256)
+      default: return VPR_ERR_UNSUPPORTED;
+    }
+  } else {
+    switch (l) {
+      LM_CASE(32) LM_CASE(64) LM_CASE(96) LM_CASE(128) LM_CASE(160) LM_CASE(192) LM_CASE(224) LM_CASE(256)
+      default: return VPR_ERR_UNSUPPORTED;
+    }
+  }
+#undef LM_CASE
+  VPR_TRY_LAUNCH(launch_kernel(local_order_kernel, dim3((unsigned)B), dim3(ORDER_MAX_KC), 0, s,
+                               static_cast<const float*>(ws_score), static_cast<const int32_t*>(ws_matches), idx, kc, n_local,
+                               index_base, k_out, vals_out, idx_out, matches_out));
+  return VPR_OK;
+}
+
+// ---- the quantiser of include/vpr_amd_patch_fp8.h ---------------------------------------------------------------------
+// One value -> the e4m3fn byte of x * 2^8.  The scale is exact in f32 (an overflow to +-Inf is a finite x beyond the range:
+// it saturates); the clamp decides saturation, the hardware convert only ever sees |v| <= 448 and rounds once, to nearest
+// even, subnormals included; fmaxf / fminf keep the sign of a zero.
+__device__ __forceinline__ float pq_scaled(float x) { return fminf(fmaxf(x * 256.0f, -448.0f), 448.0f); }
+__device__ __forceinline__ bool pq_nonfinite(float x) { return !(fabsf(x) <= FLT_MAX); }
+__device__ __forceinline__ uint32_t pq_byte(float x) {
+  const uint32_t b = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(pq_scaled(x), 0.f, 0, false) & 0xffu;
+  return pq_nonfinite(x) ? 0x7fu : b;
+}
+// four values -> four bytes, element 0 lowest
+__device__ __forceinline__ uint32_t pq_word(float x0, float x1, float x2, float x3) {
+  int pk = __builtin_amdgcn_cvt_pk_fp8_f32(pq_scaled(x0), pq_scaled(x1), 0, false);
+  pk = __builtin_amdgcn_cvt_pk_fp8_f32(pq_scaled(x2), pq_scaled(x3), pk, true);
+  uint32_t w = (uint32_t)pk;
+  if (pq_nonfinite(x0)) w = (w & 0xffffff00u) | 0x0000007fu;
+  if (pq_nonfinite(x1)) w = (w & 0xffff00ffu) | 0x00007f00u;
+  if (pq_nonfinite(x2)) w = (w & 0xff00ffffu) | 0x007f0000u;
+  if (pq_nonfinite(x3)) w = (w & 0x00ffffffu) | 0x7f000000u;
+  return w;
+}
+template <bool BF16>
+__device__ __forceinline__ float pq_load(const void* x, long long i) {
+  if constexpr (BF16) return bf16_bits_to_f32(static_cast<const uint16_t*>(x)[i]);
+  else return static_cast<const float*>(x)[i];
+}
+
+constexpr int PQ_THREADS = 256;
+// Elements [0, head) and [head + 16 nvec, count) one per thread; the nvec groups of 16 between them with 16-byte loads and
+// one 16-byte store (the host chose head so that both x + head and out + head are 16-byte aligned, or nvec = 0).
+template <bool BF16>
+__global__ __launch_bounds__(PQ_THREADS) void patch_quantize_fp8_kernel(const void* __restrict__ x, long long count, long long head,
+                                                                        long long nvec, uint8_t* __restrict__ out) {
+  const long long t0 = (long long)blockIdx.x * PQ_THREADS + threadIdx.x, stride = (long long)gridDim.x * PQ_THREADS;
+  for (long long v = t0; v < nvec; v += stride) {
+    const long long e = head + 16 * v;
+    uint32_t w[4];
+    if constexpr (BF16) {
+      const i32x4* src = reinterpret_cast<const i32x4*>(static_cast<const uint16_t*>(x) + e);
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const i32x4 u = src[c];
+        w[2 * c] = pq_word(bf16_lo(u[0]), bf16_hi(u[0]), bf16_lo(u[1]), bf16_hi(u[1]));
+        w[2 * c + 1] = pq_word(bf16_lo(u[2]), bf16_hi(u[2]), bf16_lo(u[3]), bf16_hi(u[3]));
+      }
+    } else {
+      const f32x4* src = reinterpret_cast<const f32x4*>(static_cast<const float*>(x) + e);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const f32x4 u = src[c];
+        w[c] = pq_word(u[0], u[1], u[2], u[3]);
+      }
+    }
+    *reinterpret_cast<i32x4*>(out + e) = i32x4{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+  }
+  const long long tail0 = head + 16 * nvec, nscalar = head + (count - tail0);
+  for (long long t = t0; t < nscalar; t += stride) {
+    const long long e = t < head ? t : tail0 + (t - head);
+    out[e] = (uint8_t)pq_byte(pq_load<BF16>(x, e));
+  }
+}
 
 }  // namespace vpr
 
 using namespace vpr;
 
-extern "C" size_t vpr_local_workspace_bytes(int B, int kc) {
-  if (B < 0 || kc < 1 || kc > VPR_LOCAL_MAX_KC) return 0;
-  return 2 * lm_ws_half(B, kc);                                       // f32 scores | i32 match counts
-}
+extern "C" size_t vpr_local_workspace_bytes(int B, int kc) { return lm_ws_bytes(B, kc); }
 
 extern "C" int vpr_local_rerank(const uint16_t* q_local, int n_q, const int32_t* idx, int B, int kc,
                                 const uint16_t* g_local, int n_g, int l, int n_local, int index_base, float min_sim,
                                 int k_out, float* vals_out, int32_t* idx_out, int32_t* matches_out,
                                 float* pair_score, int32_t* pair_matches, int32_t* row_nn, int32_t* col_nn,
                                 void* workspace, size_t workspace_bytes, void* stream) {
-  if (!q_local || !idx || !g_local || !vals_out || !idx_out || !workspace) return VPR_ERR_INVALID_ARG;
-  if (B < 0 || n_q < 0 || n_g < 0 || l < 0 || kc < 0 || n_local < 0 || index_base < 0) return VPR_ERR_INVALID_ARG;
-  if (k_out < 1 || k_out > kc) return VPR_ERR_INVALID_ARG;
-  if (isnan(min_sim)) return VPR_ERR_INVALID_ARG;
-  if (kc > VPR_LOCAL_MAX_KC || n_q == 0 || n_q > LM_MAX_N || n_g == 0 || n_g > LM_MAX_N) return VPR_ERR_UNSUPPORTED;
-  if (l == 0 || l % 32 != 0 || l > VPR_LOCAL_MAX_L) return VPR_ERR_UNSUPPORTED;
-  if (!aligned16(q_local) || !aligned16(g_local) || !aligned16(workspace)) return VPR_ERR_UNSUPPORTED;   // read as 16-byte chunks
-  if (!aligned4(idx) || !aligned4(vals_out) || !aligned4(idx_out) || !aligned4(matches_out) || !aligned4(pair_score) ||
-      !aligned4(pair_matches) || !aligned4(row_nn) || !aligned4(col_nn)) return VPR_ERR_UNSUPPORTED;
-  if (workspace_bytes < vpr_local_workspace_bytes(B, kc)) return VPR_ERR_UNSUPPORTED;
-  if (B == 0) return VPR_OK;
-  float* ws_score = static_cast<float*>(workspace);
-  int32_t* ws_matches = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + lm_ws_half(B, kc));
+  return local_rerank_run<uint16_t>(q_local, n_q, idx, B, kc, g_local, n_g, l, n_local, index_base, min_sim, k_out, vals_out, idx_out,
+                                    matches_out, pair_score, pair_matches, row_nn, col_nn, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t vpr_patch_workspace_bytes_fp8(int B, int kc) { return lm_ws_bytes(B, kc); }
+
+extern "C" int vpr_patch_rerank_fp8(const uint8_t* q_local, int n_q, const int32_t* idx, int B, int kc,
+                                    const uint8_t* g_local, int n_g, int l, int n_local, int index_base, float min_sim,
+                                    int k_out, float* vals_out, int32_t* idx_out, int32_t* matches_out,
+                                    float* pair_score, int32_t* pair_matches, int32_t* row_nn, int32_t* col_nn,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+  return local_rerank_run<uint8_t>(q_local, n_q, idx, B, kc, g_local, n_g, l, n_local, index_base, min_sim, k_out, vals_out, idx_out,
+                                   matches_out, pair_score, pair_matches, row_nn, col_nn, workspace, workspace_bytes, stream);
+}
+
+extern "C" int vpr_patch_quantize_fp8(const void* x, int x_is_bf16, long long count, uint8_t* out, void* stream) {
+  if (!x || !out || count < 0) return VPR_ERR_INVALID_ARG;
+  const size_t es = x_is_bf16 ? 2 : 4;
+  if (reinterpret_cast<uintptr_t>(x) % es != 0) return VPR_ERR_UNSUPPORTED;
+  if (count == 0) return VPR_OK;
+  long long head = (long long)((16 - reinterpret_cast<uintptr_t>(out) % 16) % 16);
+  if (head > count) head = count;
+  const bool vec = (reinterpret_cast<uintptr_t>(x) + (size_t)head * es) % 16 == 0;
+  const long long nvec = vec ? (count - head) / 16 : 0;
+  const long long work = nvec > count - 16 * nvec ? nvec : count - 16 * nvec;
+  long long blocks = (work + PQ_THREADS - 1) / PQ_THREADS;
+  if (blocks > 8192) blocks = 8192;                                   // grid-stride beyond
   const hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)B, (unsigned)((kc + LM_GROUP - 1) / LM_GROUP));
-  const size_t lds = lm_lds_bytes(n_g, l);
-#define LM_CASE(LL) case LL: VPR_TRY_LAUNCH(launch_local_match<LL>(grid, lds, s, q_local, n_q, idx, kc, g_local, n_g, n_local, \
-    index_base, min_sim, ws_score, ws_matches, pair_score, pair_matches, row_nn, col_nn)); break;
-  switch (l) {
-    LM_CASE(32) LM_CASE(64) LM_CASE(96) LM_CASE(128) LM_CASE(160) LM_CASE(192) LM_CASE(224) LM_CASE(256)
-    default: return VPR_ERR_UNSUPPORTED;
+  if (x_is_bf16) {
+    VPR_TRY_LAUNCH(launch_kernel(patch_quantize_fp8_kernel<true>, dim3((unsigned)blocks), dim3(PQ_THREADS), 0, s, x, count, head, nvec, out));
+  } else {
+    VPR_TRY_LAUNCH(launch_kernel(patch_quantize_fp8_kernel<false>, dim3((unsigned)blocks), dim3(PQ_THREADS), 0, s, x, count, head, nvec, out));
   }
-#undef LM_CASE
-  VPR_TRY_LAUNCH(launch_kernel(local_order_kernel, dim3((unsigned)B), dim3(ORDER_MAX_KC), 0, s,
-                               static_cast<const float*>(ws_score), static_cast<const int32_t*>(ws_matches), idx, kc, n_local,
-                               index_base, k_out, vals_out, idx_out, matches_out));
   return VPR_OK;
 }

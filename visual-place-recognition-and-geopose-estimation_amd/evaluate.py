@@ -316,7 +316,7 @@ def _check_grid(extractor, image_size: int) -> None:
 @torch.no_grad()
 def build_gallery_from_images(extractor: DinoV2Salad, csv_path: str, image_dir: str, out_dir: str, *, fp8: bool = False,
                               batch_size: int = 64, device: str = "cuda", image_size: int = 224, graph: bool = True,
-                              projection=None, whiten: bool = True, keep_fine: bool = False, keep_local: bool = False) -> int:
+                              projection=None, whiten: bool = True, keep_fine: bool = False, keep_local=False) -> int:
     """labels CSV (`filename,timestamp,latitude,longitude,angle,Region_ID`, cleaned_dataset_files/labels_train.csv:1) +
     images -> on-disk gallery (gallery.save_gallery: bf16 rows, or e4m3 rows + per-row scales with fp8=True).
     Preprocessing = the DINOv2+SALAD validation transform (dinov2salad_validation.py:18-22).  Returns the row count.
@@ -328,8 +328,11 @@ def build_gallery_from_images(extractor: DinoV2Salad, csv_path: str, image_dir: 
     calculate_retrieval_scores(rerank=); a plain bf16 gallery's rows are those descriptors already, and nothing is added.
     keep_local: the gallery also keeps every image's local features (local_features.npy: [N, n, 128] bf16 from the same
     backbone pass, DinoV2Salad.features(want_local=True); at most 256 patch tokens), what
-    calculate_retrieval_scores(local_rerank=) matches against."""
+    calculate_retrieval_scores(local_rerank=) matches against.  keep_local="fp8": their e4m3 store instead
+    (local_features_fp8.npy: [N, n, 128] uint8, features(want_local="fp8"); half the bytes — 32 KB per image at n = 256)."""
     from . import gallery as G, ops
+    if keep_local not in (False, True, "fp8"):
+        raise ValueError(f"build_gallery_from_images: keep_local must be False, True or 'fp8', got {keep_local!r}")
     _check_grid(extractor, image_size)
     dev = torch.device(device)
     extractor = extractor.to(dev).to(torch.bfloat16).eval()
@@ -339,9 +342,9 @@ def build_gallery_from_images(extractor: DinoV2Salad, csv_path: str, image_dir: 
     desc = torch.empty((len(names), 8448), dtype=torch.float32, device=dev)
     local = None
     if keep_local:
-        features = lambda x: extractor.features(x, want_local=True)
-        local = torch.empty((len(names), extractor.backbone.num_patches, extractor.aggregator.cluster_dim), dtype=torch.bfloat16,
-                            device=dev)
+        features = lambda x: extractor.features(x, want_local=keep_local)
+        local = torch.empty((len(names), extractor.backbone.num_patches, extractor.aggregator.cluster_dim),
+                            dtype=torch.uint8 if keep_local == "fp8" else torch.bfloat16, device=dev)
         fwd = GraphedForward(features, module=extractor) if graph and dev.type == "cuda" else features
     else:
         fwd = GraphedForward(extractor) if graph and dev.type == "cuda" else extractor
@@ -427,7 +430,8 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
     local_rerank (kc): local-feature re-ranking — every search yields kc coarse candidates, re-ranked to k by the mutual-
     nearest-neighbour matches (similarity >= min_sim) between the query's and the candidates' patch features
     (local_features.npy, build_gallery_from_images(keep_local=True); ShardedGallery.search_local_reranked); topk_scores are
-    then local scores.  Not together with rerank or query_expansion."""
+    then local scores.  Not together with rerank or query_expansion.  A gallery that keeps the e4m3 store instead
+    (local_features_fp8.npy, keep_local="fp8") is matched in that form: the queries' features are features(want_local="fp8")."""
     from . import gallery as G
     from .retrieval import ShardedGallery
     _check_grid(extractor, image_size)
@@ -435,8 +439,9 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
     extractor = extractor.to(dev).to(torch.bfloat16).eval()
     if local_rerank is not None and (rerank is not None or query_expansion is not None):
         raise ValueError("calculate_retrieval_scores: local_rerank combines neither with rerank nor with query_expansion")
-    if local_rerank is not None and not os.path.exists(os.path.join(gallery_dir, G.LOCAL_FILE)):
-        raise ValueError(f"local_rerank: {gallery_dir} has no {G.LOCAL_FILE} (build_gallery_from_images(keep_local=True))")
+    if local_rerank is not None and not any(os.path.exists(os.path.join(gallery_dir, f)) for f in (G.LOCAL_FILE, G.LOCAL_FP8_FILE)):
+        raise ValueError(f"local_rerank: {gallery_dir} has no {G.LOCAL_FILE} (build_gallery_from_images(keep_local=True)) "
+                         f"and no {G.LOCAL_FP8_FILE} (keep_local='fp8')")
     has_fine = os.path.exists(os.path.join(gallery_dir, G.FINE_FILE))
     shard = G.load_gallery_shard(gallery_dir, dev, rank, world, load_fine=rerank is not None and has_fine,
                                  load_local=local_rerank is not None)
@@ -454,7 +459,8 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
     kk = min(k, shard.n_total)
     vals = torch.empty((len(names), kk), dtype=torch.float32, device=dev)
     idx = torch.empty((len(names), kk), dtype=torch.int32, device=dev)
-    features = lambda x: extractor.features(x, want_bf16=True, want_local=local_rerank is not None)
+    want_local = local_rerank is not None and ("fp8" if shard.local.dtype == torch.uint8 else True)
+    features = lambda x: extractor.features(x, want_bf16=True, want_local=want_local)
     fwd = GraphedForward(features, module=extractor) if graph and dev.type == "cuda" else features
     two_tier = {} if rerank is None else {"rerank": int(rerank)}     # named only when asked for
     for idxs, u8 in _batches(image_dir, names, batch_size, dev):

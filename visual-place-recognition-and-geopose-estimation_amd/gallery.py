@@ -15,6 +15,9 @@ On-disk format (a directory; every array is a plain .npy so shards can be memory
   local_features.npy   (optional) [N, n, l] uint16 (bf16 bit patterns): every image's n L2-normalised patch descriptors of
                        width l (SaladAggregator.local_features), what ShardedGallery.search_local_reranked matches the
                        queries' patches against.  A directory without it loads as ever.
+  local_features_fp8.npy (optional, instead of local_features.npy: a directory never holds both) [N, n, l] uint8: the same
+                       features as OCP e4m3 bytes of x * 2^8 (ops.quantize_patch_fp8, include/vpr_amd_patch_fp8.h), half the
+                       bytes; the search then matches on them (ops.local_rerank_fp8).
 Rank r of R loads rows [N*r/R, N*(r+1)/R) only.
 """
 from __future__ import annotations
@@ -35,6 +38,7 @@ LABEL_COLUMNS = ("latitude", "longitude", "angle", "Region_ID")
 PROJECTION_FILE = "projection.npz"
 FINE_FILE = "fine_descriptors.npy"
 LOCAL_FILE = "local_features.npy"
+LOCAL_FP8_FILE = "local_features_fp8.npy"
 
 
 @dataclass
@@ -47,7 +51,7 @@ class GalleryShard:
     dtype: str
     labels_dev: Optional[torch.Tensor] = None   # [N, 4] float64 on the GPU: the same table for ops.retrieval_pose (device_labels)
     projection: Optional["DescriptorProjection"] = None   # what the rows went through (projection.npz), or None
-    local: Optional[torch.Tensor] = None  # [n_local, n, l] bf16 on the GPU (local_features.npy; load_local), or None
+    local: Optional[torch.Tensor] = None  # [n_local, n, l] bf16 (local_features.npy) or uint8 (local_features_fp8.npy) on the GPU (load_local), or None
     fine: Optional[torch.Tensor] = None   # [n_local, D_fine] bf16 on the GPU (fine_descriptors.npy; load_fine), or None
 
 
@@ -57,10 +61,12 @@ def save_gallery(path: str, descriptors: torch.Tensor, labels: np.ndarray, scale
     """descriptors: [N,D] torch.bfloat16 (bf16 gallery) or torch.uint8 (+ scales: fp8 gallery).
     projection: the DescriptorProjection the rows went through (project_gallery); written as projection.npz.
     fine: [N, D_fine] torch.bfloat16, the full-precision descriptors of the same rows; written as fine_descriptors.npy.
-    local: [N, n, l] torch.bfloat16, the local features of the same rows; written as local_features.npy."""
+    local: [N, n, l] torch.bfloat16, the local features of the same rows, written as local_features.npy; or torch.uint8, their
+    e4m3 store, written as local_features_fp8.npy.  The file that is not written is removed."""
     os.makedirs(path, exist_ok=True)
-    if local is not None and (local.dim() != 3 or local.dtype != torch.bfloat16 or local.shape[0] != descriptors.shape[0]):
-        raise ValueError(f"local must be bfloat16 [N, n, l] with one image per descriptor ({descriptors.shape[0]})")
+    if local is not None and (local.dim() != 3 or local.dtype not in (torch.bfloat16, torch.uint8)
+                              or local.shape[0] != descriptors.shape[0]):
+        raise ValueError(f"local must be bfloat16 or uint8 (e4m3 bytes) [N, n, l] with one image per descriptor ({descriptors.shape[0]})")
     if fine is not None and (fine.dim() != 2 or fine.dtype != torch.bfloat16 or fine.shape[0] != descriptors.shape[0]):
         raise ValueError(f"fine must be bfloat16 [N, D_fine] with one row per descriptor ({descriptors.shape[0]})")
     if projection is not None and projection.d != descriptors.shape[1]:
@@ -96,11 +102,12 @@ def save_gallery(path: str, descriptors: torch.Tensor, labels: np.ndarray, scale
         np.save(fine_path, fine.detach().cpu().contiguous().view(torch.uint16).numpy())
     elif os.path.exists(fine_path):            # nor do the old fine rows
         os.remove(fine_path)
-    local_path = os.path.join(path, LOCAL_FILE)
-    if local is not None:
-        np.save(local_path, local.detach().cpu().contiguous().view(torch.uint16).numpy())
-    elif os.path.exists(local_path):           # nor the old local features
-        os.remove(local_path)
+    for name, dtype, view in ((LOCAL_FILE, torch.bfloat16, torch.uint16), (LOCAL_FP8_FILE, torch.uint8, torch.uint8)):
+        local_path = os.path.join(path, name)
+        if local is not None and local.dtype == dtype:
+            np.save(local_path, local.detach().cpu().contiguous().view(view).numpy())
+        elif os.path.exists(local_path):       # nor the old local features, of either kind
+            os.remove(local_path)
 
 
 def device_labels(labels: np.ndarray, device: torch.device) -> torch.Tensor:
@@ -119,7 +126,8 @@ def load_gallery_shard(path: str, device: torch.device, rank: int = 0, world: in
                        device_labels: bool = False, load_fine: bool = False, load_local: bool = False) -> GalleryShard:
     """device_labels: also place the label table on `device` (GalleryShard.labels_dev), for the on-device retrieval pose.
     load_fine: also read this rank's slice of fine_descriptors.npy (GalleryShard.fine); the file must then exist.
-    load_local: also read this rank's slice of local_features.npy (GalleryShard.local); the file must then exist."""
+    load_local: also read this rank's slice of local_features.npy (GalleryShard.local, bf16) or, where the directory holds
+    that one, of local_features_fp8.npy (uint8); one of them must then exist."""
     with open(os.path.join(path, "meta.json")) as f:
         meta = json.load(f)
     if meta.get("version") != 1:
@@ -148,13 +156,14 @@ def load_gallery_shard(path: str, device: torch.device, rank: int = 0, world: in
         fine = torch.from_numpy(np.array(arr[lo:hi])).to(device).view(torch.bfloat16)
     local = None
     if load_local:
-        local_path = os.path.join(path, LOCAL_FILE)
-        if not os.path.exists(local_path):
-            raise ValueError(f"load_local: {path} has no {LOCAL_FILE}")
-        arr = np.load(local_path, mmap_mode="r")
-        if arr.ndim != 3 or arr.shape[0] != meta["n"]:
-            raise ValueError(f"{LOCAL_FILE} is {arr.shape}, the gallery has {meta['n']} rows")
-        local = torch.from_numpy(np.array(arr[lo:hi])).to(device).view(torch.bfloat16)
+        name = LOCAL_FILE if os.path.exists(os.path.join(path, LOCAL_FILE)) else LOCAL_FP8_FILE
+        if not os.path.exists(os.path.join(path, name)):
+            raise ValueError(f"load_local: {path} has no {LOCAL_FILE} and no {LOCAL_FP8_FILE}")
+        arr = np.load(os.path.join(path, name), mmap_mode="r")
+        if arr.ndim != 3 or arr.shape[0] != meta["n"] or arr.dtype != (np.uint16 if name == LOCAL_FILE else np.uint8):
+            raise ValueError(f"{name} is {arr.dtype} {arr.shape}, the gallery has {meta['n']} rows")
+        local = torch.from_numpy(np.array(arr[lo:hi])).to(device)
+        local = local.view(torch.bfloat16) if name == LOCAL_FILE else local
     return GalleryShard(rows, scales, labels, meta["n"], lo, meta["dtype"], labels_dev, projection, local=local, fine=fine)
 
 

@@ -133,13 +133,15 @@ class SaladAggregator(nn.Module):
         return (desc, desc16) if want_bf16 else desc
 
     @torch.no_grad()
-    def local_features(self, tokens: torch.Tensor) -> torch.Tensor:
+    def local_features(self, tokens: torch.Tensor, fp8: bool = False) -> torch.Tensor:
         """Per-patch local descriptors for local-feature re-ranking (include/vpr_amd_local.h): patch tokens [B, n, C] (no cls
         row; bf16 or f32) -> [B, n, cluster_dim] bf16, the cluster_features MLP of every patch in eval arithmetic (its Dropout
         is never applied), L2-normalised per patch in f32; an all-zero output row stays zero.  bf16 tokens on the GPU run the
         two layers on the MFMA GEMM (bf16 operands and hidden layer, f32 accumulation); anything else runs them in f32 torch
         with the f32 weights.  n > 256 (322 px and up) raises before any launch: the matching kernel holds one image's
-        patches in a single tile set."""
+        patches in a single tile set.
+        fp8=True: [B, n, cluster_dim] uint8 instead, the e4m3 store of include/vpr_amd_patch_fp8.h (ops.quantize_patch_fp8),
+        quantised from the f32 normalised value in one rounding, not through bf16; on the GPU only."""
         if tokens.dim() != 3 or tokens.shape[2] != self.num_channels:
             raise ValueError(f"SaladAggregator.local_features: tokens must be [B, n, {self.num_channels}] patch tokens, "
                              f"got {tuple(tokens.shape)}")
@@ -158,6 +160,8 @@ class SaladAggregator(nn.Module):
             f = h @ w.w2_c.T + w.b2_c
         norm = f.norm(dim=1, keepdim=True)
         f = torch.where(norm > 0, f / norm, torch.zeros_like(f))
+        if fp8:
+            return ops.quantize_patch_fp8(f.contiguous()).view(B, n, self.cluster_dim)
         return f.to(torch.bfloat16).view(B, n, self.cluster_dim)
 
     def dropout_p(self) -> float:
@@ -208,21 +212,24 @@ class DinoV2Salad(nn.Module):
         return t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16)
 
     @torch.no_grad()
-    def features(self, x: torch.Tensor, want_bf16: bool = False, events: Optional[list] = None, want_local: bool = False):
+    def features(self, x: torch.Tensor, want_bf16: bool = False, events: Optional[list] = None, want_local=False):
         """images -> descriptor (and its bf16 copy): backbone tokens stay in the layout the backbone
         computed them in (SplitTokens on the HIP path), no re-layout copy before SALAD.
         events: a list -> a (start, end) pair of timing events around the aggregation on the current stream is appended
         (bench.py: the SALAD stage as the step runs it, token MLP on the backbone's cls-row stream).
         want_local: the result gains a last element, the local features [B, n, 128] bf16 of the same backbone pass
         (SaladAggregator.local_features; at most 256 patch tokens, ValueError before the backbone runs otherwise).  The
-        descriptor is the default call's, bit for bit."""
+        descriptor is the default call's, bit for bit.  want_local="fp8": that element is their e4m3 store instead, uint8
+        [B, n, 128] (local_features(fp8=True)); True keeps the bf16 result bit for bit."""
+        if want_local not in (False, True, "fp8"):
+            raise ValueError(f"DinoV2Salad.features: want_local must be False, True or 'fp8', got {want_local!r}")
         if want_local:
             if self.backbone.num_patches > _lib.LOCAL_MAX_N:
                 raise ValueError(f"DinoV2Salad.features(want_local=True): {self.backbone.num_patches} patch tokens per image, but "
                                  f"local-feature re-ranking takes at most {_lib.LOCAL_MAX_N} (224 px images at patch 14)")
             keep: list = []
             out = self._features(x, want_bf16, events, keep)
-            local = self.aggregator.local_features(keep[0])
+            local = self.aggregator.local_features(keep[0], fp8=want_local == "fp8")
             return (*out, local) if want_bf16 else (out, local)
         return self._features(x, want_bf16, events)
 

@@ -953,9 +953,10 @@ def rerank_rows(q: torch.Tensor, idx: torch.Tensor, rows: torch.Tensor, index_ba
     return vals, out
 
 
-def _local_check(what: str, q_local, idx, g_local, k) -> int:
+def _local_check(what: str, q_local, idx, g_local, k, dtype=torch.bfloat16, l_step: int = 32) -> int:
+    """The argument checks of both element types: bf16 features of a width that is a multiple of 32, e4m3 bytes of 64."""
     for t, name in ((q_local, "q_local"), (g_local, "g_local")):
-        _need(t, torch.bfloat16, name, 3)
+        _need(t, dtype, name, 3)
     _need(idx, torch.int32, "idx", 2)
     if idx.shape[0] != q_local.shape[0]:
         raise RuntimeError(f"{what}: q_local and idx disagree on B")
@@ -967,8 +968,8 @@ def _local_check(what: str, q_local, idx, g_local, k) -> int:
         if not 1 <= t.shape[1] <= _lib.LOCAL_MAX_N:
             raise RuntimeError(f"{what}: {name} must hold 1..{_lib.LOCAL_MAX_N} patches per image, got {t.shape[1]}")
     l = q_local.shape[2]
-    if l % 32 or not 32 <= l <= _lib.LOCAL_MAX_L:
-        raise RuntimeError(f"{what}: the feature width must be a multiple of 32 in 32..{_lib.LOCAL_MAX_L}, got {l}")
+    if l % l_step or not l_step <= l <= _lib.LOCAL_MAX_L:
+        raise RuntimeError(f"{what}: the feature width must be a multiple of {l_step} in {l_step}..{_lib.LOCAL_MAX_L}, got {l}")
     kc = idx.shape[1]
     if not 1 <= kc <= _lib.LOCAL_MAX_KC:
         raise RuntimeError(f"{what}: idx must hold 1..{_lib.LOCAL_MAX_KC} candidates per query, got {kc}")
@@ -987,25 +988,20 @@ class LocalRerankDebug(NamedTuple):
     col_nn: torch.Tensor
 
 
-def local_rerank(q_local: torch.Tensor, idx: torch.Tensor, g_local: torch.Tensor, index_base: int = 0, k: Optional[int] = None,
-                 min_sim: float = 0.0, ws: Optional[torch.Tensor] = None, debug: bool = False):
-    """Local-feature re-ranking (include/vpr_amd_local.h): q_local bf16 [B, n_q, l], idx int32 [B, kc] (kc <= 128) the candidates
-    of a search as global rows, g_local = this shard's local features bf16 [n_local, n_g, l], owning global rows index_base ...
-    Returns (vals f32 [B, k], idx int32 [B, k], matches int32 [B, k]): the k best (None: all kc) of the candidates this shard
-    owns by the sum of the similarities of their mutual-nearest-neighbour patch pairs of similarity >= min_sim, (score desc,
-    index asc); everything else is never dereferenced and comes back as (-inf, -1, 0) at the tail.  debug=True: a fourth
-    element, LocalRerankDebug.  ws: a byte buffer of vpr_local_workspace_bytes(B, kc); None: the current stream's cached one."""
-    k = _local_check("local_rerank", q_local, idx, g_local, k)
+def _local_rerank_call(what: str, entry: str, ws_entry: str, dtype, l_step: int, q_local, idx, g_local, index_base, k, min_sim,
+                       ws, debug):
+    """local_rerank / local_rerank_fp8: the checks, the workspace, the outputs and the one library call."""
+    k = _local_check(what, q_local, idx, g_local, k, dtype, l_step)
     min_sim = float(min_sim)
     if min_sim != min_sim:
-        raise RuntimeError("local_rerank: min_sim must be a number")
+        raise RuntimeError(f"{what}: min_sim must be a number")
     B, n_q, l = q_local.shape
     n_local, n_g = g_local.shape[:2]
     kc = idx.shape[1]
     dev = q_local.device
-    need = _lib.lib().vpr_local_workspace_bytes(B, kc)
+    need = getattr(_lib.lib(), ws_entry)(B, kc)
     if ws is None:
-        ws = workspace("local_rerank", need, dev)
+        ws = workspace(what, need, dev)
     else:
         _need(ws, torch.uint8, "ws", 1)
     vals = torch.empty((B, k), dtype=torch.float32, device=dev)
@@ -1017,9 +1013,43 @@ def local_rerank(q_local: torch.Tensor, idx: torch.Tensor, g_local: torch.Tensor
                                torch.empty((B, kc, n_q), dtype=torch.int32, device=dev),
                                torch.empty((B, kc, n_g), dtype=torch.int32, device=dev))
     if B:
-        _call("vpr_local_rerank", _ptr(q_local), n_q, _ptr(idx), B, kc, _ptr(g_local), n_g, l, n_local, int(index_base), min_sim,
+        _call(entry, _ptr(q_local), n_q, _ptr(idx), B, kc, _ptr(g_local), n_g, l, n_local, int(index_base), min_sim,
               k, _ptr(vals), _ptr(out), _ptr(matches), *[_ptr(t) for t in (dbg or (None,) * 4)], _ptr(ws), ws.numel(), _stream())
     return (vals, out, matches, dbg) if debug else (vals, out, matches)
+
+
+def local_rerank(q_local: torch.Tensor, idx: torch.Tensor, g_local: torch.Tensor, index_base: int = 0, k: Optional[int] = None,
+                 min_sim: float = 0.0, ws: Optional[torch.Tensor] = None, debug: bool = False):
+    """Local-feature re-ranking (include/vpr_amd_local.h): q_local bf16 [B, n_q, l], idx int32 [B, kc] (kc <= 128) the candidates
+    of a search as global rows, g_local = this shard's local features bf16 [n_local, n_g, l], owning global rows index_base ...
+    Returns (vals f32 [B, k], idx int32 [B, k], matches int32 [B, k]): the k best (None: all kc) of the candidates this shard
+    owns by the sum of the similarities of their mutual-nearest-neighbour patch pairs of similarity >= min_sim, (score desc,
+    index asc); everything else is never dereferenced and comes back as (-inf, -1, 0) at the tail.  debug=True: a fourth
+    element, LocalRerankDebug.  ws: a byte buffer of vpr_local_workspace_bytes(B, kc); None: the current stream's cached one."""
+    return _local_rerank_call("local_rerank", "vpr_local_rerank", "vpr_local_workspace_bytes", torch.bfloat16, 32, q_local, idx,
+                              g_local, index_base, k, min_sim, ws, debug)
+
+
+def quantize_patch_fp8(x: torch.Tensor) -> torch.Tensor:
+    """Patch features to their e4m3 store (include/vpr_amd_patch_fp8.h): x f32 or bf16 of any shape -> uint8 of that shape, the
+    OCP e4m3fn byte of x * 2^8 per element, one round-to-nearest-even from the f32 value; beyond +-448 / 256 saturates, NaN and
+    +-Inf become the NaN byte 0x7F."""
+    if isinstance(x, torch.Tensor) and x.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"x: expected dtype torch.float32 or torch.bfloat16, got {x.dtype}")
+    _need(x, x.dtype if isinstance(x, torch.Tensor) else torch.float32, "x")
+    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    if x.numel():
+        _call("vpr_patch_quantize_fp8", _ptr(x), int(x.dtype == torch.bfloat16), x.numel(), _ptr(out), _stream())
+    return out
+
+
+def local_rerank_fp8(q_local: torch.Tensor, idx: torch.Tensor, g_local: torch.Tensor, index_base: int = 0,
+                     k: Optional[int] = None, min_sim: float = 0.0, ws: Optional[torch.Tensor] = None, debug: bool = False):
+    """local_rerank on e4m3 patch features (include/vpr_amd_patch_fp8.h): q_local uint8 [B, n_q, l] and g_local uint8
+    [n_local, n_g, l] as quantize_patch_fp8 writes them, l a multiple of 64; the similarity is 2^-16 times the dot product of
+    the byte values, everything else — arguments, outputs, debug=, ws — is local_rerank's."""
+    return _local_rerank_call("local_rerank_fp8", "vpr_patch_rerank_fp8", "vpr_patch_workspace_bytes_fp8", torch.uint8,
+                              _lib.PATCH_FP8_MIN_L, q_local, idx, g_local, index_base, k, min_sim, ws, debug)
 
 
 PROJECT_CHUNK_ROWS = 65536      # rows per vpr_project_rows call: bounds the workspace for million-row inputs

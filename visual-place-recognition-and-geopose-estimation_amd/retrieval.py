@@ -80,6 +80,14 @@ class HipEngine:
         (vpr_local_rerank): (vals, idx, matches) [B, k]."""
         return torch.ops.vpr.local_rerank(q_local_feats, idx, local_feats, index_base, k, min_sim)
 
+    def local_rerank_fp8(self, q_local_feats, idx, local_feats, index_base, k, min_sim=0.0):
+        """local_rerank on e4m3 patch features, both sides uint8 (vpr_patch_rerank_fp8): (vals, idx, matches) [B, k]."""
+        return torch.ops.vpr.local_rerank_fp8(q_local_feats, idx, local_feats, index_base, k, min_sim)
+
+    def quantize_patch_fp8(self, feats):
+        """Local features bf16 or f32 -> their e4m3 store, uint8 of the same shape (vpr_patch_quantize_fp8)."""
+        return torch.ops.vpr.patch_quantize_fp8(feats.contiguous())
+
 
 def pose_labels(labels, device) -> torch.Tensor:
     """The label table for torch.ops.vpr.retrieval_pose: a [N, 4] float64 tensor on `device` (gallery.device_labels /
@@ -156,7 +164,8 @@ class ShardedGallery:
         fine_rows ([n_local, D_fine] bf16 or f32, this shard's rows of the full-precision descriptors the local rows were made
         from): the second tier of search_reranked (include/vpr_amd_rerank.h); nothing else reads them.
         local_feats ([n_local, n, l] bf16, this shard's images' local features, SaladAggregator.local_features): what
-        search_local_reranked matches the queries' patches against (include/vpr_amd_local.h); nothing else reads them."""
+        search_local_reranked matches the queries' patches against (include/vpr_amd_local.h); nothing else reads them.  uint8:
+        their e4m3 store (include/vpr_amd_patch_fp8.h; half the bytes), matched by the e4m3 form of the same stage."""
         lo, hi = shard_bounds(n_total, rank, world)
         if local_rows.shape[0] != hi - lo:
             raise ValueError(f"rank {rank}: shard has {local_rows.shape[0]} rows, expected {hi - lo}")
@@ -175,8 +184,8 @@ class ShardedGallery:
             if local_feats.dim() != 3 or local_feats.shape[0] != hi - lo:
                 raise ValueError(f"rank {rank}: local_feats must be [{hi - lo}, n, l], one image per local row; "
                                  f"got {tuple(local_feats.shape)}")
-            if local_feats.dtype != torch.bfloat16:
-                raise ValueError(f"local_feats: bf16, got {local_feats.dtype}")
+            if local_feats.dtype not in (torch.bfloat16, torch.uint8):
+                raise ValueError(f"local_feats: bf16 or uint8 (e4m3 bytes), got {local_feats.dtype}")
         self.local_feats = local_feats
         self.fine_rows = fine_rows
         self.projection = projection
@@ -280,15 +289,18 @@ class ShardedGallery:
         ws, score_events: of the coarse search, as in `search`.
         Sharded meaning, as search_reranked: the answer is the k best by local score among the UNION of the shards' coarse
         top-kc — each shard re-ranks its own kc candidates, so up to world * kc images are considered, a superset of the
-        global coarse top-kc.  With one shard that is the coarse top-kc itself.  Values are local scores (always finite)."""
+        global coarse top-kc.  With one shard that is the coarse top-kc itself.  Values are local scores (always finite).
+        A gallery of e4m3 local features (uint8 `local_feats`) takes q_local_feats as bf16, quantised here, or as uint8."""
         if self.local_feats is None:
             raise ValueError("search_local_reranked: this gallery has no local_feats")
         if not 1 <= kc <= 64:
             raise ValueError(f"search_local_reranked: one coarse search yields at most 64 candidates; kc = {kc}")
         if not 1 <= k <= kc:
             raise ValueError(f"search_local_reranked: k must be in 1..kc (k = {k}, kc = {kc})")
-        if q_local_feats is None or q_local_feats.dim() != 3 or q_local_feats.dtype != torch.bfloat16:
-            raise ValueError("search_local_reranked: q_local_feats must be bf16 [B, n_q, l]")
+        fp8 = self.local_feats.dtype == torch.uint8
+        if q_local_feats is None or q_local_feats.dim() != 3 or q_local_feats.dtype not in ((torch.bfloat16, torch.uint8) if fp8
+                                                                                          else (torch.bfloat16,)):
+            raise ValueError(f"search_local_reranked: q_local_feats must be bf16 {'or uint8 ' if fp8 else ''}[B, n_q, l]")
         if q_local_feats.shape[2] != self.local_feats.shape[2]:
             raise ValueError(f"search_local_reranked: the queries' local features are {q_local_feats.shape[2]} wide, the "
                              f"gallery's {self.local_feats.shape[2]}")
@@ -297,8 +309,19 @@ class ShardedGallery:
         if max(q_local_feats.shape[1], self.local_feats.shape[1]) > 256:
             raise ValueError("search_local_reranked: at most 256 patches per image")
         _, i = self._local(self.project_queries(q_all), kc, ws, score_events)
-        v, i, _ = self.engine.local_rerank(q_local_feats.contiguous(), i.contiguous(), self.local_feats, self.index_base, k, min_sim)
+        if fp8:
+            v, i, _ = self.engine.local_rerank_fp8(self.local_query_feats(q_local_feats), i.contiguous(), self.local_feats,
+                                                   self.index_base, k, min_sim)
+        else:
+            v, i, _ = self.engine.local_rerank(q_local_feats.contiguous(), i.contiguous(), self.local_feats, self.index_base, k, min_sim)
         return self._merged(v, i)
+
+    def local_query_feats(self, q_local_feats: torch.Tensor) -> torch.Tensor:
+        """The queries' local features as this gallery's second stage reads them: bf16 ones become their e4m3 store when the
+        gallery holds one (one rounding from the value handed in); anything else comes back as it is, contiguous."""
+        if self.local_feats is not None and self.local_feats.dtype == torch.uint8 and q_local_feats.dtype != torch.uint8:
+            return self.engine.quantize_patch_fp8(q_local_feats)
+        return q_local_feats.contiguous()
 
     def expand(self, q_all: torch.Tensor, vals: torch.Tensor, idx: torch.Tensor, n_use: int, alpha: float = 3.0,
                q_weight: float = 1.0) -> torch.Tensor:
@@ -370,6 +393,7 @@ class ShardedGallery:
         rows: when a projection made the travelling rows d wide, the D_in-wide ones are gathered as well.
         local_rerank = kc: the local-feature form (search_local_reranked) with this rank's q_local_feats [B_local, n_q, l] bf16,
         gathered across the ranks like the queries when the gallery is collective; not together with rerank= or expand=.
+        With e4m3 local features in the gallery, bf16 ones are quantised before that gather (half the bytes travel).
         ws, ws2, score_events: handed to search_gathered."""
         if local_rerank is not None and rerank is not None:
             raise ValueError("search_local_queries: local_rerank and rerank are two kinds of second stage; name one of them")
@@ -380,7 +404,10 @@ class ShardedGallery:
         q_fine = None
         if rerank is not None:
             q_fine = q_all if q_proj is q_local else self.gather_queries(q_local)
-        feats_all = None if local_rerank is None else self.gather_queries(q_local_feats.contiguous())
+        feats_all = None
+        if local_rerank is not None:
+            bf16 = isinstance(q_local_feats, torch.Tensor) and q_local_feats.dtype == torch.bfloat16 and q_local_feats.dim() == 3
+            feats_all = self.gather_queries(self.local_query_feats(q_local_feats) if bf16 else q_local_feats.contiguous())
         v, i = self.search_gathered(q_all, k, expand, rerank, q_fine, ws, ws2, score_events, local_rerank, feats_all, min_sim)
         b = q_local.shape[0]
         return v[self.rank * b:(self.rank + 1) * b], i[self.rank * b:(self.rank + 1) * b]
@@ -417,7 +444,8 @@ class GraphedRetrieval:
     queries are `self.q`, vals are fine scores, and the poses come from the re-ranked rows.
     local_rerank (kc): the graph holds the local-feature form, ShardedGallery.search_local_reranked (not with `rerank` or
     `expand`): `self.q_feats` [B_local, n, l] bf16 (n, l: the gallery's) is a second static input,
-    filled by __call__(q_local, q_local_feats); vals are local scores."""
+    filled by __call__(q_local, q_local_feats); vals are local scores.  A gallery of e4m3 local features makes it uint8:
+    __call__ takes bf16 features, quantised into it before the replay, or uint8 ones."""
 
     def __init__(self, gallery: ShardedGallery, batch_local: int, k: int, labels=None, mode: str = "top1",
                  temperature: float = 0.01, scaler=None, expand=None, rerank: Optional[int] = None,
@@ -431,7 +459,8 @@ class GraphedRetrieval:
                 raise ValueError("GraphedRetrieval: local_rerank combines neither with rerank nor with expand")
             if gallery.local_feats is None:
                 raise ValueError("GraphedRetrieval: local_rerank needs a gallery with local_feats")
-            self.q_feats = torch.zeros((batch_local, *gallery.local_feats.shape[1:]), dtype=torch.bfloat16, device=gallery.rows.device)
+            self.q_feats = torch.zeros((batch_local, *gallery.local_feats.shape[1:]), dtype=gallery.local_feats.dtype,
+                                       device=gallery.rows.device)
         self.expand = expansion_params(expand)
         self.labels = None if labels is None else pose_labels(labels, gallery.rows.device)
         self.mode, self.temperature, self.scaler = mode, temperature, pose_scaler(scaler)
@@ -467,6 +496,6 @@ class GraphedRetrieval:
     def __call__(self, q_local: torch.Tensor, q_local_feats: Optional[torch.Tensor] = None):
         self.q.copy_(q_local)
         if self.q_feats is not None:
-            self.q_feats.copy_(q_local_feats)
+            self.q_feats.copy_(self.g.local_query_feats(q_local_feats))
         self._captured.graph.replay()
         return self.vals, self.idx

@@ -14,6 +14,7 @@ that seam, so the HIP hot path is visible to PyTorch's dispatcher like any other
     torch.ops.vpr.project_rows                         (PCA / whitening projection of descriptors + L2 re-normalisation)
     torch.ops.vpr.rerank_rows                          (two-tier retrieval: coarse candidates re-ranked on full-precision rows)
     torch.ops.vpr.local_rerank                         (local-feature re-ranking: mutual-nearest-neighbour patch matches)
+    torch.ops.vpr.patch_quantize_fp8 / local_rerank_fp8   (the same on e4m3 patch features: half the feature store)
     torch.ops.vpr.pose_head / ln_meanpool_head
     torch.ops.vpr.head_train_epoch                     (head-only fine-tuning pass; mutates parameters and AdamW moments)
     torch.ops.vpr.head_train_epoch_dropout             (the same pass with Dropout(p) after the ReLU, training mode)
@@ -283,10 +284,33 @@ def local_rerank(q_local: Tensor, idx: Tensor, g_local: Tensor, index_base: int 
 
 
 @local_rerank.register_fake
-def _(q_local, idx, g_local, index_base=0, k=None, min_sim=0.0):
+def _local_rerank_fake(q_local, idx, g_local, index_base=0, k=None, min_sim=0.0):
     B, k = idx.shape[0], idx.shape[1] if k is None else k
     new = lambda dtype: q_local.new_empty((B, k), dtype=dtype)
     return new(torch.float32), new(torch.int32), new(torch.int32)
+
+
+@torch.library.custom_op("vpr::patch_quantize_fp8", mutates_args=())
+def patch_quantize_fp8(x: Tensor) -> Tensor:
+    """Patch features f32 or bf16, any shape -> uint8 of that shape: the e4m3fn byte of x * 2^8, one round-to-nearest-even
+    from the f32 value.  vpr_patch_quantize_fp8."""
+    return ops.quantize_patch_fp8(x)
+
+
+@patch_quantize_fp8.register_fake
+def _(x):
+    return x.new_empty(x.shape, dtype=torch.uint8)
+
+
+@torch.library.custom_op("vpr::local_rerank_fp8", mutates_args=())
+def local_rerank_fp8(q_local: Tensor, idx: Tensor, g_local: Tensor, index_base: int = 0, k: Optional[int] = None,
+                     min_sim: float = 0.0) -> Tuple[Tensor, Tensor, Tensor]:
+    """local_rerank on e4m3 patch features: q_local uint8 [B, n_q, l], g_local uint8 [n_local, n_g, l] (patch_quantize_fp8
+    bytes, l a multiple of 64); outputs as local_rerank.  vpr_patch_rerank_fp8."""
+    return ops.local_rerank_fp8(q_local, idx, g_local, index_base, k, min_sim)
+
+
+local_rerank_fp8.register_fake(_local_rerank_fake)            # the output shapes of the bf16 form
 
 
 # ------------------------------------------------------------------------------------------------------------ heads
@@ -362,4 +386,4 @@ def _(X, Y, order, batch_size, W1, b1, W2, b2, m, v, first_step, lr, beta1, beta
 OPS = ("head_train_epoch", "head_train_epoch_dropout", "salad_aggregate", "salad_aggregate_split", "salad_aggregate_f32", "salad_aggregate_train", "knn_topk", "knn_topk_fp8", "quantize_fp8_rows",
        "topk_merge", "pose_head", "ln_meanpool_head", "retrieval_pose", "query_expand", "query_expand_finish", "project_rows",
        "rerank_rows", "salad_aggregate_n", "salad_aggregate_f32_n", "salad_aggregate_hires", "salad_aggregate_f32_hires",
-       "local_rerank")
+       "local_rerank", "patch_quantize_fp8", "local_rerank_fp8")
