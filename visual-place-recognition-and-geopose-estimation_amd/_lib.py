@@ -226,6 +226,19 @@ PATCH_FP8_PROTOTYPES = {
     "vpr_patch_rerank_fp8": LOCAL_PROTOTYPES["vpr_local_rerank"],           # the parameter list of the eighth table's call
 }
 
+# include/vpr_amd_local_hires.h, the eleventh table: both element types of the re-ranking for up to 1369 patches per image
+LOCAL_HIRES_MAX_N = 1369                                    # VPR_LOCAL_HIRES_MAX_N
+LOCAL_HIRES_PROTOTYPES = {
+    "vpr_hires_local_workspace_bytes": LOCAL_PROTOTYPES["vpr_local_workspace_bytes"],
+    "vpr_hires_local_rerank": LOCAL_PROTOTYPES["vpr_local_rerank"],         # the parameter list of the eighth table's call
+    "vpr_hires_patch_rerank_fp8": LOCAL_PROTOTYPES["vpr_local_rerank"],
+}
+
+
+def local_hires_sum_roundings(n_g: int) -> int:
+    """VPR_LOCAL_HIRES_SUM_ROUNDINGS: L_sum of the score summed in blocks of 256 columns."""
+    return LOCAL_SUM_ROUNDINGS + (n_g + 255) // 256
+
 
 def rerank_roundings(D: int, rows_are_f32: bool) -> int:
     """VPR_RERANK_ROUNDINGS: L of the fine score, the roundings on the longest path from a product to the result."""
@@ -253,7 +266,7 @@ def lib() -> ctypes.CDLL:
                                           + list(RERANK_PROTOTYPES.items()) + list(SALAD_STAGES_PROTOTYPES.items())
                                           + list(SALAD_ANYRES_PROTOTYPES.items()) + list(SALAD_HIRES_PROTOTYPES.items())
                                           + list(LOCAL_PROTOTYPES.items()) + list(SALAD_F32_STAGES_PROTOTYPES.items())
-                                          + list(PATCH_FP8_PROTOTYPES.items())):
+                                          + list(PATCH_FP8_PROTOTYPES.items()) + list(LOCAL_HIRES_PROTOTYPES.items())):
             fn = getattr(handle, name)   # AttributeError if a declared symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

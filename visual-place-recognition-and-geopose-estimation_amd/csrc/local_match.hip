@@ -15,38 +15,17 @@
 //     xor 32, the 8 waves through LDS in ascending wave (= row) order.
 // Thread j < n_g then decides column j's match and the score is summed in the order the header states.
 // order: one 128-thread workgroup per query: order_rank of vpr_common.h, the order stage of vpr_rerank_rows.
+// lm_better, the swizzle lm_off, the workspace rule and the argument checks are in local_match.h, shared with the kernel for
+// more than 256 patches (local_match_hires.hip), which also launches this file's order stage.
 #include <float.h>
 #include <math.h>
-#include "vpr_common.h"
-#include "vpr_internal.h"
-#include "../../include/vpr_amd_local.h"
-#include "../../include/vpr_amd_patch_fp8.h"
+#include "local_match.h"
 
 namespace vpr {
 
-constexpr int LM_WAVES = 8;                         // = VPR_LOCAL_MAX_N / 32 row tiles
-constexpr int LM_THREADS = LM_WAVES * WAVE;
 constexpr int LM_GROUP = 4;                         // candidates per workgroup
 constexpr int LM_MAX_N = VPR_LOCAL_MAX_N;
 static_assert(LM_WAVES * 32 == LM_MAX_N && VPR_LOCAL_MAX_KC == ORDER_MAX_KC, "one wave per 32-row tile; order_rank's workgroup");
-
-// a beats b: a exists and (b does not, or a's value is larger, or equal with the lower index)
-__device__ __forceinline__ bool lm_better(float av, int ai, float bv, int bi) {
-  return ai >= 0 && (bi < 0 || av > bv || (av == bv && ai < bi));
-}
-
-// Swizzle of the staged features: chunk c of row r (a row is CPR chunks of 16 B: L / 8 for bf16, L / 16 for e4m3) sits at
-// chunk c ^ f(r) of its row, f(r) = (r >> SH) & MASK with (SH, MASK) = (0, 15) if 16 | CPR, (1, 7) if 8 | CPR, else (2, 3): the
-// 16 rows of a ds_read_b128 lane group at one logical chunk fall into 16 distinct 16-byte slots of the 256-byte bank row.  CPR
-// is a multiple of 4, and f(r) stays below the largest power of two (<= 16) dividing CPR: the XOR stays inside the row, and
-// chunks 2 m and 2 m + 1 (the two reads of an e4m3 operand) stay a pair.  Restated and checked exhaustively on the host for
-// every supported width of both elements (tests/test_local_match_fp8_cpu.py).
-template <int CPR>
-__device__ __forceinline__ int lm_off(int row, int chunk) {
-  static_assert(CPR % 4 == 0 && CPR <= 32, "a row is a whole number of 64-byte groups");
-  constexpr int SH = CPR % 16 == 0 ? 0 : CPR % 8 == 0 ? 1 : 2, MASK = CPR % 16 == 0 ? 15 : CPR % 8 == 0 ? 7 : 3;
-  return (row * CPR + (chunk ^ ((row >> SH) & MASK))) << 4;
-}
 
 // LDS of one workgroup: features [ngp][L] elements of es bytes | column best value [8][ngp] f32 | column best row [8][ngp] i32 |
 // row_nn [256] i32 | wave sums [4] f32 + wave counts [4] i32, ngp = n_g rounded up to 32
@@ -258,10 +237,10 @@ int launch_local_match(dim3 grid, size_t lds, hipStream_t s, const Elem* q_local
                        index_base, min_sim, ws_score, ws_matches, pair_score, pair_matches, row_nn, col_nn);
 }
 
-inline size_t lm_ws_half(int B, int kc) { return align_up((size_t)(B > 0 ? B : 1) * kc * sizeof(float), 256); }
-inline size_t lm_ws_bytes(int B, int kc) {
-  if (B < 0 || kc < 1 || kc > VPR_LOCAL_MAX_KC) return 0;
-  return 2 * lm_ws_half(B, kc);                                       // f32 scores | i32 match counts
+int launch_local_order(const float* scores, const int32_t* matches, const int32_t* idx, int B, int kc, int n_local, int index_base,
+                       int k_out, float* vals_out, int32_t* idx_out, int32_t* matches_out, hipStream_t stream) {
+  return launch_kernel(local_order_kernel, dim3((unsigned)B), dim3(ORDER_MAX_KC), 0, stream, scores, matches, idx, kc, n_local,
+                       index_base, k_out, vals_out, idx_out, matches_out);
 }
 
 // The checks and the two launches of both element types; l_step = the width's granule (32 bf16, 64 e4m3).
@@ -272,16 +251,8 @@ int local_rerank_run(const Elem* q_local, int n_q, const int32_t* idx, int B, in
                      size_t workspace_bytes, void* stream) {
   constexpr bool FP8 = sizeof(Elem) == 1;
   constexpr int l_step = FP8 ? VPR_PATCH_FP8_MIN_L : 32;
-  if (!q_local || !idx || !g_local || !vals_out || !idx_out || !workspace) return VPR_ERR_INVALID_ARG;
-  if (B < 0 || n_q < 0 || n_g < 0 || l < 0 || kc < 0 || n_local < 0 || index_base < 0) return VPR_ERR_INVALID_ARG;
-  if (k_out < 1 || k_out > kc) return VPR_ERR_INVALID_ARG;
-  if (isnan(min_sim)) return VPR_ERR_INVALID_ARG;
-  if (kc > VPR_LOCAL_MAX_KC || n_q == 0 || n_q > LM_MAX_N || n_g == 0 || n_g > LM_MAX_N) return VPR_ERR_UNSUPPORTED;
-  if (l == 0 || l % l_step != 0 || l > VPR_LOCAL_MAX_L) return VPR_ERR_UNSUPPORTED;
-  if (!aligned16(q_local) || !aligned16(g_local) || !aligned16(workspace)) return VPR_ERR_UNSUPPORTED;   // read as 16-byte chunks
-  if (!aligned4(idx) || !aligned4(vals_out) || !aligned4(idx_out) || !aligned4(matches_out) || !aligned4(pair_score) ||
-      !aligned4(pair_matches) || !aligned4(row_nn) || !aligned4(col_nn)) return VPR_ERR_UNSUPPORTED;
-  if (workspace_bytes < lm_ws_bytes(B, kc)) return VPR_ERR_UNSUPPORTED;
+  VPR_TRY_LAUNCH(lm_check(q_local, n_q, idx, B, kc, g_local, n_g, l, l_step, LM_MAX_N, n_local, index_base, min_sim, k_out, vals_out,
+                          idx_out, matches_out, pair_score, pair_matches, row_nn, col_nn, workspace, workspace_bytes));
   if (B == 0) return VPR_OK;
   float* ws_score = static_cast<float*>(workspace);
   int32_t* ws_matches = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + lm_ws_half(B, kc));
@@ -302,9 +273,7 @@ int local_rerank_run(const Elem* q_local, int n_q, const int32_t* idx, int B, in
     }
   }
 #undef LM_CASE
-  VPR_TRY_LAUNCH(launch_kernel(local_order_kernel, dim3((unsigned)B), dim3(ORDER_MAX_KC), 0, s,
-                               static_cast<const float*>(ws_score), static_cast<const int32_t*>(ws_matches), idx, kc, n_local,
-                               index_base, k_out, vals_out, idx_out, matches_out));
+  VPR_TRY_LAUNCH(launch_local_order(ws_score, ws_matches, idx, B, kc, n_local, index_base, k_out, vals_out, idx_out, matches_out, s));
   return VPR_OK;
 }
 

@@ -316,7 +316,8 @@ def _check_grid(extractor, image_size: int) -> None:
 @torch.no_grad()
 def build_gallery_from_images(extractor: DinoV2Salad, csv_path: str, image_dir: str, out_dir: str, *, fp8: bool = False,
                               batch_size: int = 64, device: str = "cuda", image_size: int = 224, graph: bool = True,
-                              projection=None, whiten: bool = True, keep_fine: bool = False, keep_local=False) -> int:
+                              projection=None, whiten: bool = True, keep_fine: bool = False, keep_local=False,
+                              local_hires: bool = False) -> int:
     """labels CSV (`filename,timestamp,latitude,longitude,angle,Region_ID`, cleaned_dataset_files/labels_train.csv:1) +
     images -> on-disk gallery (gallery.save_gallery: bf16 rows, or e4m3 rows + per-row scales with fp8=True).
     Preprocessing = the DINOv2+SALAD validation transform (dinov2salad_validation.py:18-22).  Returns the row count.
@@ -329,7 +330,10 @@ def build_gallery_from_images(extractor: DinoV2Salad, csv_path: str, image_dir: 
     keep_local: the gallery also keeps every image's local features (local_features.npy: [N, n, 128] bf16 from the same
     backbone pass, DinoV2Salad.features(want_local=True); at most 256 patch tokens), what
     calculate_retrieval_scores(local_rerank=) matches against.  keep_local="fp8": their e4m3 store instead
-    (local_features_fp8.npy: [N, n, 128] uint8, features(want_local="fp8"); half the bytes — 32 KB per image at n = 256)."""
+    (local_features_fp8.npy: [N, n, 128] uint8, features(want_local="fp8"); half the bytes — 32 KB per image at n = 256).
+    local_hires (with keep_local): an extractor of 257 to 1369 patch tokens is accepted (features(hires=True); img_size 322 to
+    518).  The files keep their format, only n differs: 135 KB bf16 or 68 KB e4m3 per image at 322 px (n = 529), 350 KB or
+    175 KB at 518 px (n = 1369)."""
     from . import gallery as G, ops
     if keep_local not in (False, True, "fp8"):
         raise ValueError(f"build_gallery_from_images: keep_local must be False, True or 'fp8', got {keep_local!r}")
@@ -342,7 +346,7 @@ def build_gallery_from_images(extractor: DinoV2Salad, csv_path: str, image_dir: 
     desc = torch.empty((len(names), 8448), dtype=torch.float32, device=dev)
     local = None
     if keep_local:
-        features = lambda x: extractor.features(x, want_local=keep_local)
+        features = lambda x: extractor.features(x, want_local=keep_local, hires=local_hires)
         local = torch.empty((len(names), extractor.backbone.num_patches, extractor.aggregator.cluster_dim),
                             dtype=torch.uint8 if keep_local == "fp8" else torch.bfloat16, device=dev)
         fwd = GraphedForward(features, module=extractor) if graph and dev.type == "cuda" else features
@@ -410,7 +414,7 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
                                tau: float = 25.0, mode: str = "top1", batch_size: int = 64, device: str = "cuda", graph: bool = True,
                                image_size: int = 224, rank: int = 0, world: int = 1, group=None, verbose: bool = True,
                                on_device: bool = False, query_expansion=None, rerank: Optional[int] = None,
-                               local_rerank: Optional[int] = None, min_sim: float = 0.0) -> dict:
+                               local_rerank: Optional[int] = None, min_sim: float = 0.0, local_hires: bool = False) -> dict:
     """Validation split through descriptor -> sharded cosine top-k -> label transfer:
       pose      (lat, lon, angle) of the best match, or the softmax-weighted mean of the k matches (gallery.label_transfer);
       final_loss on lat/lon with the validation scripts' formula (dinov2salad_validation.py:101), MAAE on the angle
@@ -431,7 +435,10 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
     nearest-neighbour matches (similarity >= min_sim) between the query's and the candidates' patch features
     (local_features.npy, build_gallery_from_images(keep_local=True); ShardedGallery.search_local_reranked); topk_scores are
     then local scores.  Not together with rerank or query_expansion.  A gallery that keeps the e4m3 store instead
-    (local_features_fp8.npy, keep_local="fp8") is matched in that form: the queries' features are features(want_local="fp8")."""
+    (local_features_fp8.npy, keep_local="fp8") is matched in that form: the queries' features are features(want_local="fp8").
+    local_hires (with local_rerank): the gallery's and the queries' images hold up to 1369 patch tokens (a gallery built with
+    build_gallery_from_images(local_hires=True); features(hires=True) and ShardedGallery(local_hires=True)); per image the
+    gallery then keeps 135 KB bf16 or 68 KB e4m3 at 322 px, 350 KB or 175 KB at 518 px."""
     from . import gallery as G
     from .retrieval import ShardedGallery
     _check_grid(extractor, image_size)
@@ -452,7 +459,8 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
         fine = shard.rows
     # offline evaluation: unconditionally exact neighbours (queries the device certificate flags are re-run on f64 scores)
     sg = ShardedGallery(shard.rows, shard.n_total, rank, world, group=group, scales=shard.scales, exact_fallback=True,
-                        projection=shard.projection, fine_rows=fine, local_feats=shard.local)
+                        projection=shard.projection, fine_rows=fine, local_feats=shard.local,
+                        local_hires=local_hires)
     df = _existing_rows(val_csv_path, image_dir)
     names = df["filename"].tolist()
     prep = ResizeNormalize(image_size, "bilinear", HALF_MEAN, HALF_STD, torch.bfloat16)
@@ -460,7 +468,7 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
     vals = torch.empty((len(names), kk), dtype=torch.float32, device=dev)
     idx = torch.empty((len(names), kk), dtype=torch.int32, device=dev)
     want_local = local_rerank is not None and ("fp8" if shard.local.dtype == torch.uint8 else True)
-    features = lambda x: extractor.features(x, want_bf16=True, want_local=want_local)
+    features = lambda x: extractor.features(x, want_bf16=True, want_local=want_local, hires=local_hires)
     fwd = GraphedForward(features, module=extractor) if graph and dev.type == "cuda" else features
     two_tier = {} if rerank is None else {"rerank": int(rerank)}     # named only when asked for
     for idxs, u8 in _batches(image_dir, names, batch_size, dev):

@@ -133,7 +133,7 @@ class SaladAggregator(nn.Module):
         return (desc, desc16) if want_bf16 else desc
 
     @torch.no_grad()
-    def local_features(self, tokens: torch.Tensor, fp8: bool = False) -> torch.Tensor:
+    def local_features(self, tokens: torch.Tensor, fp8: bool = False, hires: bool = False) -> torch.Tensor:
         """Per-patch local descriptors for local-feature re-ranking (include/vpr_amd_local.h): patch tokens [B, n, C] (no cls
         row; bf16 or f32) -> [B, n, cluster_dim] bf16, the cluster_features MLP of every patch in eval arithmetic (its Dropout
         is never applied), L2-normalised per patch in f32; an all-zero output row stays zero.  bf16 tokens on the GPU run the
@@ -141,12 +141,17 @@ class SaladAggregator(nn.Module):
         with the f32 weights.  n > 256 (322 px and up) raises before any launch: the matching kernel holds one image's
         patches in a single tile set.
         fp8=True: [B, n, cluster_dim] uint8 instead, the e4m3 store of include/vpr_amd_patch_fp8.h (ops.quantize_patch_fp8),
-        quantised from the f32 normalised value in one rounding, not through bf16; on the GPU only."""
+        quantised from the f32 normalised value in one rounding, not through bf16; on the GPU only.
+        hires=True: the limit is 1369 patches (518 px), the range of include/vpr_amd_local_hires.h; the features are the same
+        code per patch, so at n <= 256 the result is the default call's bit for bit."""
         if tokens.dim() != 3 or tokens.shape[2] != self.num_channels:
             raise ValueError(f"SaladAggregator.local_features: tokens must be [B, n, {self.num_channels}] patch tokens, "
                              f"got {tuple(tokens.shape)}")
         B, n, C = tokens.shape
-        if n > _lib.LOCAL_MAX_N:
+        if hires and n > _lib.LOCAL_HIRES_MAX_N:
+            raise ValueError(f"SaladAggregator.local_features(hires=True): {n} patch tokens per image, but local-feature "
+                             f"re-ranking takes at most {_lib.LOCAL_HIRES_MAX_N} (518 px images at patch 14)")
+        if not hires and n > _lib.LOCAL_MAX_N:
             raise ValueError(f"SaladAggregator.local_features: {n} patch tokens per image, but local-feature re-ranking takes at "
                              f"most {_lib.LOCAL_MAX_N} (224 px images at patch 14)")
         x = tokens.reshape(B * n, C)
@@ -212,7 +217,8 @@ class DinoV2Salad(nn.Module):
         return t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16)
 
     @torch.no_grad()
-    def features(self, x: torch.Tensor, want_bf16: bool = False, events: Optional[list] = None, want_local=False):
+    def features(self, x: torch.Tensor, want_bf16: bool = False, events: Optional[list] = None, want_local=False,
+                 hires: bool = False):
         """images -> descriptor (and its bf16 copy): backbone tokens stay in the layout the backbone
         computed them in (SplitTokens on the HIP path), no re-layout copy before SALAD.
         events: a list -> a (start, end) pair of timing events around the aggregation on the current stream is appended
@@ -220,16 +226,21 @@ class DinoV2Salad(nn.Module):
         want_local: the result gains a last element, the local features [B, n, 128] bf16 of the same backbone pass
         (SaladAggregator.local_features; at most 256 patch tokens, ValueError before the backbone runs otherwise).  The
         descriptor is the default call's, bit for bit.  want_local="fp8": that element is their e4m3 store instead, uint8
-        [B, n, 128] (local_features(fp8=True)); True keeps the bf16 result bit for bit."""
+        [B, n, 128] (local_features(fp8=True)); True keeps the bf16 result bit for bit.
+        hires=True (with want_local): up to 1369 patch tokens (img_size 322, 448, 518), the features that
+        ops.local_rerank_hires / local_rerank_fp8_hires and ShardedGallery(local_hires=True) take."""
         if want_local not in (False, True, "fp8"):
             raise ValueError(f"DinoV2Salad.features: want_local must be False, True or 'fp8', got {want_local!r}")
         if want_local:
-            if self.backbone.num_patches > _lib.LOCAL_MAX_N:
+            if hires and self.backbone.num_patches > _lib.LOCAL_HIRES_MAX_N:
+                raise ValueError(f"DinoV2Salad.features(want_local=True, hires=True): {self.backbone.num_patches} patch tokens per "
+                                 f"image, but local-feature re-ranking takes at most {_lib.LOCAL_HIRES_MAX_N} (518 px images at patch 14)")
+            if not hires and self.backbone.num_patches > _lib.LOCAL_MAX_N:
                 raise ValueError(f"DinoV2Salad.features(want_local=True): {self.backbone.num_patches} patch tokens per image, but "
                                  f"local-feature re-ranking takes at most {_lib.LOCAL_MAX_N} (224 px images at patch 14)")
             keep: list = []
             out = self._features(x, want_bf16, events, keep)
-            local = self.aggregator.local_features(keep[0], fp8=want_local == "fp8")
+            local = self.aggregator.local_features(keep[0], fp8=want_local == "fp8", hires=hires)
             return (*out, local) if want_bf16 else (out, local)
         return self._features(x, want_bf16, events)
 

@@ -953,8 +953,9 @@ def rerank_rows(q: torch.Tensor, idx: torch.Tensor, rows: torch.Tensor, index_ba
     return vals, out
 
 
-def _local_check(what: str, q_local, idx, g_local, k, dtype=torch.bfloat16, l_step: int = 32) -> int:
-    """The argument checks of both element types: bf16 features of a width that is a multiple of 32, e4m3 bytes of 64."""
+def _local_check(what: str, q_local, idx, g_local, k, dtype=torch.bfloat16, l_step: int = 32, max_n: int = _lib.LOCAL_MAX_N) -> int:
+    """The argument checks of both element types: bf16 features of a width that is a multiple of 32, e4m3 bytes of 64; max_n
+    = the patch limit of the form (256, or 1369 for the _hires calls)."""
     for t, name in ((q_local, "q_local"), (g_local, "g_local")):
         _need(t, dtype, name, 3)
     _need(idx, torch.int32, "idx", 2)
@@ -965,8 +966,8 @@ def _local_check(what: str, q_local, idx, g_local, k, dtype=torch.bfloat16, l_st
     if idx.device != q_local.device or g_local.device != q_local.device:
         raise RuntimeError(f"{what}: q_local, idx and g_local must live on one device")
     for t, name in ((q_local, "q_local"), (g_local, "g_local")):
-        if not 1 <= t.shape[1] <= _lib.LOCAL_MAX_N:
-            raise RuntimeError(f"{what}: {name} must hold 1..{_lib.LOCAL_MAX_N} patches per image, got {t.shape[1]}")
+        if not 1 <= t.shape[1] <= max_n:
+            raise RuntimeError(f"{what}: {name} must hold 1..{max_n} patches per image, got {t.shape[1]}")
     l = q_local.shape[2]
     if l % l_step or not l_step <= l <= _lib.LOCAL_MAX_L:
         raise RuntimeError(f"{what}: the feature width must be a multiple of {l_step} in {l_step}..{_lib.LOCAL_MAX_L}, got {l}")
@@ -989,9 +990,9 @@ class LocalRerankDebug(NamedTuple):
 
 
 def _local_rerank_call(what: str, entry: str, ws_entry: str, dtype, l_step: int, q_local, idx, g_local, index_base, k, min_sim,
-                       ws, debug):
-    """local_rerank / local_rerank_fp8: the checks, the workspace, the outputs and the one library call."""
-    k = _local_check(what, q_local, idx, g_local, k, dtype, l_step)
+                       ws, debug, max_n: int = _lib.LOCAL_MAX_N):
+    """local_rerank / local_rerank_fp8 and their _hires forms: the checks, the workspace, the outputs and the one library call."""
+    k = _local_check(what, q_local, idx, g_local, k, dtype, l_step, max_n)
     min_sim = float(min_sim)
     if min_sim != min_sim:
         raise RuntimeError(f"{what}: min_sim must be a number")
@@ -1050,6 +1051,23 @@ def local_rerank_fp8(q_local: torch.Tensor, idx: torch.Tensor, g_local: torch.Te
     the byte values, everything else — arguments, outputs, debug=, ws — is local_rerank's."""
     return _local_rerank_call("local_rerank_fp8", "vpr_patch_rerank_fp8", "vpr_patch_workspace_bytes_fp8", torch.uint8,
                               _lib.PATCH_FP8_MIN_L, q_local, idx, g_local, index_base, k, min_sim, ws, debug)
+
+
+def local_rerank_hires(q_local: torch.Tensor, idx: torch.Tensor, g_local: torch.Tensor, index_base: int = 0,
+                       k: Optional[int] = None, min_sim: float = 0.0, ws: Optional[torch.Tensor] = None, debug: bool = False):
+    """local_rerank for 1..1369 patches on either side (include/vpr_amd_local_hires.h; 322 to 518 px images): arguments,
+    outputs, debug= and ws= are local_rerank's.  The score of more than 256 candidate patches is summed in blocks of 256
+    columns; at 256 patches and below every output equals local_rerank's bit for bit."""
+    return _local_rerank_call("local_rerank_hires", "vpr_hires_local_rerank", "vpr_hires_local_workspace_bytes", torch.bfloat16, 32,
+                              q_local, idx, g_local, index_base, k, min_sim, ws, debug, _lib.LOCAL_HIRES_MAX_N)
+
+
+def local_rerank_fp8_hires(q_local: torch.Tensor, idx: torch.Tensor, g_local: torch.Tensor, index_base: int = 0,
+                           k: Optional[int] = None, min_sim: float = 0.0, ws: Optional[torch.Tensor] = None, debug: bool = False):
+    """local_rerank_fp8 for 1..1369 patches on either side (include/vpr_amd_local_hires.h): everything else is
+    local_rerank_fp8's; at 256 patches and below every output equals it bit for bit."""
+    return _local_rerank_call("local_rerank_fp8_hires", "vpr_hires_patch_rerank_fp8", "vpr_hires_local_workspace_bytes", torch.uint8,
+                              _lib.PATCH_FP8_MIN_L, q_local, idx, g_local, index_base, k, min_sim, ws, debug, _lib.LOCAL_HIRES_MAX_N)
 
 
 PROJECT_CHUNK_ROWS = 65536      # rows per vpr_project_rows call: bounds the workspace for million-row inputs

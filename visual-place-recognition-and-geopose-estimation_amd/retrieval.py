@@ -17,7 +17,7 @@ from typing import Optional, Tuple
 import torch
 import torch.distributed as dist
 
-from . import _streams, ops
+from . import _lib, _streams, ops
 from . import torch_ops  # noqa: F401  registers torch.ops.vpr.*
 
 
@@ -84,6 +84,14 @@ class HipEngine:
         """local_rerank on e4m3 patch features, both sides uint8 (vpr_patch_rerank_fp8): (vals, idx, matches) [B, k]."""
         return torch.ops.vpr.local_rerank_fp8(q_local_feats, idx, local_feats, index_base, k, min_sim)
 
+    def local_rerank_hires(self, q_local_feats, idx, local_feats, index_base, k, min_sim=0.0):
+        """local_rerank for up to 1369 patches on either side (vpr_hires_local_rerank): (vals, idx, matches) [B, k]."""
+        return torch.ops.vpr.local_rerank_hires(q_local_feats, idx, local_feats, index_base, k, min_sim)
+
+    def local_rerank_fp8_hires(self, q_local_feats, idx, local_feats, index_base, k, min_sim=0.0):
+        """local_rerank_fp8 for up to 1369 patches on either side (vpr_hires_patch_rerank_fp8): (vals, idx, matches) [B, k]."""
+        return torch.ops.vpr.local_rerank_fp8_hires(q_local_feats, idx, local_feats, index_base, k, min_sim)
+
     def quantize_patch_fp8(self, feats):
         """Local features bf16 or f32 -> their e4m3 store, uint8 of the same shape (vpr_patch_quantize_fp8)."""
         return torch.ops.vpr.patch_quantize_fp8(feats.contiguous())
@@ -148,7 +156,8 @@ class ShardedGallery:
     def __init__(self, local_rows: torch.Tensor, n_total: int, rank: int = 0, world: int = 1,
                  engine=None, group: Optional[dist.ProcessGroup] = None, scales: Optional[torch.Tensor] = None,
                  norm_bound: Optional[float] = None, force_collectives: bool = False, exact_fallback: bool = False,
-                 projection=None, fine_rows: Optional[torch.Tensor] = None, local_feats: Optional[torch.Tensor] = None):
+                 projection=None, fine_rows: Optional[torch.Tensor] = None, local_feats: Optional[torch.Tensor] = None,
+                 local_hires: bool = False):
         """local_rows: [n_local, D] bf16, or uint8 e4m3 bytes with per-row f32 `scales` (value = scale * fp8).
         norm_bound: upper bound of the (dequantised) row norms for the exactness certificate; None = L2-normalised
         descriptors (what SALAD emits); `measure_norm_bound()` computes it from the rows.
@@ -165,7 +174,9 @@ class ShardedGallery:
         from): the second tier of search_reranked (include/vpr_amd_rerank.h); nothing else reads them.
         local_feats ([n_local, n, l] bf16, this shard's images' local features, SaladAggregator.local_features): what
         search_local_reranked matches the queries' patches against (include/vpr_amd_local.h); nothing else reads them.  uint8:
-        their e4m3 store (include/vpr_amd_patch_fp8.h; half the bytes), matched by the e4m3 form of the same stage."""
+        their e4m3 store (include/vpr_amd_patch_fp8.h; half the bytes), matched by the e4m3 form of the same stage.
+        local_hires: search_local_reranked (and what runs it: search_gathered, search_local_queries, GraphedRetrieval) takes up
+        to 1369 patches per image on either side instead of 256 (include/vpr_amd_local_hires.h; 322 to 518 px images)."""
         lo, hi = shard_bounds(n_total, rank, world)
         if local_rows.shape[0] != hi - lo:
             raise ValueError(f"rank {rank}: shard has {local_rows.shape[0]} rows, expected {hi - lo}")
@@ -187,6 +198,7 @@ class ShardedGallery:
             if local_feats.dtype not in (torch.bfloat16, torch.uint8):
                 raise ValueError(f"local_feats: bf16 or uint8 (e4m3 bytes), got {local_feats.dtype}")
         self.local_feats = local_feats
+        self.local_hires = bool(local_hires)
         self.fine_rows = fine_rows
         self.projection = projection
         self.scales = scales
@@ -290,7 +302,9 @@ class ShardedGallery:
         Sharded meaning, as search_reranked: the answer is the k best by local score among the UNION of the shards' coarse
         top-kc — each shard re-ranks its own kc candidates, so up to world * kc images are considered, a superset of the
         global coarse top-kc.  With one shard that is the coarse top-kc itself.  Values are local scores (always finite).
-        A gallery of e4m3 local features (uint8 `local_feats`) takes q_local_feats as bf16, quantised here, or as uint8."""
+        A gallery of e4m3 local features (uint8 `local_feats`) takes q_local_feats as bf16, quantised here, or as uint8.
+        A gallery made with local_hires=True takes up to 1369 patches on either side; when either side exceeds 256 the match
+        runs on the engine's local_rerank_hires / local_rerank_fp8_hires, otherwise on the 256-patch entries as always."""
         if self.local_feats is None:
             raise ValueError("search_local_reranked: this gallery has no local_feats")
         if not 1 <= kc <= 64:
@@ -306,14 +320,19 @@ class ShardedGallery:
                              f"gallery's {self.local_feats.shape[2]}")
         if q_local_feats.shape[0] != q_all.shape[0]:
             raise ValueError("search_local_reranked: q_all and q_local_feats disagree on B")
-        if max(q_local_feats.shape[1], self.local_feats.shape[1]) > 256:
+        n_max = max(q_local_feats.shape[1], self.local_feats.shape[1])
+        if self.local_hires and n_max > _lib.LOCAL_HIRES_MAX_N:
+            raise ValueError(f"search_local_reranked: at most {_lib.LOCAL_HIRES_MAX_N} patches per image")
+        if not self.local_hires and n_max > 256:
             raise ValueError("search_local_reranked: at most 256 patches per image")
+        hires = n_max > _lib.LOCAL_MAX_N
         _, i = self._local(self.project_queries(q_all), kc, ws, score_events)
         if fp8:
-            v, i, _ = self.engine.local_rerank_fp8(self.local_query_feats(q_local_feats), i.contiguous(), self.local_feats,
-                                                   self.index_base, k, min_sim)
+            entry = self.engine.local_rerank_fp8_hires if hires else self.engine.local_rerank_fp8
+            v, i, _ = entry(self.local_query_feats(q_local_feats), i.contiguous(), self.local_feats, self.index_base, k, min_sim)
         else:
-            v, i, _ = self.engine.local_rerank(q_local_feats.contiguous(), i.contiguous(), self.local_feats, self.index_base, k, min_sim)
+            entry = self.engine.local_rerank_hires if hires else self.engine.local_rerank
+            v, i, _ = entry(q_local_feats.contiguous(), i.contiguous(), self.local_feats, self.index_base, k, min_sim)
         return self._merged(v, i)
 
     def local_query_feats(self, q_local_feats: torch.Tensor) -> torch.Tensor:

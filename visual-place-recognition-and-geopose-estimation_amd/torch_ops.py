@@ -15,6 +15,7 @@ that seam, so the HIP hot path is visible to PyTorch's dispatcher like any other
     torch.ops.vpr.rerank_rows                          (two-tier retrieval: coarse candidates re-ranked on full-precision rows)
     torch.ops.vpr.local_rerank                         (local-feature re-ranking: mutual-nearest-neighbour patch matches)
     torch.ops.vpr.patch_quantize_fp8 / local_rerank_fp8   (the same on e4m3 patch features: half the feature store)
+    torch.ops.vpr.local_rerank_hires / local_rerank_fp8_hires   (both for up to 1369 patches per image: 322 to 518 px)
     torch.ops.vpr.pose_head / ln_meanpool_head
     torch.ops.vpr.head_train_epoch                     (head-only fine-tuning pass; mutates parameters and AdamW moments)
     torch.ops.vpr.head_train_epoch_dropout             (the same pass with Dropout(p) after the ReLU, training mode)
@@ -313,6 +314,25 @@ def local_rerank_fp8(q_local: Tensor, idx: Tensor, g_local: Tensor, index_base: 
 local_rerank_fp8.register_fake(_local_rerank_fake)            # the output shapes of the bf16 form
 
 
+@torch.library.custom_op("vpr::local_rerank_hires", mutates_args=())
+def local_rerank_hires(q_local: Tensor, idx: Tensor, g_local: Tensor, index_base: int = 0, k: Optional[int] = None,
+                       min_sim: float = 0.0) -> Tuple[Tensor, Tensor, Tensor]:
+    """local_rerank for 1..1369 patches on either side (322 to 518 px images); outputs as local_rerank, equal to it bit for
+    bit at 256 patches and below.  vpr_hires_local_rerank."""
+    return ops.local_rerank_hires(q_local, idx, g_local, index_base, k, min_sim)
+
+
+@torch.library.custom_op("vpr::local_rerank_fp8_hires", mutates_args=())
+def local_rerank_fp8_hires(q_local: Tensor, idx: Tensor, g_local: Tensor, index_base: int = 0, k: Optional[int] = None,
+                           min_sim: float = 0.0) -> Tuple[Tensor, Tensor, Tensor]:
+    """local_rerank_fp8 for 1..1369 patches on either side; outputs as local_rerank.  vpr_hires_patch_rerank_fp8."""
+    return ops.local_rerank_fp8_hires(q_local, idx, g_local, index_base, k, min_sim)
+
+
+local_rerank_hires.register_fake(_local_rerank_fake)          # the output shapes do not depend on the patch counts
+local_rerank_fp8_hires.register_fake(_local_rerank_fake)
+
+
 # ------------------------------------------------------------------------------------------------------------ heads
 @torch.library.custom_op("vpr::pose_head", mutates_args=())
 def pose_head(x: Tensor, W1: Optional[Tensor], b1: Optional[Tensor], W2: Tensor, b2: Tensor, sincos_offset: int) -> Tensor:
@@ -386,4 +406,4 @@ def _(X, Y, order, batch_size, W1, b1, W2, b2, m, v, first_step, lr, beta1, beta
 OPS = ("head_train_epoch", "head_train_epoch_dropout", "salad_aggregate", "salad_aggregate_split", "salad_aggregate_f32", "salad_aggregate_train", "knn_topk", "knn_topk_fp8", "quantize_fp8_rows",
        "topk_merge", "pose_head", "ln_meanpool_head", "retrieval_pose", "query_expand", "query_expand_finish", "project_rows",
        "rerank_rows", "salad_aggregate_n", "salad_aggregate_f32_n", "salad_aggregate_hires", "salad_aggregate_f32_hires",
-       "local_rerank", "patch_quantize_fp8", "local_rerank_fp8")
+       "local_rerank", "patch_quantize_fp8", "local_rerank_fp8", "local_rerank_hires", "local_rerank_fp8_hires")
