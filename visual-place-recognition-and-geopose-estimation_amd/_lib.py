@@ -234,6 +234,18 @@ LOCAL_HIRES_PROTOTYPES = {
     "vpr_hires_patch_rerank_fp8": LOCAL_PROTOTYPES["vpr_local_rerank"],
 }
 
+# include/vpr_amd_spatial.h, the twelfth table: spatial verification of the patch matches (a dominant-shift vote on the grid)
+SPATIAL_MAX_N, SPATIAL_MAX_BINS, SPATIAL_MAX_TOL = 1369, 5329, 8     # VPR_SPATIAL_MAX_N, VPR_SPATIAL_MAX_BINS, VPR_SPATIAL_MAX_TOL
+SPATIAL_PROTOTYPES = {
+    "vpr_spatial_workspace_bytes": (c_size_t, [c_int] * 3),                 # B kc n_g
+    # partner sim | P n_q gw_q n_g gw_g tol | score inliers matches shift inlier_mask | stream
+    "vpr_spatial_verify": (c_int, [_P, _P] + [c_int] * 6 + [_P] * 6),
+    # q_local n_q | idx B kc | g_local n_g l n_local index_base min_sim | k_out vals_out idx_out inliers_out |
+    # pair_score pair_inliers pair_matches pair_shift row_nn col_nn | feat_is_fp8 gw_q gw_g tol | workspace workspace_bytes | stream
+    "vpr_spatial_local_rerank": (c_int, [_P, c_int, _P, c_int, c_int, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P, _P, _P]
+                                 + [_P] * 6 + [c_int] * 4 + [_P, c_size_t, _P]),
+}
+
 
 def local_hires_sum_roundings(n_g: int) -> int:
     """VPR_LOCAL_HIRES_SUM_ROUNDINGS: L_sum of the score summed in blocks of 256 columns."""
@@ -266,7 +278,8 @@ def lib() -> ctypes.CDLL:
                                           + list(RERANK_PROTOTYPES.items()) + list(SALAD_STAGES_PROTOTYPES.items())
                                           + list(SALAD_ANYRES_PROTOTYPES.items()) + list(SALAD_HIRES_PROTOTYPES.items())
                                           + list(LOCAL_PROTOTYPES.items()) + list(SALAD_F32_STAGES_PROTOTYPES.items())
-                                          + list(PATCH_FP8_PROTOTYPES.items()) + list(LOCAL_HIRES_PROTOTYPES.items())):
+                                          + list(PATCH_FP8_PROTOTYPES.items()) + list(LOCAL_HIRES_PROTOTYPES.items())
+                                          + list(SPATIAL_PROTOTYPES.items())):
             fn = getattr(handle, name)   # AttributeError if a declared symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

@@ -36,11 +36,14 @@ inline size_t lm_lds_bytes(int n_g, int l, int es) {
 
 // Elem = uint16_t: bf16 features, S = the accumulator.  Elem = uint8_t: e4m3 bytes of x * 2^8, S = 2^-16 * the accumulator.
 // The e4m3 form at l <= 128 asks for 4 waves per SIMD (<= 128 VGPRs): with its 49 KB of LDS two workgroups then share a CU.
-template <typename Elem, int L>
+// LIST: the match list match_q / match_sim is written as well (include/vpr_amd_spatial.h); a flag of the template, so that the
+// kernels of the calls without a list are compiled without a trace of it.
+template <typename Elem, int L, bool LIST>
 __global__ __launch_bounds__(LM_THREADS, (sizeof(Elem) == 1 && L <= 128) ? 4 : 1) void local_match_kernel(
     const Elem* __restrict__ q_local, int n_q, const int32_t* __restrict__ idx, int kc, const Elem* __restrict__ g_local,
     int n_g, int n_local, int index_base, float min_sim, float* __restrict__ ws_score, int32_t* __restrict__ ws_matches,
-    float* __restrict__ pair_score, int32_t* __restrict__ pair_matches, int32_t* __restrict__ row_nn, int32_t* __restrict__ col_nn) {
+    float* __restrict__ pair_score, int32_t* __restrict__ pair_matches, int32_t* __restrict__ row_nn, int32_t* __restrict__ col_nn,
+    int32_t* __restrict__ match_q, float* __restrict__ match_sim) {
   constexpr bool FP8 = sizeof(Elem) == 1;
   constexpr int EPC = 16 / sizeof(Elem);                              // elements per 16-byte chunk
   constexpr int CPR = L / EPC, KS = FP8 ? L / 64 : L / 16;            // chunks per row; MFMA k-steps
@@ -72,6 +75,7 @@ __global__ __launch_bounds__(LM_THREADS, (sizeof(Elem) == 1 && L <= 128) ? 4 : 1
       if (pair_matches && tid == 0) pair_matches[p] = 0;
       if (row_nn) for (int i = tid; i < n_q; i += LM_THREADS) row_nn[p * n_q + i] = -1;
       if (col_nn) for (int i = tid; i < n_g; i += LM_THREADS) col_nn[p * n_g + i] = -1;
+      if constexpr (LIST) for (int i = tid; i < n_g; i += LM_THREADS) { match_q[p * n_g + i] = -1; match_sim[p * n_g + i] = 0.f; }
     }
   }
   if (!any) return;                                                   // nothing of this group is local: no loads, no staging
@@ -190,21 +194,13 @@ __global__ __launch_bounds__(LM_THREADS, (sizeof(Elem) == 1 && L <= 128) ? 4 : 1
       }
       if (col_nn) col_nn[p * n_g + tid] = ci;
       if (ci >= 0 && s_rownn[ci] == tid && cv >= min_sim) { contrib = cv; matched = 1; }
+      if constexpr (LIST) { match_q[p * n_g + tid] = matched ? ci : -1; match_sim[p * n_g + tid] = contrib; }
     }
-    if (wave < 4) {                                                   // columns 0 .. 255
-      const float ws = wave_sum(contrib);
-      int wc = matched;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) wc += __shfl_xor(wc, o, 64);
-      if (lane == 0) { s_part[wave] = ws; s_cnt[wave] = wc; }
-    }
+    if (wave < 4) lm_block_partials(contrib, matched, 0, lane, wave, s_part, s_cnt);      // columns 0 .. 255: one block
     __syncthreads();
     if (tid == 0) {
-      float s = 0.f;
       int c = 0;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) { s += s_part[w]; c += s_cnt[w]; }
-      s = fminf(fmaxf(s, -FLT_MAX), FLT_MAX);                         // every term is finite; an overflowing sum is clamped
+      const float s = lm_fold_block(s_part, s_cnt, 0, c);
       ws_score[p] = s;
       ws_matches[p] = c;
       if (pair_score) pair_score[p] = s;
@@ -228,19 +224,55 @@ __global__ __launch_bounds__(ORDER_MAX_KC) void local_order_kernel(
   }
 }
 
-template <typename Elem, int L>
+template <typename Elem, int L, bool LIST>
 int launch_local_match(dim3 grid, size_t lds, hipStream_t s, const Elem* q_local, int n_q, const int32_t* idx, int kc,
                        const Elem* g_local, int n_g, int n_local, int index_base, float min_sim, float* ws_score,
-                       int32_t* ws_matches, float* pair_score, int32_t* pair_matches, int32_t* row_nn, int32_t* col_nn) {
-  VPR_TRY_LAUNCH((optin_dynamic_lds<local_match_kernel<Elem, L>>(lm_lds_bytes(LM_MAX_N, L, sizeof(Elem)))));   // the LDS size varies per call: the maximum
-  return launch_kernel(local_match_kernel<Elem, L>, grid, dim3(LM_THREADS), lds, s, q_local, n_q, idx, kc, g_local, n_g, n_local,
-                       index_base, min_sim, ws_score, ws_matches, pair_score, pair_matches, row_nn, col_nn);
+                       int32_t* ws_matches, float* pair_score, int32_t* pair_matches, int32_t* row_nn, int32_t* col_nn,
+                       int32_t* match_q, float* match_sim) {
+  VPR_TRY_LAUNCH((optin_dynamic_lds<local_match_kernel<Elem, L, LIST>>(lm_lds_bytes(LM_MAX_N, L, sizeof(Elem)))));   // the LDS size varies per call: the maximum
+  return launch_kernel(local_match_kernel<Elem, L, LIST>, grid, dim3(LM_THREADS), lds, s, q_local, n_q, idx, kc, g_local, n_g, n_local,
+                       index_base, min_sim, ws_score, ws_matches, pair_score, pair_matches, row_nn, col_nn, match_q, match_sim);
 }
 
 int launch_local_order(const float* scores, const int32_t* matches, const int32_t* idx, int B, int kc, int n_local, int index_base,
                        int k_out, float* vals_out, int32_t* idx_out, int32_t* matches_out, hipStream_t stream) {
   return launch_kernel(local_order_kernel, dim3((unsigned)B), dim3(ORDER_MAX_KC), 0, stream, scores, matches, idx, kc, n_local,
                        index_base, k_out, vals_out, idx_out, matches_out);
+}
+
+// The match launch of one element type: the kernel for the width, with (LIST: match_q and match_sim non-null) or without the
+// match list.  The arguments have passed lm_check (or the caller's own).
+template <typename Elem, bool LIST>
+int local_match_dispatch(const Elem* q_local, int n_q, const int32_t* idx, int B, int kc, const Elem* g_local, int n_g, int l,
+                         int n_local, int index_base, float min_sim, float* ws_score, int32_t* ws_matches, float* pair_score,
+                         int32_t* pair_matches, int32_t* row_nn, int32_t* col_nn, int32_t* match_q, float* match_sim, hipStream_t s) {
+  constexpr bool FP8 = sizeof(Elem) == 1;
+  const dim3 grid((unsigned)B, (unsigned)((kc + LM_GROUP - 1) / LM_GROUP));
+  const size_t lds = lm_lds_bytes(n_g, l, sizeof(Elem));
+#define LM_CASE(LL) case LL: return launch_local_match<Elem, LL, LIST>(grid, lds, s, q_local, n_q, idx, kc, g_local, n_g, n_local, index_base, \
+    min_sim, ws_score, ws_matches, pair_score, pair_matches, row_nn, col_nn, match_q, match_sim);
+  if constexpr (FP8) {
+    switch (l) {
+      LM_CASE(64) LM_CASE(128) LM_CASE(192) LM_CASE(256)
+      default: return VPR_ERR_UNSUPPORTED;
+    }
+  } else {
+    switch (l) {
+      LM_CASE(32) LM_CASE(64) LM_CASE(96) LM_CASE(128) LM_CASE(160) LM_CASE(192) LM_CASE(224) LM_CASE(256)
+      default: return VPR_ERR_UNSUPPORTED;
+    }
+  }
+#undef LM_CASE
+}
+
+int launch_local_match_list(bool fp8, const void* q_local, int n_q, const int32_t* idx, int B, int kc, const void* g_local, int n_g,
+                            int l, int n_local, int index_base, float min_sim, float* ws_score, int32_t* ws_matches, int32_t* row_nn,
+                            int32_t* col_nn, int32_t* match_q, float* match_sim, hipStream_t stream) {
+  if (fp8)
+    return local_match_dispatch<uint8_t, true>(static_cast<const uint8_t*>(q_local), n_q, idx, B, kc, static_cast<const uint8_t*>(g_local), n_g, l,
+                                n_local, index_base, min_sim, ws_score, ws_matches, nullptr, nullptr, row_nn, col_nn, match_q, match_sim, stream);
+  return local_match_dispatch<uint16_t, true>(static_cast<const uint16_t*>(q_local), n_q, idx, B, kc, static_cast<const uint16_t*>(g_local), n_g, l,
+                              n_local, index_base, min_sim, ws_score, ws_matches, nullptr, nullptr, row_nn, col_nn, match_q, match_sim, stream);
 }
 
 // The checks and the two launches of both element types; l_step = the width's granule (32 bf16, 64 e4m3).
@@ -257,22 +289,8 @@ int local_rerank_run(const Elem* q_local, int n_q, const int32_t* idx, int B, in
   float* ws_score = static_cast<float*>(workspace);
   int32_t* ws_matches = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + lm_ws_half(B, kc));
   const hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)B, (unsigned)((kc + LM_GROUP - 1) / LM_GROUP));
-  const size_t lds = lm_lds_bytes(n_g, l, sizeof(Elem));
-#define LM_CASE(LL) case LL: VPR_TRY_LAUNCH((launch_local_match<Elem, LL>(grid, lds, s, q_local, n_q, idx, kc, g_local, n_g, n_local, \
-    index_base, min_sim, ws_score, ws_matches, pair_score, pair_matches, row_nn, col_nn))); break;
-  if constexpr (FP8) {
-    switch (l) {
-      LM_CASE(64) LM_CASE(128) LM_CASE(192) LM_CASE(256)
-      default: return VPR_ERR_UNSUPPORTED;
-    }
-  } else {
-    switch (l) {
-      LM_CASE(32) LM_CASE(64) LM_CASE(96) LM_CASE(128) LM_CASE(160) LM_CASE(192) LM_CASE(224) LM_CASE(256)
-      default: return VPR_ERR_UNSUPPORTED;
-    }
-  }
-#undef LM_CASE
+  VPR_TRY_LAUNCH((local_match_dispatch<Elem, false>(q_local, n_q, idx, B, kc, g_local, n_g, l, n_local, index_base, min_sim, ws_score, ws_matches,
+                                      pair_score, pair_matches, row_nn, col_nn, nullptr, nullptr, s)));
   VPR_TRY_LAUNCH(launch_local_order(ws_score, ws_matches, idx, B, kc, n_local, index_base, k_out, vals_out, idx_out, matches_out, s));
   return VPR_OK;
 }

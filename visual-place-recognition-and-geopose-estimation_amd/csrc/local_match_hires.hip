@@ -39,11 +39,15 @@ inline size_t lh_lds_bytes(int n_q, int n_g, int l, int es) {
   return cw * l * es + 2 * LM_WAVES * cw * 4 + 8 * (ngp + nqp) + 2 * LH_MAX_BLOCKS * 4 * 4;
 }
 
-template <typename Elem, int L>
-__global__ __launch_bounds__(LM_THREADS, 1) void local_match_hires_kernel(
+// LIST: the match list match_q / match_sim is written as well (include/vpr_amd_spatial.h); a flag of the template, as in
+// local_match.hip.  The e4m3 form at l <= 128 fits two workgroups into a CU's LDS and needs <= 128 VGPRs for the second one;
+// without the list it is compiled to exactly 128, with it the bound has to be asked for.
+template <typename Elem, int L, bool LIST>
+__global__ __launch_bounds__(LM_THREADS, (LIST && sizeof(Elem) == 1 && L <= 128) ? 4 : 1) void local_match_hires_kernel(
     const Elem* __restrict__ q_local, int n_q, const int32_t* __restrict__ idx, int kc, const Elem* __restrict__ g_local,
     int n_g, int n_local, int index_base, float min_sim, float* __restrict__ ws_score, int32_t* __restrict__ ws_matches,
-    float* __restrict__ pair_score, int32_t* __restrict__ pair_matches, int32_t* __restrict__ row_nn, int32_t* __restrict__ col_nn) {
+    float* __restrict__ pair_score, int32_t* __restrict__ pair_matches, int32_t* __restrict__ row_nn, int32_t* __restrict__ col_nn,
+    int32_t* __restrict__ match_q, float* __restrict__ match_sim) {
   constexpr bool FP8 = sizeof(Elem) == 1;
   constexpr int EPC = 16 / sizeof(Elem);                              // elements per 16-byte chunk
   constexpr int CPR = L / EPC, KS = FP8 ? L / 64 : L / 16;            // 16-byte chunks per row; MFMA k-steps
@@ -80,6 +84,7 @@ __global__ __launch_bounds__(LM_THREADS, 1) void local_match_hires_kernel(
     if (pair_matches && tid == 0) pair_matches[p] = 0;
     if (row_nn) for (int i = tid; i < n_q; i += LM_THREADS) row_nn[p * n_q + i] = -1;
     if (col_nn) for (int i = tid; i < n_g; i += LM_THREADS) col_nn[p * n_g + i] = -1;
+    if constexpr (LIST) for (int i = tid; i < n_g; i += LM_THREADS) { match_q[p * n_g + i] = -1; match_sim[p * n_g + i] = 0.f; }
     return;                                                           // not local: no loads, no staging
   }
   const Elem* gimg = g_local + grow * n_g * L;                        // 0 <= grow < n_local: inside g_local
@@ -222,25 +227,16 @@ __global__ __launch_bounds__(LM_THREADS, 1) void local_match_hires_kernel(
         const int ci = s_ci[col];
         if (col_nn) col_nn[p * n_g + col] = ci;
         if (ci >= 0 && s_rowi[ci] == col && cv >= min_sim) { contrib = cv; matched = 1; }
+        if constexpr (LIST) { match_q[p * n_g + col] = matched ? ci : -1; match_sim[p * n_g + col] = contrib; }
       }
-      const float ws = wave_sum(contrib);
-      int wc = matched;
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) wc += __shfl_xor(wc, o, 64);
-      if (lane == 0) { s_part[t * 4 + wave] = ws; s_cnt[t * 4 + wave] = wc; }
+      lm_block_partials(contrib, matched, t, lane, wave, s_part, s_cnt);
     }
   }
   __syncthreads();
   if (tid == 0) {
-    float run = 0.f;
-    int c = 0;
-    for (int t = 0; t < ncb; ++t) {
-      float s = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) { s += s_part[t * 4 + w]; c += s_cnt[t * 4 + w]; }
-      s = fminf(fmaxf(s, -FLT_MAX), FLT_MAX);                         // every term is finite; an overflowing sum is clamped
-      run = fminf(fmaxf(run + s, -FLT_MAX), FLT_MAX);
-    }
+    float run;
+    int c;
+    lm_fold_blocks(s_part, s_cnt, ncb, run, c);
     ws_score[p] = run;
     ws_matches[p] = c;
     if (pair_score) pair_score[p] = run;
@@ -248,13 +244,52 @@ __global__ __launch_bounds__(LM_THREADS, 1) void local_match_hires_kernel(
   }
 }
 
-template <typename Elem, int L>
+template <typename Elem, int L, bool LIST>
 int launch_local_match_hires(dim3 grid, size_t lds, hipStream_t s, const Elem* q_local, int n_q, const int32_t* idx, int kc,
                              const Elem* g_local, int n_g, int n_local, int index_base, float min_sim, float* ws_score,
-                             int32_t* ws_matches, float* pair_score, int32_t* pair_matches, int32_t* row_nn, int32_t* col_nn) {
-  VPR_TRY_LAUNCH((optin_dynamic_lds<local_match_hires_kernel<Elem, L>>(lh_lds_bytes(LH_MAX_N, LH_MAX_N, L, sizeof(Elem)))));   // the LDS size varies per call: the maximum
-  return launch_kernel(local_match_hires_kernel<Elem, L>, grid, dim3(LM_THREADS), lds, s, q_local, n_q, idx, kc, g_local, n_g,
-                       n_local, index_base, min_sim, ws_score, ws_matches, pair_score, pair_matches, row_nn, col_nn);
+                             int32_t* ws_matches, float* pair_score, int32_t* pair_matches, int32_t* row_nn, int32_t* col_nn,
+                             int32_t* match_q, float* match_sim) {
+  VPR_TRY_LAUNCH((optin_dynamic_lds<local_match_hires_kernel<Elem, L, LIST>>(lh_lds_bytes(LH_MAX_N, LH_MAX_N, L, sizeof(Elem)))));   // the LDS size varies per call: the maximum
+  return launch_kernel(local_match_hires_kernel<Elem, L, LIST>, grid, dim3(LM_THREADS), lds, s, q_local, n_q, idx, kc, g_local, n_g,
+                       n_local, index_base, min_sim, ws_score, ws_matches, pair_score, pair_matches, row_nn, col_nn, match_q, match_sim);
+}
+
+// The match launch of one element type: the kernel for the width, with (LIST: match_q and match_sim non-null) or without the
+// match list.  The arguments have passed lm_check (or the caller's own).
+template <typename Elem, bool LIST>
+int local_match_hires_dispatch(const Elem* q_local, int n_q, const int32_t* idx, int B, int kc, const Elem* g_local, int n_g, int l,
+                               int n_local, int index_base, float min_sim, float* ws_score, int32_t* ws_matches, float* pair_score,
+                               int32_t* pair_matches, int32_t* row_nn, int32_t* col_nn, int32_t* match_q, float* match_sim,
+                               hipStream_t s) {
+  constexpr bool FP8 = sizeof(Elem) == 1;
+  const dim3 grid((unsigned)B, (unsigned)kc);
+  const size_t lds = lh_lds_bytes(n_q, n_g, l, sizeof(Elem));
+#define LH_CASE(LL) case LL: return launch_local_match_hires<Elem, LL, LIST>(grid, lds, s, q_local, n_q, idx, kc, g_local, n_g, n_local, \
+    index_base, min_sim, ws_score, ws_matches, pair_score, pair_matches, row_nn, col_nn, match_q, match_sim);
+  if constexpr (FP8) {
+    switch (l) {
+      LH_CASE(64) LH_CASE(128) LH_CASE(192) LH_CASE(256)
+      default: return VPR_ERR_UNSUPPORTED;
+    }
+  } else {
+    switch (l) {
+      LH_CASE(32) LH_CASE(64) LH_CASE(96) LH_CASE(128) LH_CASE(160) LH_CASE(192) LH_CASE(224) LH_CASE(256)
+      default: return VPR_ERR_UNSUPPORTED;
+    }
+  }
+#undef LH_CASE
+}
+
+int launch_local_match_hires_list(bool fp8, const void* q_local, int n_q, const int32_t* idx, int B, int kc, const void* g_local,
+                                  int n_g, int l, int n_local, int index_base, float min_sim, float* ws_score, int32_t* ws_matches,
+                                  int32_t* row_nn, int32_t* col_nn, int32_t* match_q, float* match_sim, hipStream_t stream) {
+  if (fp8)
+    return local_match_hires_dispatch<uint8_t, true>(static_cast<const uint8_t*>(q_local), n_q, idx, B, kc, static_cast<const uint8_t*>(g_local), n_g,
+                                      l, n_local, index_base, min_sim, ws_score, ws_matches, nullptr, nullptr, row_nn, col_nn, match_q,
+                                      match_sim, stream);
+  return local_match_hires_dispatch<uint16_t, true>(static_cast<const uint16_t*>(q_local), n_q, idx, B, kc, static_cast<const uint16_t*>(g_local), n_g,
+                                    l, n_local, index_base, min_sim, ws_score, ws_matches, nullptr, nullptr, row_nn, col_nn, match_q,
+                                    match_sim, stream);
 }
 
 // The checks and the two launches of both element types.
@@ -271,22 +306,8 @@ int local_rerank_hires_run(const Elem* q_local, int n_q, const int32_t* idx, int
   float* ws_score = static_cast<float*>(workspace);
   int32_t* ws_matches = reinterpret_cast<int32_t*>(static_cast<char*>(workspace) + lm_ws_half(B, kc));
   const hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)B, (unsigned)kc);
-  const size_t lds = lh_lds_bytes(n_q, n_g, l, sizeof(Elem));
-#define LH_CASE(LL) case LL: VPR_TRY_LAUNCH((launch_local_match_hires<Elem, LL>(grid, lds, s, q_local, n_q, idx, kc, g_local, n_g, \
-    n_local, index_base, min_sim, ws_score, ws_matches, pair_score, pair_matches, row_nn, col_nn))); break;
-  if constexpr (FP8) {
-    switch (l) {
-      LH_CASE(64) LH_CASE(128) LH_CASE(192) LH_CASE(256)
-      default: return VPR_ERR_UNSUPPORTED;
-    }
-  } else {
-    switch (l) {
-      LH_CASE(32) LH_CASE(64) LH_CASE(96) LH_CASE(128) LH_CASE(160) LH_CASE(192) LH_CASE(224) LH_CASE(256)
-      default: return VPR_ERR_UNSUPPORTED;
-    }
-  }
-#undef LH_CASE
+  VPR_TRY_LAUNCH((local_match_hires_dispatch<Elem, false>(q_local, n_q, idx, B, kc, g_local, n_g, l, n_local, index_base, min_sim, ws_score,
+                                            ws_matches, pair_score, pair_matches, row_nn, col_nn, nullptr, nullptr, s)));
   VPR_TRY_LAUNCH(launch_local_order(ws_score, ws_matches, idx, B, kc, n_local, index_base, k_out, vals_out, idx_out, matches_out, s));
   return VPR_OK;
 }

@@ -414,7 +414,8 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
                                tau: float = 25.0, mode: str = "top1", batch_size: int = 64, device: str = "cuda", graph: bool = True,
                                image_size: int = 224, rank: int = 0, world: int = 1, group=None, verbose: bool = True,
                                on_device: bool = False, query_expansion=None, rerank: Optional[int] = None,
-                               local_rerank: Optional[int] = None, min_sim: float = 0.0, local_hires: bool = False) -> dict:
+                               local_rerank: Optional[int] = None, min_sim: float = 0.0, local_hires: bool = False,
+                               spatial_tol: Optional[int] = None) -> dict:
     """Validation split through descriptor -> sharded cosine top-k -> label transfer:
       pose      (lat, lon, angle) of the best match, or the softmax-weighted mean of the k matches (gallery.label_transfer);
       final_loss on lat/lon with the validation scripts' formula (dinov2salad_validation.py:101), MAAE on the angle
@@ -438,10 +439,15 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
     (local_features_fp8.npy, keep_local="fp8") is matched in that form: the queries' features are features(want_local="fp8").
     local_hires (with local_rerank): the gallery's and the queries' images hold up to 1369 patch tokens (a gallery built with
     build_gallery_from_images(local_hires=True); features(hires=True) and ShardedGallery(local_hires=True)); per image the
-    gallery then keeps 135 KB bf16 or 68 KB e4m3 at 322 px, 350 KB or 175 KB at 518 px."""
+    gallery then keeps 135 KB bf16 or 68 KB e4m3 at 322 px, 350 KB or 175 KB at 518 px.
+    spatial_tol (with local_rerank; 0..8): the matches are verified spatially (include/vpr_amd_spatial.h;
+    ShardedGallery.search_local_reranked(spatial_tol=)) on the patch grid of `image_size`, image_size // 14 wide on both sides;
+    topk_scores are then the verified scores."""
     from . import gallery as G
     from .retrieval import ShardedGallery
     _check_grid(extractor, image_size)
+    if spatial_tol is not None and local_rerank is None:
+        raise ValueError("calculate_retrieval_scores: spatial_tol verifies the matches of local_rerank; name its kc")
     dev = torch.device(device)
     extractor = extractor.to(dev).to(torch.bfloat16).eval()
     if local_rerank is not None and (rerank is not None or query_expansion is not None):
@@ -460,7 +466,7 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
     # offline evaluation: unconditionally exact neighbours (queries the device certificate flags are re-run on f64 scores)
     sg = ShardedGallery(shard.rows, shard.n_total, rank, world, group=group, scales=shard.scales, exact_fallback=True,
                         projection=shard.projection, fine_rows=fine, local_feats=shard.local,
-                        local_hires=local_hires)
+                        local_hires=local_hires, local_grid=None if spatial_tol is None else image_size // 14)
     df = _existing_rows(val_csv_path, image_dir)
     names = df["filename"].tolist()
     prep = ResizeNormalize(image_size, "bilinear", HALF_MEAN, HALF_STD, torch.bfloat16)
@@ -475,6 +481,8 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
         _, d16, *feats = fwd(prep(u8))
         if local_rerank is not None:
             two_tier = {"local_rerank": int(local_rerank), "q_local_feats": feats[0], "min_sim": float(min_sim)}
+            if spatial_tol is not None:
+                two_tier["spatial_tol"] = int(spatial_tol)
         v, i = sg.search_local_queries(d16, kk, query_expansion, **two_tier)
         sel = torch.tensor(idxs, device=dev)
         vals[sel], idx[sel] = v, i

@@ -92,6 +92,11 @@ class HipEngine:
         """local_rerank_fp8 for up to 1369 patches on either side (vpr_hires_patch_rerank_fp8): (vals, idx, matches) [B, k]."""
         return torch.ops.vpr.local_rerank_fp8_hires(q_local_feats, idx, local_feats, index_base, k, min_sim)
 
+    def local_rerank_spatial(self, q_local_feats, idx, local_feats, index_base, k, min_sim=0.0, gw_q=1, gw_g=1, tol=1):
+        """The local re-ranking of either element type with spatial verification, up to 1369 patches on either side
+        (vpr_spatial_local_rerank): (vals, idx, inliers) [B, k]."""
+        return torch.ops.vpr.local_rerank_spatial(q_local_feats, idx, local_feats, gw_q, gw_g, tol, index_base, k, min_sim)
+
     def quantize_patch_fp8(self, feats):
         """Local features bf16 or f32 -> their e4m3 store, uint8 of the same shape (vpr_patch_quantize_fp8)."""
         return torch.ops.vpr.patch_quantize_fp8(feats.contiguous())
@@ -157,7 +162,7 @@ class ShardedGallery:
                  engine=None, group: Optional[dist.ProcessGroup] = None, scales: Optional[torch.Tensor] = None,
                  norm_bound: Optional[float] = None, force_collectives: bool = False, exact_fallback: bool = False,
                  projection=None, fine_rows: Optional[torch.Tensor] = None, local_feats: Optional[torch.Tensor] = None,
-                 local_hires: bool = False):
+                 local_hires: bool = False, local_grid: Optional[int] = None):
         """local_rows: [n_local, D] bf16, or uint8 e4m3 bytes with per-row f32 `scales` (value = scale * fp8).
         norm_bound: upper bound of the (dequantised) row norms for the exactness certificate; None = L2-normalised
         descriptors (what SALAD emits); `measure_norm_bound()` computes it from the rows.
@@ -176,7 +181,10 @@ class ShardedGallery:
         search_local_reranked matches the queries' patches against (include/vpr_amd_local.h); nothing else reads them.  uint8:
         their e4m3 store (include/vpr_amd_patch_fp8.h; half the bytes), matched by the e4m3 form of the same stage.
         local_hires: search_local_reranked (and what runs it: search_gathered, search_local_queries, GraphedRetrieval) takes up
-        to 1369 patches per image on either side instead of 256 (include/vpr_amd_local_hires.h; 322 to 518 px images)."""
+        to 1369 patches per image on either side instead of 256 (include/vpr_amd_local_hires.h; 322 to 518 px images).
+        local_grid: the width gw of the patch grid that local_feats' n patches lie on in raster order (img_size // 14, as
+        SaladAggregator.local_features emits them); what search_local_reranked(spatial_tol=) verifies the matches on
+        (include/vpr_amd_spatial.h).  None: the gallery has no grid and takes no spatial search."""
         lo, hi = shard_bounds(n_total, rank, world)
         if local_rows.shape[0] != hi - lo:
             raise ValueError(f"rank {rank}: shard has {local_rows.shape[0]} rows, expected {hi - lo}")
@@ -197,6 +205,13 @@ class ShardedGallery:
                                  f"got {tuple(local_feats.shape)}")
             if local_feats.dtype not in (torch.bfloat16, torch.uint8):
                 raise ValueError(f"local_feats: bf16 or uint8 (e4m3 bytes), got {local_feats.dtype}")
+        if local_grid is not None:
+            if local_feats is None:
+                raise ValueError("local_grid: the width of the patch grid of local_feats; this gallery has none")
+            local_grid = int(local_grid)
+            if not 1 <= local_grid <= local_feats.shape[1] or local_feats.shape[1] % local_grid:
+                raise ValueError(f"local_grid: {local_grid} does not divide the {local_feats.shape[1]} patches of an image")
+        self.local_grid = local_grid
         self.local_feats = local_feats
         self.local_hires = bool(local_hires)
         self.fine_rows = fine_rows
@@ -293,7 +308,8 @@ class ShardedGallery:
         return self._merged(*self.engine.rerank(q_fine, i.contiguous(), self.fine_rows, self.index_base, k))
 
     def search_local_reranked(self, q_all: torch.Tensor, k: int, kc: int, q_local_feats: torch.Tensor, min_sim: float = 0.0,
-                              ws=None, score_events=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                              ws=None, score_events=None, spatial_tol: Optional[int] = None,
+                              q_grid: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Local-feature re-ranking (include/vpr_amd_local.h): the coarse local search of this shard for kc candidates
         (k <= kc <= 64, through the projection if there is one), those candidates re-ranked to k by the summed similarity of
         the mutual-nearest-neighbour patch pairs (similarity >= min_sim) between q_local_feats [B, n_q, l] bf16 and the shard's
@@ -304,7 +320,11 @@ class ShardedGallery:
         global coarse top-kc.  With one shard that is the coarse top-kc itself.  Values are local scores (always finite).
         A gallery of e4m3 local features (uint8 `local_feats`) takes q_local_feats as bf16, quantised here, or as uint8.
         A gallery made with local_hires=True takes up to 1369 patches on either side; when either side exceeds 256 the match
-        runs on the engine's local_rerank_hires / local_rerank_fp8_hires, otherwise on the 256-patch entries as always."""
+        runs on the engine's local_rerank_hires / local_rerank_fp8_hires, otherwise on the 256-patch entries as always.
+        spatial_tol (0..8; None: no verification): only the matches within spatial_tol bins of the pair's dominant shift on the
+        patch grids count (include/vpr_amd_spatial.h; the engine's local_rerank_spatial, which routes by the patch counts
+        itself).  The gallery's grid is its local_grid; q_grid is the width of the queries' grid, None: the gallery's (the
+        queries then hold as many patches as the gallery's images)."""
         if self.local_feats is None:
             raise ValueError("search_local_reranked: this gallery has no local_feats")
         if not 1 <= kc <= 64:
@@ -326,8 +346,25 @@ class ShardedGallery:
         if not self.local_hires and n_max > 256:
             raise ValueError("search_local_reranked: at most 256 patches per image")
         hires = n_max > _lib.LOCAL_MAX_N
+        if spatial_tol is not None:
+            if self.local_grid is None:
+                raise ValueError("search_local_reranked: spatial_tol needs the gallery's patch grid: ShardedGallery(local_grid=gw)")
+            if q_grid is None and q_local_feats.shape[1] != self.local_feats.shape[1]:
+                raise ValueError("search_local_reranked: the queries hold another number of patches than the gallery's images; "
+                                 "name their grid's width (q_grid)")
+            gw_q = self.local_grid if q_grid is None else int(q_grid)
+            try:
+                ops._spatial_grid_check("search_local_reranked", q_local_feats.shape[1], gw_q, self.local_feats.shape[1],
+                                        self.local_grid, spatial_tol)
+            except RuntimeError as e:
+                raise ValueError(str(e)) from None
+        elif q_grid is not None:
+            raise ValueError("search_local_reranked: q_grid is the queries' grid of a spatial search (spatial_tol)")
         _, i = self._local(self.project_queries(q_all), kc, ws, score_events)
-        if fp8:
+        if spatial_tol is not None:
+            v, i, _ = self.engine.local_rerank_spatial(self.local_query_feats(q_local_feats), i.contiguous(), self.local_feats,
+                                                       self.index_base, k, min_sim, gw_q, self.local_grid, int(spatial_tol))
+        elif fp8:
             entry = self.engine.local_rerank_fp8_hires if hires else self.engine.local_rerank_fp8
             v, i, _ = entry(self.local_query_feats(q_local_feats), i.contiguous(), self.local_feats, self.index_base, k, min_sim)
         else:
@@ -381,19 +418,22 @@ class ShardedGallery:
     def search_gathered(self, q_all: torch.Tensor, k: int, expand=None, rerank: Optional[int] = None,
                         q_fine: Optional[torch.Tensor] = None, ws=None, ws2=None,
                         score_events=None, local_rerank: Optional[int] = None, q_local_feats: Optional[torch.Tensor] = None,
-                        min_sim: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+                        min_sim: float = 0.0, spatial_tol: Optional[int] = None,
+                        q_grid: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """The search that (expand, rerank) name, over queries that are the same on every rank: `search`, `search_reranked`
         (rerank = kc) or `search_expanded` (expand: anything expansion_params takes; with rerank, of its last search).
         q_fine, ws, ws2, score_events: as those take them; an expanded search has no seam for score_events.
         local_rerank = kc: `search_local_reranked` with q_local_feats and min_sim; it is a second stage of its own and combines
-        neither with rerank= nor with expand= (ValueError)."""
+        neither with rerank= nor with expand= (ValueError).  spatial_tol, q_grid: of that search; without local_rerank a ValueError."""
         expand = expansion_params(expand)
+        if spatial_tol is not None and local_rerank is None:
+            raise ValueError("search_gathered: spatial_tol verifies the matches of local_rerank; name its kc")
         if local_rerank is not None:
             if rerank is not None:
                 raise ValueError("search_gathered: local_rerank and rerank are two kinds of second stage; name one of them")
             if expand is not None:
                 raise ValueError("search_gathered: local_rerank does not combine with expand")
-            return self.search_local_reranked(q_all, k, local_rerank, q_local_feats, min_sim, ws, score_events)
+            return self.search_local_reranked(q_all, k, local_rerank, q_local_feats, min_sim, ws, score_events, spatial_tol, q_grid)
         if expand is not None:
             if score_events is not None:
                 raise ValueError("search_gathered: score_events cannot be collected around an expanded search")
@@ -404,7 +444,8 @@ class ShardedGallery:
 
     def search_local_queries(self, q_local: torch.Tensor, k: int, expand=None, rerank: Optional[int] = None, *,
                              ws=None, ws2=None, score_events=None, local_rerank: Optional[int] = None,
-                             q_local_feats: Optional[torch.Tensor] = None, min_sim: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+                             q_local_feats: Optional[torch.Tensor] = None, min_sim: float = 0.0,
+                             spatial_tol: Optional[int] = None, q_grid: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Data-parallel form: each rank contributes B_local queries and gets back its own rows — project, gather, search
         (search_gathered), keep this rank's rows.  The eager callers and GraphedRetrieval all go through here.
         expand: None, or the query expansion to search with (expansion_params).
@@ -413,6 +454,7 @@ class ShardedGallery:
         local_rerank = kc: the local-feature form (search_local_reranked) with this rank's q_local_feats [B_local, n_q, l] bf16,
         gathered across the ranks like the queries when the gallery is collective; not together with rerank= or expand=.
         With e4m3 local features in the gallery, bf16 ones are quantised before that gather (half the bytes travel).
+        spatial_tol, q_grid: the spatial verification of that form (search_local_reranked).
         ws, ws2, score_events: handed to search_gathered."""
         if local_rerank is not None and rerank is not None:
             raise ValueError("search_local_queries: local_rerank and rerank are two kinds of second stage; name one of them")
@@ -427,7 +469,8 @@ class ShardedGallery:
         if local_rerank is not None:
             bf16 = isinstance(q_local_feats, torch.Tensor) and q_local_feats.dtype == torch.bfloat16 and q_local_feats.dim() == 3
             feats_all = self.gather_queries(self.local_query_feats(q_local_feats) if bf16 else q_local_feats.contiguous())
-        v, i = self.search_gathered(q_all, k, expand, rerank, q_fine, ws, ws2, score_events, local_rerank, feats_all, min_sim)
+        v, i = self.search_gathered(q_all, k, expand, rerank, q_fine, ws, ws2, score_events, local_rerank, feats_all, min_sim,
+                                    spatial_tol, q_grid)
         b = q_local.shape[0]
         return v[self.rank * b:(self.rank + 1) * b], i[self.rank * b:(self.rank + 1) * b]
 
@@ -464,12 +507,20 @@ class GraphedRetrieval:
     local_rerank (kc): the graph holds the local-feature form, ShardedGallery.search_local_reranked (not with `rerank` or
     `expand`): `self.q_feats` [B_local, n, l] bf16 (n, l: the gallery's) is a second static input,
     filled by __call__(q_local, q_local_feats); vals are local scores.  A gallery of e4m3 local features makes it uint8:
-    __call__ takes bf16 features, quantised into it before the replay, or uint8 ones."""
+    __call__ takes bf16 features, quantised into it before the replay, or uint8 ones.
+    spatial_tol (with local_rerank): the graph holds the spatially verified form (search_local_reranked(spatial_tol=)) on a
+    gallery made with local_grid; the queries lie on the gallery's grid."""
 
     def __init__(self, gallery: ShardedGallery, batch_local: int, k: int, labels=None, mode: str = "top1",
                  temperature: float = 0.01, scaler=None, expand=None, rerank: Optional[int] = None,
-                 local_rerank: Optional[int] = None, min_sim: float = 0.0):
+                 local_rerank: Optional[int] = None, min_sim: float = 0.0, spatial_tol: Optional[int] = None):
         self.g, self.k = gallery, k
+        self.spatial_tol = None if spatial_tol is None else int(spatial_tol)
+        if self.spatial_tol is not None:
+            if local_rerank is None:
+                raise ValueError("GraphedRetrieval: spatial_tol verifies the matches of local_rerank; name its kc")
+            if gallery.local_grid is None:
+                raise ValueError("GraphedRetrieval: spatial_tol needs the gallery's patch grid: ShardedGallery(local_grid=gw)")
         self.rerank = None if rerank is None else int(rerank)
         self.local_rerank = None if local_rerank is None else int(local_rerank)
         self.min_sim, self.q_feats = float(min_sim), None
@@ -507,7 +558,8 @@ class GraphedRetrieval:
 
     def _run(self):
         v, i = self.g.search_local_queries(self.q, self.k, self.expand, self.rerank, ws=self.ws, ws2=self.ws2,
-                                           local_rerank=self.local_rerank, q_local_feats=self.q_feats, min_sim=self.min_sim)
+                                           local_rerank=self.local_rerank, q_local_feats=self.q_feats, min_sim=self.min_sim,
+                                           spatial_tol=self.spatial_tol)
         if self.labels is not None:
             self.pose64, self.pose4 = transfer_pose(v, i, self.labels, self.mode, self.temperature, self.scaler)
         return v, i

@@ -16,6 +16,7 @@ that seam, so the HIP hot path is visible to PyTorch's dispatcher like any other
     torch.ops.vpr.local_rerank                         (local-feature re-ranking: mutual-nearest-neighbour patch matches)
     torch.ops.vpr.patch_quantize_fp8 / local_rerank_fp8   (the same on e4m3 patch features: half the feature store)
     torch.ops.vpr.local_rerank_hires / local_rerank_fp8_hires   (both for up to 1369 patches per image: 322 to 518 px)
+    torch.ops.vpr.spatial_verify / local_rerank_spatial   (matches count only within the dominant shift of the patch grid)
     torch.ops.vpr.pose_head / ln_meanpool_head
     torch.ops.vpr.head_train_epoch                     (head-only fine-tuning pass; mutates parameters and AdamW moments)
     torch.ops.vpr.head_train_epoch_dropout             (the same pass with Dropout(p) after the ReLU, training mode)
@@ -333,6 +334,38 @@ local_rerank_hires.register_fake(_local_rerank_fake)          # the output shape
 local_rerank_fp8_hires.register_fake(_local_rerank_fake)
 
 
+@torch.library.custom_op("vpr::spatial_verify", mutates_args=())
+def spatial_verify(partner: Tensor, sim: Tensor, n_q: int, gw_q: int, gw_g: int, tol: int = 1) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Spatial verification of a match list: partner int32 [P, n_g] (the query patch of candidate column j; outside 0..n_q-1:
+    no match), sim f32 [P, n_g], grids gw_q / gw_g wide -> (score f32 [P], inliers int32 [P], matches int32 [P], shift int32
+    [P, 2], inlier_mask uint8 [P, n_g]): the matches within tol bins of the dominant grid shift.  vpr_spatial_verify."""
+    return tuple(ops.spatial_verify(partner, sim, n_q, gw_q, gw_g, tol, want_mask=True))
+
+
+@spatial_verify.register_fake
+def _(partner, sim, n_q, gw_q, gw_g, tol=1):
+    P, n_g = partner.shape
+    ops._spatial_grid_check("spatial_verify", n_q, gw_q, n_g, gw_g, tol)
+    new = lambda shape, dtype: partner.new_empty(shape, dtype=dtype)
+    return (new((P,), torch.float32), new((P,), torch.int32), new((P,), torch.int32), new((P, 2), torch.int32),
+            new((P, n_g), torch.uint8))
+
+
+@torch.library.custom_op("vpr::local_rerank_spatial", mutates_args=())
+def local_rerank_spatial(q_local: Tensor, idx: Tensor, g_local: Tensor, gw_q: int, gw_g: int, tol: int = 1, index_base: int = 0,
+                         k: Optional[int] = None, min_sim: float = 0.0) -> Tuple[Tensor, Tensor, Tensor]:
+    """local_rerank_hires (bf16 features) or local_rerank_fp8_hires (uint8 e4m3 bytes) with spatial verification: only the
+    matches within tol bins of the pair's dominant shift on the gw_q / gw_g wide patch grids count -> (scores f32, indices
+    int32, inliers int32), each [B, k].  vpr_spatial_local_rerank."""
+    return ops.local_rerank_spatial(q_local, idx, g_local, gw_q, gw_g, tol, index_base, k, min_sim)
+
+
+@local_rerank_spatial.register_fake
+def _(q_local, idx, g_local, gw_q, gw_g, tol=1, index_base=0, k=None, min_sim=0.0):
+    ops._spatial_grid_check("local_rerank_spatial", q_local.shape[1], gw_q, g_local.shape[1], gw_g, tol)
+    return _local_rerank_fake(q_local, idx, g_local, index_base, k, min_sim)
+
+
 # ------------------------------------------------------------------------------------------------------------ heads
 @torch.library.custom_op("vpr::pose_head", mutates_args=())
 def pose_head(x: Tensor, W1: Optional[Tensor], b1: Optional[Tensor], W2: Tensor, b2: Tensor, sincos_offset: int) -> Tensor:
@@ -406,4 +439,5 @@ def _(X, Y, order, batch_size, W1, b1, W2, b2, m, v, first_step, lr, beta1, beta
 OPS = ("head_train_epoch", "head_train_epoch_dropout", "salad_aggregate", "salad_aggregate_split", "salad_aggregate_f32", "salad_aggregate_train", "knn_topk", "knn_topk_fp8", "quantize_fp8_rows",
        "topk_merge", "pose_head", "ln_meanpool_head", "retrieval_pose", "query_expand", "query_expand_finish", "project_rows",
        "rerank_rows", "salad_aggregate_n", "salad_aggregate_f32_n", "salad_aggregate_hires", "salad_aggregate_f32_hires",
-       "local_rerank", "patch_quantize_fp8", "local_rerank_fp8", "local_rerank_hires", "local_rerank_fp8_hires")
+       "local_rerank", "patch_quantize_fp8", "local_rerank_fp8", "local_rerank_hires", "local_rerank_fp8_hires",
+       "spatial_verify", "local_rerank_spatial")
