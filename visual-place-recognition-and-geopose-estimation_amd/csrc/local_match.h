@@ -1,7 +1,6 @@
-// local_match.h — what the two local-feature match kernels share (local_match.hip: up to 256 patches, a candidate whole in LDS;
-// local_match_hires.hip: up to 1369, tiled over both patch axes): the comparison of the argmax folds, the swizzle of the staged
-// features, the workspace rule, the argument checks in the order both contracts state, the score's block sum (also the
-// verification kernel's, spatial.hip), and the launches that other files use: the order stage and the match launch alone.
+// local_match.h — what local_match.hip (the two local-feature match kernels, their one launch path, the order stage) shares with
+// spatial.hip: the workspace rule, the argument checks in the order the contracts state, the score's block sum (also the
+// verification kernel's), and the two launches spatial.hip uses: the match launch with the match list, and the order stage.
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -11,27 +10,6 @@
 #include "../../include/vpr_amd_patch_fp8.h"
 
 namespace vpr {
-
-constexpr int LM_WAVES = 8;                         // = 256 / 32 row tiles of a row block
-constexpr int LM_THREADS = LM_WAVES * WAVE;
-
-// a beats b: a exists and (b does not, or a's value is larger, or equal with the lower index)
-__device__ __forceinline__ bool lm_better(float av, int ai, float bv, int bi) {
-  return ai >= 0 && (bi < 0 || av > bv || (av == bv && ai < bi));
-}
-
-// Swizzle of the staged features: chunk c of row r (a row is CPR chunks of 16 B: L / 8 for bf16, L / 16 for e4m3) sits at
-// chunk c ^ f(r) of its row, f(r) = (r >> SH) & MASK with (SH, MASK) = (0, 15) if 16 | CPR, (1, 7) if 8 | CPR, else (2, 3): the
-// 16 rows of a ds_read_b128 lane group at one logical chunk fall into 16 distinct 16-byte slots of the 256-byte bank row.  CPR
-// is a multiple of 4, and f(r) stays below the largest power of two (<= 16) dividing CPR: the XOR stays inside the row, and
-// chunks 2 m and 2 m + 1 (the two reads of an e4m3 operand) stay a pair.  Restated and checked exhaustively on the host for
-// every supported width of both elements (tests/test_local_match_fp8_cpu.py).
-template <int CPR>
-__device__ __forceinline__ int lm_off(int row, int chunk) {
-  static_assert(CPR % 4 == 0 && CPR <= 32, "a row is a whole number of 64-byte groups");
-  constexpr int SH = CPR % 16 == 0 ? 0 : CPR % 8 == 0 ? 1 : 2, MASK = CPR % 16 == 0 ? 15 : CPR % 8 == 0 ? 7 : 3;
-  return (row * CPR + (chunk ^ ((row >> SH) & MASK))) << 4;
-}
 
 inline size_t lm_ws_half(int B, int kc) { return align_up((size_t)(B > 0 ? B : 1) * kc * sizeof(float), 256); }
 inline size_t lm_ws_bytes(int B, int kc) {
@@ -109,14 +87,11 @@ __device__ __forceinline__ void lm_fold_blocks(const float* s_part, const int* s
 int launch_local_order(const float* scores, const int32_t* matches, const int32_t* idx, int B, int kc, int n_local, int index_base,
                        int k_out, float* vals_out, int32_t* idx_out, int32_t* matches_out, hipStream_t stream);
 
-// The match launch alone of either element type (fp8: e4m3 bytes), for a caller that has checked its arguments; the form for
-// up to 256 patches is in local_match.hip, the one for up to 1369 in local_match_hires.hip.  match_q / match_sim [B, kc, n_g],
-// both or neither: the match list, c(j) and S[c(j)][j] of a matched column, (-1, +0) of any other and of a non-live candidate.
+// The match launch alone of either element type (fp8: e4m3 bytes), for a caller that has checked its arguments against the
+// limits of include/vpr_amd_local_hires.h; local_match.hip chooses the kernel.  match_q / match_sim [B, kc, n_g], both non-null:
+// the match list, c(j) and S[c(j)][j] of a matched column, (-1, +0) of any other and of a non-live candidate.
 int launch_local_match_list(bool fp8, const void* q_local, int n_q, const int32_t* idx, int B, int kc, const void* g_local, int n_g,
                             int l, int n_local, int index_base, float min_sim, float* ws_score, int32_t* ws_matches, int32_t* row_nn,
                             int32_t* col_nn, int32_t* match_q, float* match_sim, hipStream_t stream);
-int launch_local_match_hires_list(bool fp8, const void* q_local, int n_q, const int32_t* idx, int B, int kc, const void* g_local,
-                                  int n_g, int l, int n_local, int index_base, float min_sim, float* ws_score, int32_t* ws_matches,
-                                  int32_t* row_nn, int32_t* col_nn, int32_t* match_q, float* match_sim, hipStream_t stream);
 
 }  // namespace vpr

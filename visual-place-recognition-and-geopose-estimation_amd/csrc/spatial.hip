@@ -8,8 +8,8 @@
 //           a per-thread fold, the xor butterfly of a wave, the four waves through LDS;
 //   score   thread j - 256 t owns column j of block t, as in the match kernels: lm_block_partials / lm_fold_blocks of
 //           local_match.h, the same code, so that a pair whose matches are all inliers reproduces their score bit for bit.
-// vpr_spatial_local_rerank: the match launch of local_match.hip (both sides <= 256 patches) or local_match_hires.hip with the
-// match list as its extra output, this file's verify launch, and the order stage with the inlier counts as its payload.
+// vpr_spatial_local_rerank: the match launch of local_match.hip (which chooses between its two kernels by the patch count) with
+// the match list as its extra output, this file's verify launch, and the order stage with the inlier counts as its payload.
 #include <limits.h>
 #include "local_match.h"
 #include "../../include/vpr_amd_local_hires.h"
@@ -203,13 +203,8 @@ extern "C" int vpr_spatial_local_rerank(const void* q_local, int n_q, const int3
   float* list_sim = reinterpret_cast<float*>(ws + lm_ws_bytes(B, kc) + sv_ws_list(B, kc, n_g));
   const hipStream_t s = static_cast<hipStream_t>(stream);
   // the match kernels leave the unverified score and match count in ws_score / ws_count; the verify launch replaces them
-  if (n_q <= VPR_LOCAL_MAX_N && n_g <= VPR_LOCAL_MAX_N) {
-    VPR_TRY_LAUNCH(launch_local_match_list(feat_is_fp8 != 0, q_local, n_q, idx, B, kc, g_local, n_g, l, n_local, index_base, min_sim, ws_score,
-                                           ws_count, row_nn, col_nn, list_q, list_sim, s));
-  } else {
-    VPR_TRY_LAUNCH(launch_local_match_hires_list(feat_is_fp8 != 0, q_local, n_q, idx, B, kc, g_local, n_g, l, n_local, index_base, min_sim,
-                                                 ws_score, ws_count, row_nn, col_nn, list_q, list_sim, s));
-  }
+  VPR_TRY_LAUNCH(launch_local_match_list(feat_is_fp8 != 0, q_local, n_q, idx, B, kc, g_local, n_g, l, n_local, index_base, min_sim, ws_score,
+                                         ws_count, row_nn, col_nn, list_q, list_sim, s));
   VPR_TRY_LAUNCH(launch_spatial_verify(list_q, list_sim, (long long)B * kc, n_q, gw_q, n_g, gw_g, tol, idx, n_local, index_base, ws_score,
                                        ws_count, pair_score, pair_inliers, pair_matches, pair_shift, nullptr, s));
   VPR_TRY_LAUNCH(launch_local_order(ws_score, ws_count, idx, B, kc, n_local, index_base, k_out, vals_out, idx_out, inliers_out, s));
