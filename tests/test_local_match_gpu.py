@@ -48,7 +48,7 @@ ALL = ("row_nn", "col_nn", "pair_matches", "pair_score", "vals", "idx", "matches
 SHAPES = [(1, 1, 1, 1, 1, 32), (3, 7, 1, 31, 33, 32), (3, 8, 8, 32, 32, 64), (3, 9, 9, 33, 31, 64), (1, 7, 7, 64, 65, 128),
           (1, 8, 1, 65, 64, 256), (3, 9, 9, 196, 196, 128), (1, 7, 7, 255, 256, 256), (1, 8, 8, 256, 255, 128), (1, 9, 1, 256, 256, 256),
           (37, 64, 64, 31, 32, 32), (37, 128, 128, 1, 33, 32), (3, 128, 1, 33, 1, 64), (1, 64, 64, 196, 255, 32), (3, 1, 1, 256, 196, 64),
-          (1, 9, 9, 64, 256, 96)]
+          (1, 9, 9, 64, 256, 96), (1, 7, 7, 65, 33, 160), (3, 8, 1, 33, 255, 192), (1, 9, 9, 255, 65, 224)]
 
 
 @pytest.mark.parametrize("B,kc,k,n_q,n_g,l", SHAPES)
