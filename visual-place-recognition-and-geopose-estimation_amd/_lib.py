@@ -246,6 +246,17 @@ SPATIAL_PROTOTYPES = {
                                  + [_P] * 6 + [c_int] * 4 + [_P, c_size_t, _P]),
 }
 
+# include/vpr_amd_similarity.h, the thirteenth table: the patch matches verified under scale, rotation and shift (256 two-match
+# hypotheses of a similarity transform)
+SIM_MAX_N, SIM_MAX_SIDE, SIM_HYPOTHESES, SIM_MAX_SCALE, SIM_MAX_TOL = 1369, 37, 256, 2, 8   # the VPR_SIM_* macros
+SIMILARITY_PROTOTYPES = {
+    "vpr_similarity_workspace_bytes": (c_size_t, [c_int] * 3),              # B kc n_g
+    # partner sim | P n_q gw_q n_g gw_g tol | score inliers matches model inlier_mask | stream
+    "vpr_similarity_verify": (c_int, [_P, _P] + [c_int] * 6 + [_P] * 6),
+    # the parameter list of vpr_spatial_local_rerank; pair_model in the place of pair_shift
+    "vpr_similarity_local_rerank": SPATIAL_PROTOTYPES["vpr_spatial_local_rerank"],
+}
+
 
 def local_hires_sum_roundings(n_g: int) -> int:
     """VPR_LOCAL_HIRES_SUM_ROUNDINGS: L_sum of the score summed in blocks of 256 columns."""
@@ -279,7 +290,7 @@ def lib() -> ctypes.CDLL:
                                           + list(SALAD_ANYRES_PROTOTYPES.items()) + list(SALAD_HIRES_PROTOTYPES.items())
                                           + list(LOCAL_PROTOTYPES.items()) + list(SALAD_F32_STAGES_PROTOTYPES.items())
                                           + list(PATCH_FP8_PROTOTYPES.items()) + list(LOCAL_HIRES_PROTOTYPES.items())
-                                          + list(SPATIAL_PROTOTYPES.items())):
+                                          + list(SPATIAL_PROTOTYPES.items()) + list(SIMILARITY_PROTOTYPES.items())):
             fn = getattr(handle, name)   # AttributeError if a declared symbol is not exported
             fn.restype = restype
             fn.argtypes = argtypes

@@ -1,6 +1,7 @@
 // local_match.h — what local_match.hip (the two local-feature match kernels, their one launch path, the order stage) shares with
-// spatial.hip: the workspace rule, the argument checks in the order the contracts state, the score's block sum (also the
-// verification kernel's), and the two launches spatial.hip uses: the match launch with the match list, and the order stage.
+// the verification stages spatial.hip and similarity.hip: the workspace rules, the argument checks in the order the contracts
+// state, the score's block sum (also the verification kernels'), and the two launches the verified calls use: the match launch
+// with the match list, and the order stage.
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -8,6 +9,7 @@
 #include "vpr_internal.h"
 #include "../../include/vpr_amd_local.h"
 #include "../../include/vpr_amd_patch_fp8.h"
+#include "../../include/vpr_amd_local_hires.h"
 
 namespace vpr {
 
@@ -17,8 +19,15 @@ inline size_t lm_ws_bytes(int B, int kc) {
   return 2 * lm_ws_half(B, kc);                                       // f32 scores | i32 match counts
 }
 
+// The workspace of a verified call (spatial.hip, similarity.hip): the order stage's arrays, then the match list.
+inline size_t sv_ws_list(int B, int kc, int n_g) { return align_up((size_t)(B > 0 ? B : 1) * kc * n_g * sizeof(int32_t), 256); }
+inline size_t sv_ws_bytes(int B, int kc, int n_g) {
+  if (lm_ws_bytes(B, kc) == 0 || n_g < 1 || n_g > VPR_LOCAL_HIRES_MAX_N) return 0;
+  return lm_ws_bytes(B, kc) + 2 * sv_ws_list(B, kc, n_g);            // f32 scores | i32 counts | i32 partners | f32 similarities
+}
+
 // The status of a call, in the order the headers state; VPR_OK = launch.  max_n = the form's patch limit, l_step = the
-// width's granule (32 bf16, 64 e4m3).  Three parts, so that a call with arguments of its own (spatial.hip) can append its
+// width's granule (32 bf16, 64 e4m3).  Three parts, so that a call with arguments of its own (spatial.hip, similarity.hip) can append its
 // refusals to each group: the invalid arguments, the unsupported shapes, the alignment.
 inline int lm_check_args(const void* q_local, int n_q, const int32_t* idx, int B, int kc, const void* g_local, int n_g, int l,
                          int n_local, int index_base, float min_sim, int k_out, const float* vals_out, const int32_t* idx_out,
@@ -54,7 +63,7 @@ inline int lm_check(const void* q_local, int n_q, const int32_t* idx, int B, int
 }
 
 // The score sum that the three contracts state (vpr_amd_local.h inside a block of 256 columns, vpr_amd_local_hires.h over the
-// blocks), shared by the two match kernels and the verification kernel (spatial.hip).
+// blocks), shared by the two match kernels and the verification kernels (spatial.hip, similarity.hip).
 // lm_block_partials: waves 0 .. 3, block t: thread j - 256 t holds column j's contribution (+0 where it does not count) and
 // whether it counts; the wave_sum butterfly, the wave's sum and count to s_part / s_cnt [t][4].
 __device__ __forceinline__ void lm_block_partials(float contrib, int counted, int t, int lane, int wave, float* s_part, int* s_cnt) {

@@ -150,12 +150,6 @@ inline int sv_check_grid(int n_q, int gw_q, int n_g, int gw_g, int tol) {
   return VPR_OK;
 }
 
-inline size_t sv_ws_list(int B, int kc, int n_g) { return align_up((size_t)(B > 0 ? B : 1) * kc * n_g * sizeof(int32_t), 256); }
-inline size_t sv_ws_bytes(int B, int kc, int n_g) {
-  if (lm_ws_bytes(B, kc) == 0 || n_g < 1 || n_g > SV_MAX_N) return 0;
-  return lm_ws_bytes(B, kc) + 2 * sv_ws_list(B, kc, n_g);            // f32 scores | i32 counts | i32 partners | f32 similarities
-}
-
 inline int launch_spatial_verify(const int32_t* partner, const float* sim, long long P, int n_q, int gw_q, int n_g, int gw_g, int tol,
                                  const int32_t* idx, int n_local, int index_base, float* ws_score, int32_t* ws_inliers, float* score,
                                  int32_t* inliers, int32_t* matches, int32_t* shift, uint8_t* inlier_mask, hipStream_t s) {

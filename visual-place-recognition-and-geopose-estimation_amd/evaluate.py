@@ -415,7 +415,7 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
                                image_size: int = 224, rank: int = 0, world: int = 1, group=None, verbose: bool = True,
                                on_device: bool = False, query_expansion=None, rerank: Optional[int] = None,
                                local_rerank: Optional[int] = None, min_sim: float = 0.0, local_hires: bool = False,
-                               spatial_tol: Optional[int] = None) -> dict:
+                               spatial_tol: Optional[int] = None, spatial_model: str = "shift") -> dict:
     """Validation split through descriptor -> sharded cosine top-k -> label transfer:
       pose      (lat, lon, angle) of the best match, or the softmax-weighted mean of the k matches (gallery.label_transfer);
       final_loss on lat/lon with the validation scripts' formula (dinov2salad_validation.py:101), MAAE on the angle
@@ -442,9 +442,11 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
     gallery then keeps 135 KB bf16 or 68 KB e4m3 at 322 px, 350 KB or 175 KB at 518 px.
     spatial_tol (with local_rerank; 0..8): the matches are verified spatially (include/vpr_amd_spatial.h;
     ShardedGallery.search_local_reranked(spatial_tol=)) on the patch grid of `image_size`, image_size // 14 wide on both sides;
-    topk_scores are then the verified scores."""
+    topk_scores are then the verified scores.  spatial_model (with spatial_tol): "shift", or "similarity" for the verification
+    under one scale, rotation and shift (include/vpr_amd_similarity.h), as search_local_reranked takes it."""
     from . import gallery as G
-    from .retrieval import ShardedGallery
+    from .retrieval import ShardedGallery, _spatial_model
+    _spatial_model("calculate_retrieval_scores", spatial_model, spatial_tol)
     _check_grid(extractor, image_size)
     if spatial_tol is not None and local_rerank is None:
         raise ValueError("calculate_retrieval_scores: spatial_tol verifies the matches of local_rerank; name its kc")
@@ -483,6 +485,8 @@ def calculate_retrieval_scores(extractor: DinoV2Salad, gallery_dir: str, val_csv
             two_tier = {"local_rerank": int(local_rerank), "q_local_feats": feats[0], "min_sim": float(min_sim)}
             if spatial_tol is not None:
                 two_tier["spatial_tol"] = int(spatial_tol)
+                if spatial_model != "shift":                 # the default names nothing: the call is the one it always was
+                    two_tier["spatial_model"] = spatial_model
         v, i = sg.search_local_queries(d16, kk, query_expansion, **two_tier)
         sel = torch.tensor(idxs, device=dev)
         vals[sel], idx[sel] = v, i

@@ -7,6 +7,7 @@ only.  Any non-zero status raises RuntimeError — there is no eager/CPU fallbac
 from __future__ import annotations
 
 import ctypes
+import math
 from dataclasses import dataclass
 from typing import NamedTuple, Optional, Tuple
 
@@ -1169,6 +1170,121 @@ def local_rerank_spatial(q_local: torch.Tensor, idx: torch.Tensor, g_local: torc
                                  i32(B, kc, n_q), i32(B, kc, n_g))
     if B:
         _call("vpr_spatial_local_rerank", _ptr(q_local), n_q, _ptr(idx), B, kc, _ptr(g_local), n_g, l, n_local, int(index_base),
+              min_sim, k, _ptr(vals), _ptr(out), _ptr(inliers), *[_ptr(t) for t in (dbg or (None,) * 6)], int(fp8), gw_q, gw_g, tol,
+              _ptr(ws), ws.numel(), _stream())
+    return (vals, out, inliers, dbg) if debug else (vals, out, inliers)
+
+
+# ---- verification under a similarity transform (include/vpr_amd_similarity.h) ----
+def _similarity_grid_check(what: str, n_q: int, gw_q, n_g: int, gw_g, tol) -> Tuple[int, int, int]:
+    """The grid rules of include/vpr_amd_similarity.h: each gw divides its n, 0 <= tol <= 8, every grid side at most 37."""
+    gw_q, gw_g, tol = int(gw_q), int(gw_g), int(tol)
+    for n, gw, name in ((n_q, gw_q, "gw_q"), (n_g, gw_g, "gw_g")):
+        if not 1 <= gw <= n or n % gw:
+            raise RuntimeError(f"{what}: {name} must be a grid width in 1..{n} that divides the {n} patches of an image, got {gw}")
+    if not 0 <= tol <= _lib.SIM_MAX_TOL:
+        raise RuntimeError(f"{what}: tol must be in 0..{_lib.SIM_MAX_TOL}, got {tol}")
+    for n, gw, name in ((n_q, gw_q, "query"), (n_g, gw_g, "candidate")):
+        if max(gw, n // gw) > _lib.SIM_MAX_SIDE:
+            raise RuntimeError(f"{what}: the {name} grid is {gw} x {n // gw}; a grid side is at most {_lib.SIM_MAX_SIDE}")
+    return gw_q, gw_g, tol
+
+
+class SimilarityVerify(NamedTuple):
+    """The outputs of vpr_similarity_verify per pair: score f32 [P], inliers / matches int32 [P], model int32 [P, 6] = (h, the
+    column of m_s, the column of m_t, re, im, |dg|^2) of the winning hypothesis (six times INT32_MIN without a model),
+    inlier_mask uint8 [P, n_g] or None."""
+    score: torch.Tensor
+    inliers: torch.Tensor
+    matches: torch.Tensor
+    model: torch.Tensor
+    inlier_mask: Optional[torch.Tensor]
+
+
+def similarity_model_scale_rotation(model_row) -> Optional[Tuple[float, float]]:
+    """A model row (h, column of m_s, column of m_t, re, im, |dg|^2) on the host -> (scale, rotation in degrees) of the
+    transform that takes candidate positions to query positions: |re + i im| / |dg|^2 and atan2(im, re).  None for the row of
+    a pair without a model (INT32_MIN throughout)."""
+    _, _, _, re_, im, n2g = (int(v) for v in model_row)
+    if n2g <= 0:
+        return None
+    return math.hypot(re_, im) / n2g, math.degrees(math.atan2(im, re_))
+
+
+def similarity_verify(partner: torch.Tensor, sim: torch.Tensor, n_q: int, gw_q: int, gw_g: int, tol: int = 1,
+                      want_mask: bool = False) -> SimilarityVerify:
+    """The verification stage on its own (include/vpr_amd_similarity.h): partner int32 [P, n_g] (the query patch matched to
+    candidate column j; anything outside 0..n_q-1 is no match) and sim f32 [P, n_g]; the query grid is gw_q wide with n_q
+    patches, the candidate's gw_g wide.  256 two-match hypotheses of scale (1/2..2), rotation (+-45 degrees) and shift; the
+    matches within tol patches of the best one's prediction are the inliers, the score is the f32 sum of their similarities in
+    the order of include/vpr_amd_local_hires.h."""
+    _need(partner, torch.int32, "partner", 2)
+    _need(sim, torch.float32, "sim", 2)
+    if partner.shape != sim.shape or partner.device != sim.device:
+        raise RuntimeError("similarity_verify: partner and sim must have one shape and live on one device")
+    P, n_g = partner.shape
+    n_q = int(n_q)
+    for n, name in ((n_q, "n_q"), (n_g, "n_g")):
+        if not 1 <= n <= _lib.SIM_MAX_N:
+            raise RuntimeError(f"similarity_verify: {name} must be in 1..{_lib.SIM_MAX_N}, got {n}")
+    gw_q, gw_g, tol = _similarity_grid_check("similarity_verify", n_q, gw_q, n_g, gw_g, tol)
+    dev = partner.device
+    out = SimilarityVerify(torch.empty(P, dtype=torch.float32, device=dev), torch.empty(P, dtype=torch.int32, device=dev),
+                           torch.empty(P, dtype=torch.int32, device=dev), torch.empty((P, 6), dtype=torch.int32, device=dev),
+                           torch.empty((P, n_g), dtype=torch.uint8, device=dev) if want_mask else None)
+    if P:
+        _call("vpr_similarity_verify", _ptr(partner), _ptr(sim), P, n_q, gw_q, n_g, gw_g, tol, *[_ptr(t) for t in out], _stream())
+    return out
+
+
+class SimilarityRerankDebug(NamedTuple):
+    """The optional outputs of vpr_similarity_local_rerank, candidate order: pair_score f32 / pair_inliers / pair_matches int32
+    [B, kc], pair_model int32 [B, kc, 6] ((-inf, 0, 0, six times INT32_MIN) for a candidate the shard does not own;
+    similarity_model_scale_rotation reads a row), row_nn int32 [B, kc, n_q] / col_nn int32 [B, kc, n_g] (-1: none, or not owned)."""
+    pair_score: torch.Tensor
+    pair_inliers: torch.Tensor
+    pair_matches: torch.Tensor
+    pair_model: torch.Tensor
+    row_nn: torch.Tensor
+    col_nn: torch.Tensor
+
+
+def local_rerank_similarity(q_local: torch.Tensor, idx: torch.Tensor, g_local: torch.Tensor, gw_q: int, gw_g: int, tol: int = 1,
+                            index_base: int = 0, k: Optional[int] = None, min_sim: float = 0.0, ws: Optional[torch.Tensor] = None,
+                            debug: bool = False):
+    """Local re-ranking verified under a similarity transform (include/vpr_amd_similarity.h): local_rerank_spatial's arguments.
+    Returns (vals f32 [B, k], idx int32 [B, k], inliers int32 [B, k]): a candidate's score is the sum over the mutual-NN matches
+    that lie within tol patches of where the pair's best scale-rotation-shift hypothesis puts them; inliers is their number.
+    debug=True: a fourth element, SimilarityRerankDebug.  ws: a byte buffer of vpr_similarity_workspace_bytes(B, kc, n_g);
+    None: the current stream's cached one."""
+    what = "local_rerank_similarity"
+    if not isinstance(q_local, torch.Tensor) or q_local.dtype not in (torch.bfloat16, torch.uint8):
+        raise RuntimeError(f"{what}: q_local must be bf16 features or their uint8 e4m3 store")
+    fp8 = q_local.dtype == torch.uint8
+    k = _local_check(what, q_local, idx, g_local, k, q_local.dtype, _lib.PATCH_FP8_MIN_L if fp8 else 32, _lib.LOCAL_HIRES_MAX_N)
+    min_sim = float(min_sim)
+    if min_sim != min_sim:
+        raise RuntimeError(f"{what}: min_sim must be a number")
+    B, n_q, l = q_local.shape
+    n_local, n_g = g_local.shape[:2]
+    gw_q, gw_g, tol = _similarity_grid_check(what, n_q, gw_q, n_g, gw_g, tol)
+    kc = idx.shape[1]
+    dev = q_local.device
+    need = _lib.lib().vpr_similarity_workspace_bytes(B, kc, n_g)
+    if ws is None:
+        ws = workspace(what, need, dev)
+    else:
+        _need(ws, torch.uint8, "ws", 1)
+    vals = torch.empty((B, k), dtype=torch.float32, device=dev)
+    out = torch.empty((B, k), dtype=torch.int32, device=dev)
+    inliers = torch.empty((B, k), dtype=torch.int32, device=dev)
+    dbg = None
+    if debug:
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        dbg = SimilarityRerankDebug(torch.empty((B, kc), dtype=torch.float32, device=dev), i32(B, kc), i32(B, kc), i32(B, kc, 6),
+                                    i32(B, kc, n_q), i32(B, kc, n_g))
+    if B:
+        _call("vpr_similarity_local_rerank", _ptr(q_local), n_q, _ptr(idx), B, kc, _ptr(g_local), n_g, l, n_local, int(index_base),
               min_sim, k, _ptr(vals), _ptr(out), _ptr(inliers), *[_ptr(t) for t in (dbg or (None,) * 6)], int(fp8), gw_q, gw_g, tol,
               _ptr(ws), ws.numel(), _stream())
     return (vals, out, inliers, dbg) if debug else (vals, out, inliers)

@@ -97,6 +97,11 @@ class HipEngine:
         (vpr_spatial_local_rerank): (vals, idx, inliers) [B, k]."""
         return torch.ops.vpr.local_rerank_spatial(q_local_feats, idx, local_feats, gw_q, gw_g, tol, index_base, k, min_sim)
 
+    def local_rerank_similarity(self, q_local_feats, idx, local_feats, index_base, k, min_sim=0.0, gw_q=1, gw_g=1, tol=1):
+        """local_rerank_spatial with the matches verified under a similarity transform (scale, rotation and shift) instead of a
+        shift (vpr_similarity_local_rerank): (vals, idx, inliers) [B, k]."""
+        return torch.ops.vpr.local_rerank_similarity(q_local_feats, idx, local_feats, gw_q, gw_g, tol, index_base, k, min_sim)
+
     def quantize_patch_fp8(self, feats):
         """Local features bf16 or f32 -> their e4m3 store, uint8 of the same shape (vpr_patch_quantize_fp8)."""
         return torch.ops.vpr.patch_quantize_fp8(feats.contiguous())
@@ -155,6 +160,16 @@ def all_gather_topk(v: torch.Tensor, i: torch.Tensor, world: int, group=None):
     dist.all_gather_into_tensor(out, packed, group=group)                                   # the layout gloo and RCCL share
     out = out.view(world, B, 2 * k)
     return out[:, :, :k].contiguous().view(torch.float32), out[:, :, k:].contiguous()
+
+
+def _spatial_model(what: str, spatial_model, spatial_tol) -> bool:
+    """spatial_model of a search: "shift" (include/vpr_amd_spatial.h) or "similarity" (include/vpr_amd_similarity.h), which needs
+    a spatial_tol.  -> whether it is "similarity"."""
+    if spatial_model not in ("shift", "similarity"):
+        raise ValueError(f'{what}: spatial_model must be "shift" or "similarity", got {spatial_model!r}')
+    if spatial_model == "similarity" and spatial_tol is None:
+        raise ValueError(f'{what}: spatial_model="similarity" verifies the matches within spatial_tol patches; name spatial_tol')
+    return spatial_model == "similarity"
 
 
 class ShardedGallery:
@@ -309,7 +324,7 @@ class ShardedGallery:
 
     def search_local_reranked(self, q_all: torch.Tensor, k: int, kc: int, q_local_feats: torch.Tensor, min_sim: float = 0.0,
                               ws=None, score_events=None, spatial_tol: Optional[int] = None,
-                              q_grid: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                              q_grid: Optional[int] = None, spatial_model: str = "shift") -> Tuple[torch.Tensor, torch.Tensor]:
         """Local-feature re-ranking (include/vpr_amd_local.h): the coarse local search of this shard for kc candidates
         (k <= kc <= 64, through the projection if there is one), those candidates re-ranked to k by the summed similarity of
         the mutual-nearest-neighbour patch pairs (similarity >= min_sim) between q_local_feats [B, n_q, l] bf16 and the shard's
@@ -324,7 +339,11 @@ class ShardedGallery:
         spatial_tol (0..8; None: no verification): only the matches within spatial_tol bins of the pair's dominant shift on the
         patch grids count (include/vpr_amd_spatial.h; the engine's local_rerank_spatial, which routes by the patch counts
         itself).  The gallery's grid is its local_grid; q_grid is the width of the queries' grid, None: the gallery's (the
-        queries then hold as many patches as the gallery's images)."""
+        queries then hold as many patches as the gallery's images).
+        spatial_model (with spatial_tol): "shift", that vote; "similarity": the matches within spatial_tol patches of the pair's
+        best hypothesis of one scale, rotation and shift count instead (include/vpr_amd_similarity.h; the engine's
+        local_rerank_similarity), which holds under a zoom, where a shift vote smears; every grid side is then at most 37."""
+        similarity = _spatial_model("search_local_reranked", spatial_model, spatial_tol)
         if self.local_feats is None:
             raise ValueError("search_local_reranked: this gallery has no local_feats")
         if not 1 <= kc <= 64:
@@ -354,14 +373,17 @@ class ShardedGallery:
                                  "name their grid's width (q_grid)")
             gw_q = self.local_grid if q_grid is None else int(q_grid)
             try:
-                ops._spatial_grid_check("search_local_reranked", q_local_feats.shape[1], gw_q, self.local_feats.shape[1],
-                                        self.local_grid, spatial_tol)
+                grid_check = ops._similarity_grid_check if similarity else ops._spatial_grid_check
+                grid_check("search_local_reranked", q_local_feats.shape[1], gw_q, self.local_feats.shape[1], self.local_grid, spatial_tol)
             except RuntimeError as e:
                 raise ValueError(str(e)) from None
         elif q_grid is not None:
             raise ValueError("search_local_reranked: q_grid is the queries' grid of a spatial search (spatial_tol)")
         _, i = self._local(self.project_queries(q_all), kc, ws, score_events)
-        if spatial_tol is not None:
+        if similarity:
+            v, i, _ = self.engine.local_rerank_similarity(self.local_query_feats(q_local_feats), i.contiguous(), self.local_feats,
+                                                          self.index_base, k, min_sim, gw_q, self.local_grid, int(spatial_tol))
+        elif spatial_tol is not None:
             v, i, _ = self.engine.local_rerank_spatial(self.local_query_feats(q_local_feats), i.contiguous(), self.local_feats,
                                                        self.index_base, k, min_sim, gw_q, self.local_grid, int(spatial_tol))
         elif fp8:
@@ -419,13 +441,15 @@ class ShardedGallery:
                         q_fine: Optional[torch.Tensor] = None, ws=None, ws2=None,
                         score_events=None, local_rerank: Optional[int] = None, q_local_feats: Optional[torch.Tensor] = None,
                         min_sim: float = 0.0, spatial_tol: Optional[int] = None,
-                        q_grid: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                        q_grid: Optional[int] = None, spatial_model: str = "shift") -> Tuple[torch.Tensor, torch.Tensor]:
         """The search that (expand, rerank) name, over queries that are the same on every rank: `search`, `search_reranked`
         (rerank = kc) or `search_expanded` (expand: anything expansion_params takes; with rerank, of its last search).
         q_fine, ws, ws2, score_events: as those take them; an expanded search has no seam for score_events.
         local_rerank = kc: `search_local_reranked` with q_local_feats and min_sim; it is a second stage of its own and combines
-        neither with rerank= nor with expand= (ValueError).  spatial_tol, q_grid: of that search; without local_rerank a ValueError."""
+        neither with rerank= nor with expand= (ValueError).  spatial_tol, q_grid, spatial_model: of that search; without local_rerank a
+        ValueError."""
         expand = expansion_params(expand)
+        _spatial_model("search_gathered", spatial_model, spatial_tol)
         if spatial_tol is not None and local_rerank is None:
             raise ValueError("search_gathered: spatial_tol verifies the matches of local_rerank; name its kc")
         if local_rerank is not None:
@@ -433,7 +457,8 @@ class ShardedGallery:
                 raise ValueError("search_gathered: local_rerank and rerank are two kinds of second stage; name one of them")
             if expand is not None:
                 raise ValueError("search_gathered: local_rerank does not combine with expand")
-            return self.search_local_reranked(q_all, k, local_rerank, q_local_feats, min_sim, ws, score_events, spatial_tol, q_grid)
+            return self.search_local_reranked(q_all, k, local_rerank, q_local_feats, min_sim, ws, score_events, spatial_tol, q_grid,
+                                              spatial_model)
         if expand is not None:
             if score_events is not None:
                 raise ValueError("search_gathered: score_events cannot be collected around an expanded search")
@@ -445,7 +470,8 @@ class ShardedGallery:
     def search_local_queries(self, q_local: torch.Tensor, k: int, expand=None, rerank: Optional[int] = None, *,
                              ws=None, ws2=None, score_events=None, local_rerank: Optional[int] = None,
                              q_local_feats: Optional[torch.Tensor] = None, min_sim: float = 0.0,
-                             spatial_tol: Optional[int] = None, q_grid: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                             spatial_tol: Optional[int] = None, q_grid: Optional[int] = None,
+                             spatial_model: str = "shift") -> Tuple[torch.Tensor, torch.Tensor]:
         """Data-parallel form: each rank contributes B_local queries and gets back its own rows — project, gather, search
         (search_gathered), keep this rank's rows.  The eager callers and GraphedRetrieval all go through here.
         expand: None, or the query expansion to search with (expansion_params).
@@ -454,8 +480,9 @@ class ShardedGallery:
         local_rerank = kc: the local-feature form (search_local_reranked) with this rank's q_local_feats [B_local, n_q, l] bf16,
         gathered across the ranks like the queries when the gallery is collective; not together with rerank= or expand=.
         With e4m3 local features in the gallery, bf16 ones are quantised before that gather (half the bytes travel).
-        spatial_tol, q_grid: the spatial verification of that form (search_local_reranked).
+        spatial_tol, q_grid, spatial_model: the spatial verification of that form (search_local_reranked).
         ws, ws2, score_events: handed to search_gathered."""
+        _spatial_model("search_local_queries", spatial_model, spatial_tol)
         if local_rerank is not None and rerank is not None:
             raise ValueError("search_local_queries: local_rerank and rerank are two kinds of second stage; name one of them")
         if local_rerank is not None and (q_local_feats is None or q_local_feats.shape[0] != q_local.shape[0]):
@@ -470,7 +497,7 @@ class ShardedGallery:
             bf16 = isinstance(q_local_feats, torch.Tensor) and q_local_feats.dtype == torch.bfloat16 and q_local_feats.dim() == 3
             feats_all = self.gather_queries(self.local_query_feats(q_local_feats) if bf16 else q_local_feats.contiguous())
         v, i = self.search_gathered(q_all, k, expand, rerank, q_fine, ws, ws2, score_events, local_rerank, feats_all, min_sim,
-                                    spatial_tol, q_grid)
+                                    spatial_tol, q_grid, spatial_model)
         b = q_local.shape[0]
         return v[self.rank * b:(self.rank + 1) * b], i[self.rank * b:(self.rank + 1) * b]
 
@@ -509,12 +536,16 @@ class GraphedRetrieval:
     filled by __call__(q_local, q_local_feats); vals are local scores.  A gallery of e4m3 local features makes it uint8:
     __call__ takes bf16 features, quantised into it before the replay, or uint8 ones.
     spatial_tol (with local_rerank): the graph holds the spatially verified form (search_local_reranked(spatial_tol=)) on a
-    gallery made with local_grid; the queries lie on the gallery's grid."""
+    gallery made with local_grid; the queries lie on the gallery's grid.  spatial_model: "shift" or "similarity", as
+    search_local_reranked takes it."""
 
     def __init__(self, gallery: ShardedGallery, batch_local: int, k: int, labels=None, mode: str = "top1",
                  temperature: float = 0.01, scaler=None, expand=None, rerank: Optional[int] = None,
-                 local_rerank: Optional[int] = None, min_sim: float = 0.0, spatial_tol: Optional[int] = None):
+                 local_rerank: Optional[int] = None, min_sim: float = 0.0, spatial_tol: Optional[int] = None,
+                 spatial_model: str = "shift"):
         self.g, self.k = gallery, k
+        _spatial_model("GraphedRetrieval", spatial_model, spatial_tol)
+        self.spatial_model = spatial_model
         self.spatial_tol = None if spatial_tol is None else int(spatial_tol)
         if self.spatial_tol is not None:
             if local_rerank is None:
@@ -559,7 +590,7 @@ class GraphedRetrieval:
     def _run(self):
         v, i = self.g.search_local_queries(self.q, self.k, self.expand, self.rerank, ws=self.ws, ws2=self.ws2,
                                            local_rerank=self.local_rerank, q_local_feats=self.q_feats, min_sim=self.min_sim,
-                                           spatial_tol=self.spatial_tol)
+                                           spatial_tol=self.spatial_tol, spatial_model=self.spatial_model)
         if self.labels is not None:
             self.pose64, self.pose4 = transfer_pose(v, i, self.labels, self.mode, self.temperature, self.scaler)
         return v, i

@@ -17,6 +17,7 @@ that seam, so the HIP hot path is visible to PyTorch's dispatcher like any other
     torch.ops.vpr.patch_quantize_fp8 / local_rerank_fp8   (the same on e4m3 patch features: half the feature store)
     torch.ops.vpr.local_rerank_hires / local_rerank_fp8_hires   (both for up to 1369 patches per image: 322 to 518 px)
     torch.ops.vpr.spatial_verify / local_rerank_spatial   (matches count only within the dominant shift of the patch grid)
+    torch.ops.vpr.similarity_verify / local_rerank_similarity   (... or with one scale, rotation and shift of the patch grid)
     torch.ops.vpr.pose_head / ln_meanpool_head
     torch.ops.vpr.head_train_epoch                     (head-only fine-tuning pass; mutates parameters and AdamW moments)
     torch.ops.vpr.head_train_epoch_dropout             (the same pass with Dropout(p) after the ReLU, training mode)
@@ -366,6 +367,39 @@ def _(q_local, idx, g_local, gw_q, gw_g, tol=1, index_base=0, k=None, min_sim=0.
     return _local_rerank_fake(q_local, idx, g_local, index_base, k, min_sim)
 
 
+@torch.library.custom_op("vpr::similarity_verify", mutates_args=())
+def similarity_verify(partner: Tensor, sim: Tensor, n_q: int, gw_q: int, gw_g: int, tol: int = 1) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """Verification of a match list under a similarity transform: partner int32 [P, n_g] (the query patch of candidate column
+    j; outside 0..n_q-1: no match), sim f32 [P, n_g], grids gw_q / gw_g wide -> (score f32 [P], inliers int32 [P], matches
+    int32 [P], model int32 [P, 6], inlier_mask uint8 [P, n_g]): the matches within tol patches of the best two-match
+    hypothesis of scale, rotation and shift.  vpr_similarity_verify."""
+    return tuple(ops.similarity_verify(partner, sim, n_q, gw_q, gw_g, tol, want_mask=True))
+
+
+@similarity_verify.register_fake
+def _(partner, sim, n_q, gw_q, gw_g, tol=1):
+    P, n_g = partner.shape
+    ops._similarity_grid_check("similarity_verify", n_q, gw_q, n_g, gw_g, tol)
+    new = lambda shape, dtype: partner.new_empty(shape, dtype=dtype)
+    return (new((P,), torch.float32), new((P,), torch.int32), new((P,), torch.int32), new((P, 6), torch.int32),
+            new((P, n_g), torch.uint8))
+
+
+@torch.library.custom_op("vpr::local_rerank_similarity", mutates_args=())
+def local_rerank_similarity(q_local: Tensor, idx: Tensor, g_local: Tensor, gw_q: int, gw_g: int, tol: int = 1, index_base: int = 0,
+                            k: Optional[int] = None, min_sim: float = 0.0) -> Tuple[Tensor, Tensor, Tensor]:
+    """local_rerank_spatial's arguments, the matches verified under a similarity transform instead of a shift: only those
+    within tol patches of the pair's best scale-rotation-shift hypothesis count -> (scores f32, indices int32, inliers
+    int32), each [B, k].  vpr_similarity_local_rerank."""
+    return ops.local_rerank_similarity(q_local, idx, g_local, gw_q, gw_g, tol, index_base, k, min_sim)
+
+
+@local_rerank_similarity.register_fake
+def _(q_local, idx, g_local, gw_q, gw_g, tol=1, index_base=0, k=None, min_sim=0.0):
+    ops._similarity_grid_check("local_rerank_similarity", q_local.shape[1], gw_q, g_local.shape[1], gw_g, tol)
+    return _local_rerank_fake(q_local, idx, g_local, index_base, k, min_sim)
+
+
 # ------------------------------------------------------------------------------------------------------------ heads
 @torch.library.custom_op("vpr::pose_head", mutates_args=())
 def pose_head(x: Tensor, W1: Optional[Tensor], b1: Optional[Tensor], W2: Tensor, b2: Tensor, sincos_offset: int) -> Tensor:
@@ -440,4 +474,4 @@ OPS = ("head_train_epoch", "head_train_epoch_dropout", "salad_aggregate", "salad
        "topk_merge", "pose_head", "ln_meanpool_head", "retrieval_pose", "query_expand", "query_expand_finish", "project_rows",
        "rerank_rows", "salad_aggregate_n", "salad_aggregate_f32_n", "salad_aggregate_hires", "salad_aggregate_f32_hires",
        "local_rerank", "patch_quantize_fp8", "local_rerank_fp8", "local_rerank_hires", "local_rerank_fp8_hires",
-       "spatial_verify", "local_rerank_spatial")
+       "spatial_verify", "local_rerank_spatial", "similarity_verify", "local_rerank_similarity")
